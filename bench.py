@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the DiGA training hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-N = 1 runs in this process (headline + second arithmetic + the c4 / c5 / c1 legs + CPU baseline + bandwidth kernels + mIoU parity).
+A plain run measures the headline and nothing else: it sets up, runs W warm-up steps, times K steps (no HIP events around the
+launches), writes the last timed step's outputs if --dump-outputs is given and prints the result line.  --dump-outputs DIR writes
+what that step hands its caller -- the losses it returns and a fixed, seeded sample of the student's and the EMA teacher's state
+after it -- as DIR/<name>.npy (float32 / float64, 32 MB in all); the inputs are seeded, so two builds can be compared output for
+output.  --full adds everything else, as described below: the HIP-event kernel families and the serialised steps of the roofline,
+the second arithmetic, the c4 / c5 / c1 / translator legs, the CPU baseline, the bandwidth kernels and the mIoU parity.
+With --full, N = 1 runs in this process (headline + second arithmetic + the c4 / c5 / c1 legs + CPU baseline + bandwidth kernels + mIoU parity).
 N > 1 measures the headline configuration and the second arithmetic on every rank (the legs are 1-GPU results: --multi-gpu-legs runs
 them on all ranks too), no CPU-baseline child; rank 0 prints the same compact line.  N > 1: when the process was not started by torch.distributed.run (no WORLD_SIZE in
 the environment) it starts N worker processes itself -- before anything touches the GPU, as children, never by
@@ -110,7 +116,18 @@ def parse():
     ap.add_argument("--serial-streams", action="store_true",
                     help="run the whole step on one stream (no teacher / weight-gradient side stream): the mode the "
                          "per-kernel roofline durations are measured in; profiles/*_serial_* are rocprofv3 runs of it")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: kernel families and rooflines, the other arithmetic, the c4 / c5 / "
+                         "c1 / translator legs, the CPU baseline, the bandwidth kernels and the mIoU parity (the --no-* / --lean switches "
+                         "select among them); without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's losses and a seeded sample of the student's and the teacher's "
+                         "state as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        a.lean = a.no_prof = True
     if a.other_steps is None:
         a.other_steps = a.steps
     if a.other_warmup is None:
@@ -307,9 +324,39 @@ def geometry(a, config):
     return arch_name, B, H, W, block
 
 
-def run_steps(a, config, precision, steps, warmup, rank, world, dev, prof, graph=False):
+DUMP_SAMPLE = 1 << 22            # elements of each network's state kept by --dump-outputs (16 MB in float32)
+DUMP_SEED = 20240                # seed of the sampled positions: the same for every run and build
+
+
+def step_outputs(out, student, teacher):
+    """What the timed step hands its caller after its last call: the losses it returns (float64) and the two networks it updated in
+    place -- the student after its SGD step, the EMA teacher.  Each network's floating-point state (parameters and BatchNorm
+    statistics, state_dict order) is flattened to float32 and sampled at DUMP_SAMPLE seeded positions (ascending; all of it when smaller)."""
+    import numpy as np
+    import torch
+    arrays = {f"loss_{k}": torch.as_tensor(v).detach().to("cpu", torch.float64).reshape(-1).numpy() for k, v in out.items()}
+    for name, net in (("student", student), ("teacher", teacher)):
+        flat = torch.cat([t.detach().reshape(-1).float() for t in net.state_dict().values() if t.is_floating_point()])
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(DUMP_SEED)
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        arrays[f"{name}_state_sample"] = np.ascontiguousarray(flat.cpu().numpy(), dtype=np.float32)
+    return arrays
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def run_steps(a, config, precision, steps, warmup, rank, world, dev, prof, graph=False, dump=None):
     """Build student/teacher, run `warmup` + `steps` iterations of `config`; returns (seconds for `steps` = max over
-    ranks, kernel families, last losses, parameter counts, geometry)."""
+    ranks, kernel families, last losses, parameter counts, geometry).  `dump`: a dict that receives `step_outputs` of the
+    last timed step."""
     import torch
     from diga_amd import _lib, ddp, synthetic
     from diga_amd import config as dcfg
@@ -415,6 +462,8 @@ def run_steps(a, config, precision, steps, warmup, rank, world, dev, prof, graph
             raise SystemExit(f"rank {rank}: student parameters differ across ranks after the timed region: {[float(c) for c in allc]}")
     losses["_ranks_agree"] = agree
     losses["_peak_mem_gb"] = peak_mem
+    if dump is not None:
+        dump.update(step_outputs(out, student, teacher))       # (before the kernel-timing steps below move the networks on)
 
     def query(nsteps):
         fam = {}
@@ -714,8 +763,11 @@ def main():
     backend = torch.distributed.get_backend() if world > 1 else None
     prof = not a.no_prof
 
+    dump = {} if a.dump_outputs and rank == 0 else None
     dt, (families, families_ov), losses, counts, geom = run_steps(a, a.config, a.precision, a.steps, a.warmup, rank, world,
-                                                                  dev, prof, graph=bool(a.graph and world == 1))
+                                                                  dev, prof, graph=bool(a.graph and world == 1), dump=dump)
+    if dump is not None:
+        write_outputs(a.dump_outputs, dump)
     B, H, W, _ = geom
     other_line = None
     if not a.no_other_precision:
