@@ -72,6 +72,13 @@ SIGNATURES = {
     "diga_conv2d_wgrad_twin_workspace_bytes": (SZ, [I64] * 7),
     "diga_conv2d_wgrad_twin": (INT, [P, P, P, P, SZ] + [I64] * 15 + [P]),
     "diga_weight_transpose": (INT, [P, P, I64, I64, I64, P]),
+    "diga_make_triplet": (INT, [P, I64, P, I64, I64, P]),
+    "diga_split_bf16x6_image_bytes": (SZ, [I64, I64, I64]),
+    "diga_split_bf16x6_image": (INT, [P, P, I64, I64, I64, P]),
+    "diga_conv2d_nhwc_bf16x6": (INT, [P, P, P, P] + [I64] * 16 + [P, INT, P]),
+    "diga_conv2d_nhwc_bf16x6_epi": (INT, [P, P, P] + [I64] * 16 + [P, INT, P]),
+    "diga_conv2d_wgrad_bf16x6_workspace_bytes": (SZ, [I64] * 7),
+    "diga_conv2d_wgrad_bf16x6": (INT, [P, P, P, P, SZ] + [I64] * 15 + [P]),
     "diga_im2col_nchw": (INT, [P, P] + [I64] * 11 + [P]),
     "diga_norm_workspace_bytes": (SZ, [I64, I64, I64]),
     "diga_bn_fwd": (INT, [P, I64, P, I64, P, I64, P, P, P, P, P, P, P, I64, I64, INT, INT, INT, P, F32, F32, P, SZ, P]),
@@ -181,7 +188,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 
 # ---- conv arithmetic: host-side policy (the library keeps no process-wide mode; include/diga_hip.h, DIGA_CONV_MATH_*)
-CONV_MATH_F32, CONV_MATH_BF16X3 = 0, 1
+CONV_MATH_F32, CONV_MATH_BF16X3, CONV_MATH_BF16X6 = 0, 1, 2
 # (the mode is a field of the active configuration, diga_amd/config.py; DIGA_CONV_MATH gives its default)
 
 
@@ -189,13 +196,14 @@ def set_conv_math(mode, exact=None):
     """0 / "f32": fp32 operands and fp32 accumulation on the fp32 matrix cores -- the 1x1 / strided / stem layers as a k-ordered
     fmaf chain, the stride-1 3x3 layers through fp32 Winograd with output tiles up to 6x6 (per-layer error vs float64 <= 2.7e-5 of
     scale instead of the direct chain's 3e-7); 1 / "bf16x3": fp32 operands split into bf16 hi+lo, three bf16
-    MFMAs per product.  `exact=True` (fp32 only) caps every Winograd layer at F(2x2,3x3), whose transforms hold 0, +-1, +-1/2 only:
+    MFMAs per product; 2 / "bf16x6": the pointwise layers with fp32 operands carried exactly as three bf16 planes, six bf16 MFMAs per
+    product (fp32-equivalent; model/conv.py `_use_x6`), every other layer exactly as in mode 0.  `exact=True` (fp32 only) caps every Winograd layer at F(2x2,3x3), whose transforms hold 0, +-1, +-1/2 only:
     the direct kernels' error level (7e-7), at ~25 % more step time; `exact=False` restores the default tiles; None leaves the
     tile cap alone.  Selects which entry points DigaConv2d calls from now on; graphs already built keep the arithmetic of their
     forward pass only where they hold split-twin tensors (DigaConv2d checks and raises otherwise)."""
-    mode = {"f32": 0, "bf16x3": 1}.get(mode, mode)
-    if mode not in (CONV_MATH_F32, CONV_MATH_BF16X3):
-        raise ValueError(f"conv math must be 0 / 'f32' or 1 / 'bf16x3', not {mode!r}")
+    mode = {"f32": 0, "bf16x3": 1, "bf16x6": 2}.get(mode, mode)
+    if mode not in (CONV_MATH_F32, CONV_MATH_BF16X3, CONV_MATH_BF16X6):
+        raise ValueError(f"conv math must be 0 / 'f32', 1 / 'bf16x3' or 2 / 'bf16x6', not {mode!r}")
     if exact is not None:
         if exact and mode != CONV_MATH_F32:
             raise ValueError("exact=True belongs to the fp32 arithmetic")

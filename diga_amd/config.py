@@ -42,7 +42,7 @@ class StepConfig:
     graph_fork_wgrad: bool = True        # ... and the weight gradients as forked branches
     centroid_exchange: str = "allgather"  # N > 1: "allgather" (exact) or "allreduce" (BASELINE configs[3]'s approximate exchange)
     # ---- convolution arithmetic and path choices (diga_amd/model/conv.py)
-    conv_math: int = 0                   # 0 exact fp32 (matrix cores, Winograd for stride-1 3x3), 1 split bf16 (three bf16 MFMAs per product)
+    conv_math: int = 0                   # 0 exact fp32 (matrix cores, Winograd for stride-1 3x3), 1 split bf16 (three bf16 MFMAs per product), 2 bf16x6 (pointwise layers on three bf16 planes, fp32-equivalent; the rest as 0)
     winograd: bool = True
     winograd_ratio: float = 0.62
     winograd_default_max_tile: int = 6
@@ -81,7 +81,7 @@ class StepConfig:
         c.graph_fork_teacher = _flag("DIGA_GRAPH_FORK_TEACHER", c.graph_fork_teacher)
         c.graph_fork_wgrad = _flag("DIGA_GRAPH_FORK_WGRAD", c.graph_fork_wgrad)
         c.centroid_exchange = e("DIGA_CENTROID_EXCHANGE", c.centroid_exchange)
-        c.conv_math = 1 if e("DIGA_CONV_MATH", "") in ("bf16x3", "1") else 0
+        c.conv_math = {"bf16x3": 1, "1": 1, "bf16x6": 2, "2": 2}.get(e("DIGA_CONV_MATH", ""), 0)
         c.winograd = _flag("DIGA_CONV_WINOGRAD", c.winograd)
         c.winograd_ratio = float(e("DIGA_CONV_WINOGRAD_RATIO", c.winograd_ratio))
         c.winograd_default_max_tile = c.winograd_max_tile = int(e("DIGA_CONV_WINOGRAD_TILE", c.winograd_default_max_tile))
@@ -110,8 +110,8 @@ class StepConfig:
             raise ValueError(f"c4_overlap must be 0, 1 or 2, not {self.c4_overlap!r}")
         if self.wgrad_hold < 0:
             raise ValueError(f"wgrad_hold must be >= 0, not {self.wgrad_hold!r}")
-        if self.conv_math not in (0, 1):
-            raise ValueError(f"conv_math must be 0 (fp32) or 1 (split bf16), not {self.conv_math!r}")
+        if self.conv_math not in (0, 1, 2):
+            raise ValueError(f"conv_math must be 0 (fp32), 1 (split bf16) or 2 (bf16x6), not {self.conv_math!r}")
         if self.winograd_max_tile not in (2, 4, 6):
             raise ValueError(f"winograd_max_tile must be 2, 4 or 6, not {self.winograd_max_tile!r}")
         return self

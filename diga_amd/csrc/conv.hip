@@ -3339,6 +3339,9 @@ extern "C" int diga_conv2d_wgrad_twin(const void* dy_twin, const void* x_twin, f
     return launch_status("diga_conv2d_wgrad_twin");
 }
 
+// ---- bf16x6: fp32 operands as three bf16 planes, pointwise layers (kernels and entry points)
+#include "conv_bf16x6.h"
+
 extern "C" int diga_weight_transpose(const float* w, float* wt, int64_t K, int64_t RS, int64_t C, void* stream) {
     DIGA_REQUIRE(w && wt && K > 0 && RS > 0 && C > 0 && RS < 65536, DIGA_EINVAL, "weight_transpose: bad argument");
     dim3 grid((unsigned)ceil_div(C, 32), (unsigned)ceil_div(K, 32), (unsigned)RS);

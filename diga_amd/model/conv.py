@@ -62,6 +62,25 @@ def _use_twin(cin, k, taps, shared):
     return mode == "1" or taps > 1 or shared
 
 
+def _use_x6(cin, r, s):
+    """bf16x6 eligibility of a layer (conv_math = 2; csrc/conv_bf16x6.h): a 1x1 convolution (groups = 1 is all DigaConv2d builds) whose
+    PADDED input channel count is a multiple of 32 -- any stride, any output channel count (the kernels clamp ragged channel tiles,
+    the backward passes see channel counts padded to 32), with or without bias, BatchNorm statistics or a backward-data epilogue.
+    Not eligible: multi-tap layers (Winograd / direct fp32), the stem's im2col GEMM (its backward has its own path) and calls with a
+    folded input map / activation (`opts`) -- the callers pass those as pointwise_ok=False to _layer_math."""
+    return r == 1 and s == 1 and cin % 32 == 0
+
+
+def _layer_math(r, s, cin, pointwise_ok=True):
+    """The arithmetic ONE layer runs in under the active conv_math: 0 / 1 as set; in mode 2 (bf16x6) 2 for an eligible layer
+    (_use_x6) and 0 -- the exact-fp32 paths, Winograd included -- for every other one.  Every path decision and every `math`
+    argument handed to the library reads this, never the process-wide mode."""
+    m = _lib.get_conv_math()
+    if m != 2:
+        return m
+    return 2 if (pointwise_ok and _use_x6(cin, r, s)) else 0
+
+
 def takes_twin_only_input(conv, pointwise_ok=False):
     """True when `conv` (a DigaConv2d) reads its input exclusively through split twins -- forward on the twin kernel and
     backward-weight on the twin kernel -- so that its producer may write the twin instead of the fp32 tensor.
@@ -79,6 +98,17 @@ _WINO_CACHE = {}
 # bench.py sets this to a dict to learn what the convolutions of a step multiply: name -> [FLOPs of the direct
 # convolution (the algorithmic work), FLOPs the matrix cores execute (16/36 of it per 2x2 tile on the Winograd path)]
 flop_log = None
+
+
+# a test or tool sets this to a dict to learn which kernels ran: (pass, arithmetic) -> launches, pass in "fwd" / "dgrad" / "wgrad",
+# arithmetic in "f32" / "bf16x3" / "bf16x6" / "winograd"
+path_log = None
+
+
+def _log_path(tag, arith):
+    if path_log is not None:
+        key = (tag if isinstance(tag, str) else ("dgrad" if tag == _TAG_BWD_DATA else "fwd"), arith)
+        path_log[key] = path_log.get(key, 0) + 1
 
 
 def _log_flops(name, direct, executed):
@@ -179,7 +209,7 @@ def _tile_table(n, hi, wi, d, tile, device):
 def winograd_stats_plan(n, hi, wi, cin_padded, k, r, s, stride, padding, dilation, ho, wo):
     """(floats, records) of the statistics buffer a forward DigaConv2d on the fp32 Winograd path with 4x4 / 6x6 tiles fills for the
     BatchNorm behind it (diga_conv2d_winograd_stats_floats / _records), or None when the layer is not on that path."""
-    if _lib.get_conv_math() != 0 or not _winograd_ok(n, hi, wi, cin_padded, k, r, s, stride, (-padding[0], -padding[1]), tuple(dilation), ho, wo):
+    if _layer_math(r, s, cin_padded) != 0 or not _winograd_ok(n, hi, wi, cin_padded, k, r, s, stride, (-padding[0], -padding[1]), tuple(dilation), ho, wo):
         return None
     tile = _wino_plan(hi, wi, dilation[0])[0]
     if tile < 4 or k % 4 != 0:
@@ -210,9 +240,10 @@ def _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo):
 
 
 def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin_box=None, must_twin=False, epi=None,
-                 opts=None, keep_v=None, wino_stats=False):
+                 opts=None, keep_v=None, wino_stats=False, x6_ok=True):
     """x [N,Hi,Wi,Cin] (contiguous or a channel slice of a contiguous tensor), w_krsc [K,R,S,Cin],
     out [N,Ho,Wo,K] (same rule).  twin_box: a one-element list shared by the convs that read the very same x.
+    (In bf16x6 mode the box holds the three-plane triplet of x instead.)  x6_ok=False keeps a pointwise call off bf16x6 (the stem).
     epi: a _lib.BwdEpilogue (backward-data only, bias-free): the `_epi` entry points finish the gradient in the epilogue.
     opts: (reflect_pad, upsample_shift, activation) = a diga_conv_options_t handed to the `_opts` entry points -- x is then the SOURCE tensor of the
     (virtually) upsampled / mirrored input."""
@@ -226,7 +257,30 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
     n, hi, wi, cin = x.shape
     _, ho, wo, k = out.shape
     _, r, s, _ = w_krsc.shape
-    if (_lib.get_conv_math() == 1 and _use_twin(cin, k, r * s, twin_box is not None)
+    math = _layer_math(r, s, cin, x6_ok and copt is None)
+    if math == 2:
+        # bf16x6: both operands pre-split into three bf16 planes, copied global -> LDS by LDS-DMA (csrc/conv_bf16x6.h)
+        trip = twin_box[0] if twin_box is not None else None
+        if trip is None:
+            xc = x if x.is_contiguous() else x.contiguous()
+            trip = torch.empty(n * hi * wi * cin * 6, dtype=torch.uint8, device=x.device)
+            _lib.call("diga_make_triplet", _lib.ptr(xc), cin, _lib.ptr(trip), n * hi * wi, cin, _lib.stream())
+            if twin_box is not None:
+                twin_box[0] = trip
+        img = torch.empty(_lib.lib.diga_split_bf16x6_image_bytes(k, 1, cin), dtype=torch.uint8, device=x.device)
+        _lib.call("diga_split_bf16x6_image", _lib.ptr(w_krsc), _lib.ptr(img), k, 1, cin, _lib.stream())
+        _log_path(tag, "bf16x6")
+        _log_flops("conv_bwd_data" if tag == _TAG_BWD_DATA else "conv_fwd", 2.0 * n * ho * wo * k * cin, 2.0 * n * ho * wo * k * cin)
+        if epi is not None:
+            _lib.call("diga_conv2d_nhwc_bf16x6_epi", _lib.ptr(trip), _lib.ptr(img), _lib.ptr(out), n, hi, wi, cin, ho, wo, k,
+                      out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], ctypes.byref(epi), tag,
+                      _lib.stream())
+            return trip
+        _lib.call("diga_conv2d_nhwc_bf16x6", _lib.ptr(trip), _lib.ptr(img), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin, ho, wo, k,
+                  out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], _lib.ptr(stats), tag,
+                  _lib.stream())
+        return trip
+    if (math == 1 and _use_twin(cin, k, r * s, twin_box is not None)
             and n * hi * wi * cin * 4 < (1 << 40)):
         # split-bf16 arithmetic without register staging: both operands pre-split, copied global -> LDS by LDS-DMA
         twin = twin_box[0] if twin_box is not None else None
@@ -236,6 +290,7 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
             _lib.call("diga_make_twin", _lib.ptr(xc), cin, _lib.ptr(twin), n * hi * wi, cin, _lib.stream())
             if twin_box is not None:
                 twin_box[0] = twin
+        _log_path(tag, "bf16x3")
         img = torch.empty(_lib.lib.diga_split_bf16_image_bytes(k, r * s, cin), dtype=torch.uint8, device=x.device)
         _lib.call("diga_split_bf16_image", _lib.ptr(w_krsc), _lib.ptr(img), k, r * s, cin, _lib.stream())
         if epi is not None:
@@ -254,7 +309,8 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
     if must_twin:
         raise RuntimeError("DigaConv2d: the input holds split-twin bytes but the twin kernel is not selected "
                            "(conv math or config.conv_twin changed since the producer ran)")
-    if _lib.get_conv_math() == 1:
+    if math == 1:
+        _log_path(tag, "bf16x3")
         # split-bf16 arithmetic: the weights are split once here (two bf16 arrays), the activations inside the kernel
         nel = w_krsc.numel()
         w_hi = torch.empty(nel, dtype=torch.int16, device=w_krsc.device)
@@ -276,25 +332,27 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
         return None
     direct = 2.0 * n * ho * wo * k * r * s * cin
     name = "conv_bwd_data" if tag == _TAG_BWD_DATA else "conv_fwd"
-    if (_lib.get_conv_math() == 0 and copt is not None and copt.upsample_shift == 0 and copt.activation == 0 and copt.reflect_pad
+    if (math == 0 and copt is not None and copt.upsample_shift == 0 and copt.activation == 0 and copt.reflect_pad
             and doff[0] > 0 and doff[0] < min(hi, wi) and _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo)
             and _wino_plan(hi, wi, doff[0])[0] >= 4):
         # reflection padding folded into the Winograd input transform (the translator's 3x3 ResBlock convs; round 5)
         d = doff[0]
         tile, ratio = _wino_plan(hi, wi, d)
         _log_flops(name, direct, direct * ratio)
+        _log_path(tag, "winograd")
         ws = _lib.workspace(_lib.lib.diga_conv2d_winograd_workspace_bytes(n, hi, wi, cin, k, d, tile), x.device, "winograd")
         _lib.call("diga_conv2d_winograd_f32_opts", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
                   n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile, ctypes.byref(copt), _lib.ptr(_tile_table(n, hi, wi, d, tile, x.device)),
                   tag, _lib.stream())
         return None
-    if (_lib.get_conv_math() == 0 and copt is None and (stats is None or wino_stats)
+    if (math == 0 and copt is None and (stats is None or wino_stats)
             and _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo)):
         d = abs(doff[0])
         tile, ratio = _wino_plan(hi, wi, d)
         if stats is not None and (tile < 4 or epi is not None or doff[0] < 0):
             raise RuntimeError("DigaConv2d: Winograd statistics come with the forward output transform of 4x4 / 6x6 tiles")
         _log_flops(name, direct, direct * ratio)
+        _log_path(tag, "winograd")
         nbytes = _lib.lib.diga_conv2d_winograd_workspace_bytes(n, hi, wi, cin, k, d, tile)
         ws = _lib.workspace(nbytes, x.device, "winograd")
         tab = _tile_table(n, hi, wi, d, tile, x.device)
@@ -316,6 +374,7 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
                   _lib.stream())
         return None
     _log_flops(name, direct, direct)
+    _log_path(tag, "f32")
     if epi is not None:
         _lib.call("diga_conv2d_nhwc_f32_epi", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(out), n, hi, wi, cin,
                   x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1],
@@ -365,7 +424,7 @@ class _StemConvFn(torch.autograd.Function):
         w2 = _pad_last(weight.detach().permute(0, 2, 3, 1).reshape(k, 1, 1, kk).contiguous(), kp)
         out = torch.empty((n, ho, wo, k), dtype=torch.float32, device=x.device)
         b = None if bias is None else bias.detach().float().contiguous()
-        _conv_launch(xcol, w2, b, out, (1, 1), (0, 0), (1, 1), _TAG_FWD, stats)
+        _conv_launch(xcol, w2, b, out, (1, 1), (0, 0), (1, 1), _TAG_FWD, stats, x6_ok=False)     # (bf16x6 mode: the stem stays exact fp32)
         ctx.save_for_backward(xcol)
         ctx.geom = (k, c, r, s, kk, kp, bias is not None, weight.stride())
         return out.permute(0, 3, 1, 2)
@@ -387,8 +446,10 @@ class _StemConvFn(torch.autograd.Function):
             dwp = torch.empty((kq, 1, 1, kp), dtype=torch.float32, device=xcol.device)
             nbytes = _lib.lib.diga_conv2d_wgrad_workspace_bytes(n, ho, wo, kq, kp, 1, 1)
             ws = _lib.workspace(nbytes, xcol.device, "wgrad")
+            lm = _layer_math(1, 1, kp, False)
+            _log_path("wgrad", "bf16x3" if lm == 1 else "f32")
             _lib.call("diga_conv2d_wgrad_nhwc_f32", _lib.ptr(gyp), _lib.ptr(xcol), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(),
-                      n, ho, wo, kp, kp, ho, wo, kq, kq, 1, 1, 1, 1, 0, 0, 1, 1, _lib.get_conv_math(), _lib.stream())
+                      n, ho, wo, kp, kp, ho, wo, kq, kq, 1, 1, 1, 1, 0, 0, 1, 1, lm, _lib.stream())
             dw = torch.empty_strided((k, c, r, s), w_strides, dtype=torch.float32, device=xcol.device)
             dw.copy_(dwp[:k, 0, 0, :kk].reshape(k, r, s, c).permute(0, 3, 1, 2))
         if has_bias and ctx.needs_input_grad[2]:
@@ -443,7 +504,8 @@ class _Conv2dFn(torch.autograd.Function):
         wino_stats = isinstance(stats, tuple)         # (buffer, "records"): the Winograd output transform fills it (DigaConv2d.forward)
         if wino_stats:
             stats = stats[0]
-        if (ctx.needs_input_grad[1] and _lib.get_conv_math() == 0 and k % 256 == 0 and cp % 128 == 0 and (stats is None or wino_stats)
+        lm = _layer_math(r, s, cp, opts is None or not any(opts))
+        if (ctx.needs_input_grad[1] and lm == 0 and k % 256 == 0 and cp % 128 == 0 and (stats is None or wino_stats)
                 and (opts is None or not any(opts)) and config.active().winograd_keep_v
                 and _winograd_ok(n, hi, wi, cp, k, r, s, stride, (-padding[0], -padding[1]), dilation, ho, wo)):
             keep_v = [None]
@@ -453,7 +515,9 @@ class _Conv2dFn(torch.autograd.Function):
         ctx.max_tile = config.active().winograd_max_tile      # (the kept transform's layout is the forward's tile: checked in backward)
         ctx.save_for_backward(xn, w)
         # the split twin of the input serves the weight gradient too (multi-tap / shared-input layers, Cout >= 256)
-        ctx.x_twin = x_twin if (ctx.needs_input_grad[1] and k >= 256 and k % 8 == 0 and cp == c) else None
+        ctx.x_twin = x_twin if (lm != 2 and ctx.needs_input_grad[1] and k >= 256 and k % 8 == 0 and cp == c) else None
+        # bf16x6: the three-plane triplet of the (padded) input serves the weight gradient of every eligible layer
+        ctx.x_trip = x_twin if (lm == 2 and ctx.needs_input_grad[1]) else None
         ctx.dy_is_twin = bool(dy_is_twin)
         if dy_is_twin and ctx.x_twin is None and ctx.needs_input_grad[1]:
             raise RuntimeError("DigaConv2d: twin_grad=True on a layer whose weight gradient is not on the twin kernel")
@@ -494,7 +558,8 @@ class _Conv2dFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         xn, w = ctx.saved_tensors
         stride, padding, dilation, c_true, has_bias, w_strides = ctx.geom
-        if (ctx.x_is_twin or ctx.dy_is_twin or ctx.x_twin is not None) and _lib.get_conv_math() != ctx.math:
+        x_trip = getattr(ctx, "x_trip", None)
+        if (ctx.x_is_twin or ctx.dy_is_twin or ctx.x_twin is not None or x_trip is not None) and _lib.get_conv_math() != ctx.math:
             raise RuntimeError("DigaConv2d: the conv arithmetic (_lib.set_conv_math) changed between forward and backward of a graph that "
                                "holds split-twin tensors (their bytes are only readable by the twin kernels)")
         if ctx.x_is_twin and ctx.needs_input_grad[1] and ctx.x_twin is None:
@@ -512,6 +577,10 @@ class _Conv2dFn(torch.autograd.Function):
         x_twin = getattr(ctx, "x_twin", None)
         use_tw = x_twin is not None and ctx.needs_input_grad[1] and _lib.get_conv_math() == 1 and kp == k
         dy_box = [None] if use_tw else None            # the twin of dy: built once, read by backward-data and -weight
+        lm = _layer_math(r, s, cp)                     # this layer's arithmetic (bf16x6 mode: 2 for pointwise layers, else 0)
+        use_x6 = lm == 2
+        if use_x6:
+            dy_box = [None]                            # the triplet of dy, shared the same way
         if ctx.dy_is_twin:          # the BatchNorm after this conv wrote its dx as a twin (same bytes per element)
             if not (kp == k and _lib.get_conv_math() == 1 and cp > 64 and (use_tw or not ctx.needs_input_grad[1])):
                 raise RuntimeError("DigaConv2d: twin gradient on a layer that is not on the twin kernels")
@@ -530,7 +599,7 @@ class _Conv2dFn(torch.autograd.Function):
                 # rows per partial-sum record of the backward-data epilogue this call will run (the Winograd form writes one
                 # record per tile group: any divisor of the row count the finaliser is told works, 128 as before)
                 epi_chunk = _lib.lib.diga_conv2d_epi_chunk_rows(n, ho, wo, kp, hi, wi, cp, r, s, 1, 1, padding[0], padding[1],
-                                                                  _lib.get_conv_math())
+                                                                  lm)
                 chain = ctx.chain if (ctx.chain is not None and not ctx.chain.get("disabled")) else None
                 last_of_chain = False
                 if chain is not None:
@@ -580,13 +649,13 @@ class _Conv2dFn(torch.autograd.Function):
                     epi.mean, epi.invstd, epi.partials = _lib.ptr(box["mean"]), _lib.ptr(box["invstd"]), _lib.ptr(part)
                     box["premasked"] = (dxn.data_ptr(), part, dxn, add, dxn._version, epi_chunk)
                 _conv_launch(gyp, wt, None, dxn, (1, 1), (padding[0], padding[1]), (-dilation[0], -dilation[1]),
-                             _TAG_BWD_DATA, None, dy_box if ((use_tw or ctx.dy_is_twin) and cp > 64) else None,
+                             _TAG_BWD_DATA, None, dy_box if (((use_tw or ctx.dy_is_twin) and cp > 64) or use_x6) else None,
                              must_twin=ctx.dy_is_twin, epi=epi)
             else:
                 if (r, s) != (1, 1) or padding != (0, 0):
                     raise NotImplementedError("backward-data of strided convs is only needed (and built) for 1x1")
                 dense = torch.empty((n, ho, wo, cp), dtype=torch.float32, device=w.device)
-                _conv_launch(gyp, wt, None, dense, (1, 1), (0, 0), (1, 1), _TAG_BWD_DATA)
+                _conv_launch(gyp, wt, None, dense, (1, 1), (0, 0), (1, 1), _TAG_BWD_DATA, twin_box=dy_box if use_x6 else None)
                 dxn = torch.zeros((n, hi, wi, cp), dtype=torch.float32, device=w.device)
                 dxn[:, ::stride[0], ::stride[1]] = dense
             dx = dxn[..., :c_true].permute(0, 3, 1, 2)
@@ -644,12 +713,38 @@ class _Conv2dFn(torch.autograd.Function):
                 if not alias:
                     dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
 
+            dy_trip = x_tr = None
+            if use_x6:
+                dy_trip, x_tr = dy_box[0], x_trip
+                if dy_trip is None:                 # backward-data did not build it (no input gradient wanted)
+                    dy_trip = torch.empty(n * ho * wo * kp * 6, dtype=torch.uint8, device=w.device)
+                    _lib.call("diga_make_triplet", _lib.ptr(gyp), kp, _lib.ptr(dy_trip), n * ho * wo, kp, st)
+                if x_tr is None:                    # the forward ran in another arithmetic and saved none
+                    x_tr = torch.empty(n * hi * wi * cp * 6, dtype=torch.uint8, device=w.device)
+                    _lib.call("diga_make_triplet", _lib.ptr(xn), cp, _lib.ptr(x_tr), n * hi * wi, cp, st)
+            ctx.x_trip = None
+
+            def run_x6():
+                _log_path("wgrad", "bf16x6")
+                _log_flops("conv_bwd_weight", 2.0 * n * ho * wo * kp * cp, 2.0 * n * ho * wo * kp * cp)
+                nbytes = _lib.lib.diga_conv2d_wgrad_bf16x6_workspace_bytes(n, ho, wo, kp, cp, 1, 1)
+                ws = _lib.workspace(nbytes, w.device, "wgrad")
+                _lib.call("diga_conv2d_wgrad_bf16x6", _lib.ptr(dy_trip), _lib.ptr(x_tr), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(),
+                          n, hi, wi, cp, ho, wo, kp, 1, 1, stride[0], stride[1], -padding[0], -padding[1], dilation[0],
+                          dilation[1], _lib.stream())
+                if not alias:
+                    dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
+
             def run():
+                if use_x6:
+                    return run_x6()
                 if use_tw:
+                    _log_path("wgrad", "bf16x3")
                     return run_twin()
-                if (_lib.get_conv_math() == 0 and kp % 256 == 0 and cp % 128 == 0 and gyp.stride(2) % 4 == 0
+                if (lm == 0 and kp % 256 == 0 and cp % 128 == 0 and gyp.stride(2) % 4 == 0
                         and _winograd_ok(n, hi, wi, cp, kp, r, s, stride, (-padding[0], -padding[1]), dilation, ho, wo)):
                     tile, ratio = _wino_plan(hi, wi, dilation[0])
+                    _log_path("wgrad", "winograd")
                     _log_flops("conv_bwd_weight", 2.0 * n * ho * wo * kp * 9 * cp, 2.0 * n * ho * wo * kp * 9 * cp * ratio)
                     nb = _lib.lib.diga_conv2d_wgrad_winograd_workspace_bytes(n, hi, wi, cp, kp, dilation[0], tile, 1 if wino_v is not None else 0)
                     wsw = _lib.workspace(nb, w.device, "winograd_wgrad")
@@ -660,11 +755,12 @@ class _Conv2dFn(torch.autograd.Function):
                         dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
                     return
                 _log_flops("conv_bwd_weight", 2.0 * n * ho * wo * kp * r * s * cp, 2.0 * n * ho * wo * kp * r * s * cp)
+                _log_path("wgrad", "bf16x3" if lm == 1 else "f32")
                 nbytes = _lib.lib.diga_conv2d_wgrad_workspace_bytes(n, ho, wo, kp, cp, r, s)
                 ws = _lib.workspace(nbytes, w.device, "wgrad")
                 _lib.call("diga_conv2d_wgrad_nhwc_f32", _lib.ptr(gyp), _lib.ptr(xn), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(),
                           n, hi, wi, cp, xn.stride(2), ho, wo, kp, gyp.stride(2), r, s, stride[0], stride[1],
-                          -padding[0], -padding[1], dilation[0], dilation[1], _lib.get_conv_math(), _lib.stream())
+                          -padding[0], -padding[1], dilation[0], dilation[1], lm, _lib.stream())
                 if not alias:
                     dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
 
@@ -681,7 +777,7 @@ class _Conv2dFn(torch.autograd.Function):
                 with torch.cuda.stream(side):
                     run()
                 dw.record_stream(side)          # (a returned gradient: never held, see _lib.release_to_side)
-                _lib.release_to_side(side, (gyp, xn) + (() if alias else (dwp,)) + ((dy_twin, x_twin) if use_tw else ())
+                _lib.release_to_side(side, (gyp, xn) + (() if alias else (dwp,)) + ((dy_twin, x_twin) if use_tw else ()) + ((dy_trip, x_tr) if use_x6 else ())
                                      + ((wino_v,) if wino_v is not None else ()))
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(gy)
@@ -721,7 +817,7 @@ class DigaConv2d(nn.Conv2d):
             wo = (w + 2 * self.padding[1] - self.dilation[1] * (self.kernel_size[1] - 1) - 1) // self.stride[1] + 1
         wino_records = None
         if self.emit_bn_stats and self.training and self.out_channels % 4 == 0:
-            on_wino = (_lib.get_conv_math() == 0 and fn is _Conv2dFn and (opts is None or not any(opts))
+            on_wino = (_layer_math(self.kernel_size[0], self.kernel_size[1], _pad_to(self.in_channels)) == 0 and fn is _Conv2dFn and (opts is None or not any(opts))
                        and _winograd_ok(n, h, w, _pad_to(self.in_channels), self.out_channels, self.kernel_size[0], self.kernel_size[1],
                                         self.stride, (-self.padding[0], -self.padding[1]), tuple(self.dilation), ho, wo))
             if not on_wino:
@@ -773,6 +869,8 @@ class DigaConv2d(nn.Conv2d):
         elif stats is not None:
             chunk = _lib.lib.diga_conv2d_stats_chunk_rows(n, h, w, _pad_to(self.in_channels), ho, wo, self.out_channels,
                                                           self.kernel_size[0], self.kernel_size[1], self.stride[0], self.stride[1],
-                                                          -self.padding[0], -self.padding[1], _lib.get_conv_math())
+                                                          -self.padding[0], -self.padding[1],
+                                                          _layer_math(self.kernel_size[0], self.kernel_size[1], _pad_to(self.in_channels),
+                                                                      fn is _Conv2dFn))
             y._diga_bn_partials = (stats, chunk)     # picked up by the DigaBatchNorm2d that consumes y
         return y

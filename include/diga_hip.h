@@ -311,9 +311,14 @@ typedef struct diga_conv_options {
  * environment variable DIGA_CONV_MATH) -- the library holds no process-wide mode.
  *   DIGA_CONV_MATH_F32    v_mfma_f32_32x32x2_f32, exact fp32 (k-ordered fmaf chain)
  *   DIGA_CONV_MATH_BF16X3 operands split into bf16 hi+lo, hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16 with fp32
- *                         accumulate (~1e-5 relative per product) */
+ *                         accumulate (~1e-5 relative per product)
+ *   DIGA_CONV_MATH_BF16X6 operands carried exactly as THREE bf16 planes (24 significand bits), six of the nine plane products
+ *                         on v_mfma_f32_16x16x32_bf16 with fp32 accumulate: fp32-equivalent (dropped terms <= 2^-24 of a
+ *                         product).  Pointwise (1x1) layers only, through the diga_*_bf16x6 entry points below; the host runs
+ *                         every other layer exactly as in DIGA_CONV_MATH_F32.  diga_conv2d_wgrad_nhwc_f32 does not take it. */
 #define DIGA_CONV_MATH_F32 0
 #define DIGA_CONV_MATH_BF16X3 1
+#define DIGA_CONV_MATH_BF16X6 2
 
 /* Tuned split-bf16 forward / backward-data: same contract as diga_conv2d_nhwc_f32 in DIGA_CONV_MATH_BF16X3, but the
  * weights are passed already split (diga_split_bf16 of the [Cout][R][S][Cin] array, once per step), so the kernel
@@ -438,6 +443,35 @@ int diga_conv2d_wgrad_twin(const void* dy_twin, const void* x_twin, float* dw, v
                            int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t R,
                            int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
                            int64_t off_dx, void* stream);
+
+/* bf16x6 (DIGA_CONV_MATH_BF16X6): 1x1 convolutions with BOTH operands pre-split into three bf16 planes and staged by LDS-DMA.
+ *   triplet  = diga_make_triplet of dense [M][C] fp32 activations (C % 8 == 0): per pixel and group of 8 channels 16 B of
+ *              plane 0, 16 B of plane 1, 16 B of plane 2, plane0 = bf16(a), plane1 = bf16(a - plane0), plane2 =
+ *              bf16(a - plane0 - plane1) (6*C bytes per pixel; the planes sum to a exactly for normal fp32 of magnitude
+ *              >= 2^-110; a non-finite a gives nan in the low planes);
+ *   wgt_img  = diga_split_bf16x6_image of the [Cout][R*S][Cin] weights (diga_split_bf16x6_image_bytes bytes, Cin % 32 == 0):
+ *              the three planes as LDS images per (output-channel tile, 32-channel K-step).
+ * Per product a1 b1 + a0 b2 + a2 b0 + a0 b1 + a1 b0 + a0 b0, fp32 accumulate, the five small terms summed apart per
+ * 32-deep K-step.  diga_conv2d_nhwc_bf16x6 / _epi: the contract of diga_conv2d_nhwc_twin / _twin_epi (bias, stats_partial
+ * in 128-row chunks, the diga_bwd_epilogue_t epilogue) restricted to R == S == 1 (any stride / offset: pixels outside the
+ * image read zeros).  diga_conv2d_wgrad_bf16x6: dw [Cout][Cin] from the triplets of dy [N,Ho,Wo,Cout] and x [N,Hi,Wi,Cin]
+ * (channel counts % 8 == 0), split over pixel ranges and summed in fixed order (deterministic); workspace 16-byte aligned. */
+int diga_make_triplet(const float* x, int64_t ld, void* triplet, int64_t M, int64_t C, void* stream);
+size_t diga_split_bf16x6_image_bytes(int64_t Cout, int64_t RS, int64_t Cin);
+int diga_split_bf16x6_image(const float* w, void* img, int64_t Cout, int64_t RS, int64_t Cin, void* stream);
+int diga_conv2d_nhwc_bf16x6(const void* in_triplet, const void* wgt_img, const float* bias, float* out, int64_t N, int64_t Hi,
+                            int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
+                            int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
+                            float* stats_partial, int prof_tag, void* stream);
+int diga_conv2d_nhwc_bf16x6_epi(const void* in_triplet, const void* wgt_img, float* out, int64_t N, int64_t Hi, int64_t Wi,
+                                int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
+                                int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
+                                const diga_bwd_epilogue_t* epi, int prof_tag, void* stream);
+size_t diga_conv2d_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R, int64_t S);
+int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_triplet, float* dw, void* workspace, size_t workspace_bytes,
+                             int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t R,
+                             int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
+                             int64_t off_dx, void* stream);
 
 /* Stem (7x7/2 on the 3-channel NCHW image, G5/model/seg_model_noaux.py:221): out[n,ho,wo][(r*S+s)*C + c] =
  * x[n,c,ho*stride-pad+r,wo*stride-pad+s] (zero outside / beyond R*S*C up to Kpad), after which the conv is a

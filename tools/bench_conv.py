@@ -2,9 +2,11 @@
 """Per-shape timing of the conv kernels (forward, backward-data, backward-weight) on the layer
 geometries of ResNet-101 DeepLabV2 at the C2 size (16 images of 768x768 -> 193x193 / 97x97 maps).
 
-    python tools/bench_conv.py [--images 16] [--reps 5]
+    python tools/bench_conv.py [--images 16] [--reps 5] [--math f32|bf16x3|bf16x6]
 Prints one line per (shape, pass): ms, TFLOP/s, fraction of the 157.3 TFLOP/s fp32 MFMA peak, and the
 share of a training step's conv time that shape accounts for (count x time).
+--math bf16x6: the pointwise layers run on bf16x6, the rest on the exact-fp32 paths; the operand split passes are part of the
+figures (forward: inside the timed call; backward: the elementwise launches -- triplet of dy, weight images -- are added to dgrad).
 """
 import argparse
 import os
@@ -17,7 +19,7 @@ sys.path.insert(0, ROOT)
 from diga_amd import _lib  # noqa: E402
 from diga_amd.model.conv import DigaConv2d  # noqa: E402
 
-PEAK = 157.3          # fp32 MFMA peak; the split-bf16 mode is priced against 2500 / 3 = 833.3 (see --math)
+PEAK = 157.3          # fp32 MFMA peak; the split-bf16 mode is priced against 2500 / 3 = 833.3, bf16x6 against 2500 / 6 (see --math)
 # name, count per forward, Cin, Cout, k, stride, dil, spatial (H=W)
 SHAPES = [
     ("stem7x7", 1, 3, 64, 7, 2, 1, 768),
@@ -52,13 +54,14 @@ def main():
     ap.add_argument("--images", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--math", default="f32", choices=["f32", "bf16x3"])
+    ap.add_argument("--math", default="f32", choices=["f32", "bf16x3", "bf16x6"])
     a = ap.parse_args()
-    _lib.set_conv_math(1 if a.math == "bf16x3" else 0)
+    _lib.set_conv_math(a.math)
     global PEAK
-    PEAK = 2500.0 / 3.0 if a.math == "bf16x3" else 157.3
+    PEAK = {"bf16x3": 2500.0 / 3.0, "bf16x6": 2500.0 / 6.0}.get(a.math, 157.3)
     dev = "cuda"
     rows, tot = [], {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}
+    pw = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the pointwise (1x1) rows alone
     for name, count, cin, cout, k, stride, dil, hw in SHAPES:
         if a.only and a.only not in name:
             continue
@@ -80,22 +83,32 @@ def main():
 
         # isolate the two backward kernels through the event profiler inside the library
         _lib.call("diga_prof_reset")
-        _lib.call("diga_prof_enable", 1)
         for _ in range(a.reps):
             m.weight.grad = None
             if need_dx:
                 x.grad = None
-            m(x).backward(gy)
-        torch.cuda.synchronize()
-        _lib.call("diga_prof_enable", 0)
+            out = m(x)
+            torch.cuda.synchronize()
+            _lib.call("diga_prof_enable", 1)             # (the backward alone: the forward's own split passes are in t_f)
+            out.backward(gy)
+            torch.cuda.synchronize()
+            _lib.call("diga_prof_enable", 0)
         nd, td = _lib.prof_query("conv_bwd_data")
         nw, tw = _lib.prof_query("conv_bwd_weight")
         t_d = td / nd if nd else 0.0
         t_w = tw / nw if nw else 0.0
+        if a.math == "bf16x6" and k == 1:
+            # the split passes of the backward (triplet of dy, the weight image; booked as elementwise) belong to the layer's time
+            ne, te = _lib.prof_query("elementwise")
+            t_d += te / a.reps
         rows.append((name, count, flops, t_f, t_d, t_w))
         tot["fwd"] += count * t_f
         tot["dgrad"] += count * t_d
         tot["wgrad"] += count * t_w
+        if k == 1:
+            pw["fwd"] += count * t_f
+            pw["dgrad"] += count * t_d
+            pw["wgrad"] += count * t_w
         del m, x, y, gy
         torch.cuda.empty_cache()
     print(f"{'shape':18s} {'cnt':>3s} {'GFLOP':>8s} | {'fwd ms':>8s} {'TF/s':>6s} {'frac':>5s} | {'dgrad ms':>8s} {'TF/s':>6s} | "
@@ -106,6 +119,7 @@ def main():
               f"{t_w:8.3f} {tf(t_w):6.1f} | {100 * count * t_f / tot['fwd']:.1f}% {100 * count * t_d / max(tot['dgrad'], 1e-9):.1f}% "
               f"{100 * count * t_w / max(tot['wgrad'], 1e-9):.1f}%")
     print(f"sum over one forward: fwd {tot['fwd']:.1f} ms, dgrad {tot['dgrad']:.1f} ms, wgrad {tot['wgrad']:.1f} ms")
+    print(f"pointwise rows, count-weighted ({a.math}): fwd {pw['fwd']:.2f} ms, dgrad {pw['dgrad']:.2f} ms, wgrad {pw['wgrad']:.2f} ms")
 
 
 if __name__ == "__main__":

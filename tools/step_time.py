@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Whole-step time of the DiGA warm-up step (student + EMA teacher, ResNet-101 DeepLabV2) under each convolution arithmetic, on
+synthetic data -- the figure bench.py reports for its headline leg, for arithmetics bench.py cannot select (bf16x6).
+
+    python tools/step_time.py [--math f32 bf16x6] [--batch 8] [--size 768 768] [--steps 5] [--warmup 2] [--rounds 2] [--serial-streams]
+The arithmetics are run alternately, `rounds` times each, in one process; every run builds fresh models from the same seed.
+--serial-streams switches the teacher / weight-gradient side streams off (kernel times add up: what the arithmetic changes by itself).
+Prints ms per step and crops/s per run and the last step's losses (the arithmetics must agree on them to rounding)."""
+import argparse
+import os
+import random
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from diga_amd import _lib, config, synthetic  # noqa: E402
+from diga_amd.model import seg_model_noaux as sm  # noqa: E402
+from diga_amd.model.model_noaux import SegModel  # noqa: E402
+from diga_amd.train_step import DigaTrainer  # noqa: E402
+
+MATH = {"f32": 0, "bf16x3": 1, "bf16x6": 2}
+
+
+def run(math, batch, h, w, steps, warmup, serial=False, dev="cuda"):
+    cfg = config.DEFAULTS.replace(conv_math=MATH[math])
+    if serial:
+        cfg = cfg.serial_streams()
+    prev = _lib.get_conv_math()
+    _lib.set_conv_math(cfg.conv_math)
+    try:
+        torch.manual_seed(0)
+        student, teacher = SegModel(arch=sm.RESNET101).to(dev), SegModel(arch=sm.RESNET101).to(dev)
+        teacher.train()
+        tr = DigaTrainer(student, teacher, rng=random.Random(1234), config=cfg)
+        data = synthetic.warmup_batch(1234, batch, h, w, block=32, device=dev)
+        it, out = 0, None
+        for _ in range(warmup):
+            tr.warmup_step(it, *data)
+            it += 1
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(steps):
+            out = tr.warmup_step(it, *data)
+            it += 1
+        e.record()
+        torch.cuda.synchronize()
+        _lib.join_side()
+        return s.elapsed_time(e) / steps, {k: round(float(v), 6) for k, v in out.items()}
+    finally:
+        _lib.set_conv_math(prev)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--math", nargs="+", default=["f32", "bf16x6"], choices=sorted(MATH))
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--size", type=int, nargs=2, default=[768, 768])
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--serial-streams", action="store_true")
+    a = ap.parse_args()
+    for r in range(a.rounds):
+        for math in a.math:
+            ms, out = run(math, a.batch, a.size[0], a.size[1], a.steps, a.warmup, a.serial_streams)
+            torch.cuda.empty_cache()
+            print(f"round {r + 1} {math:7s}: {ms:8.2f} ms per step = {a.batch * 1e3 / ms:6.2f} crops/s | last step: {out}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
