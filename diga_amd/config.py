@@ -58,6 +58,7 @@ class StepConfig:
     relu_bits: bool = True               # ReLU masks as bit planes instead of reading the activated tensor in backward
     fuse_bwd: bool = True                # residual-junction add + ReLU mask + BN-backward reduce in the backward-data epilogue
     junction_chain: bool = True
+    fold_downsample_bn: bool = True      # the downsample BatchNorm's apply pass inside the junction relu(bn3(c3) + skip) that alone reads it
     # ---- data parallelism (diga_amd/ddp.py)
     ddp_bucket_mb: int = 25
     ddp_grad_views: bool = True          # gradients live in the all-reduce buckets
@@ -95,6 +96,7 @@ class StepConfig:
         c.relu_bits = _flag("DIGA_RELU_BITS", c.relu_bits)
         c.fuse_bwd = _flag("DIGA_FUSE_BWD", c.fuse_bwd)
         c.junction_chain = _flag("DIGA_JUNCTION_CHAIN", c.junction_chain)
+        c.fold_downsample_bn = _flag("DIGA_FOLD_DOWNSAMPLE_BN", c.fold_downsample_bn)
         c.ddp_bucket_mb = int(e("DIGA_DDP_BUCKET_MB", c.ddp_bucket_mb))
         c.ddp_grad_views = _flag("DIGA_DDP_GRAD_VIEWS", c.ddp_grad_views)
         c.ddp_overlap = _flag("DIGA_DDP_OVERLAP", c.ddp_overlap)

@@ -2481,12 +2481,19 @@ struct GemmArgs {
     const float* W;
     float* out;
     int M, K, Cout, tiles_m, tiles_n, wb_tiles;      // M: valid rows (tiles_m = ceil(M / 256); rows beyond M load zeros, store nothing)
+    int rows_valid;                                  // rows of a weight-panel batch (wb_tiles tiles) that are not zero padding; wb_tiles == 0: M
     int64_t wb_stride;
     int64_t a_ld, out_ld;                            // floats between rows of A / out
     const float* bias;                               // nullable [Cout]
     float* stats;                                    // nullable [ceil(M / 64)][3][Cout]: {sum (y - s), sum (y - s)^2, s = first row} per 64-row chunk
 };
 
+// A 64-row wave piece whose rows are all padding (the row tail of the last tile: 97 x 97 maps leave 16 valid rows of 256 in it, in
+// every batch of a Winograd product and at the end of every 1x1 layer) skips its fragment reads and MFMAs for the whole tile --
+// its accumulators stay the +0 the MFMAs on zero rows would have left -- and only keeps the barriers.
+// STATS / BIAS: the drain's per-element statistics arithmetic and bias add exist only in the instantiation that stores them (the
+// Winograd-domain and backward-data launches pass neither); the remaining operations are the same, in the same order.
+template <bool STATS, bool BIAS>
 __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g) {
     constexpr int A_BYTES = 256 * 128, B_BYTES = 128 * 128, STAGE = A_BYTES + B_BYTES;
     extern __shared__ __align__(16) unsigned char smem_b[];
@@ -2559,6 +2566,15 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
     }
 
     const int wm = wv >> 1, wn = wv & 1;
+    // (wave-uniform by construction; through an SGPR so that the skip below is a scalar branch)
+    const int piece_row = __builtin_amdgcn_readfirstlane(wm * 64);
+    auto piece_live = [&](int it_) {
+#ifdef DIGA_GEMM_ALL_PIECES_LIVE                                  // A/B build: padding pieces multiply their zeros, as before
+        return true;
+#endif
+        const int tile_m = (start + slot + nslots * it_) / g.tiles_n;
+        return (g.wb_tiles > 0 ? tile_m % g.wb_tiles : tile_m) * 256 + piece_row < g.rows_valid;
+    };
     f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -2577,8 +2593,21 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
 #define DIGA_FOFF(t) ((t) << 5)
 
     __builtin_amdgcn_s_barrier();                                // stage 0 has landed
-    int cur = 0, it = 0, ks_in_tile = 0;
-    for (int gs = 0; gs < total_steps; ++gs) {
+    int cur = 0;
+    for (int it = 0; it < nmine; ++it) {
+        if (!piece_live(it)) {
+            // nothing but padding in this wave's 64 rows: the tile's barriers, no reads, no MFMAs
+            for (int ks = 0; ks < ksteps; ++ks) {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                cur = cur == 2 ? 0 : cur + 1;
+            }
+        } else {
+        // lgkmcnt(0): with a kernel argument's scalar load still counted as pending at the loop's entry the compiler makes the first
+        // wait of EVERY K-step lgkmcnt(0) -- all eight fragment reads before the first MFMA instead of the three it needs (seen in
+        // the <true, false> instantiation)
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        for (int ks = 0; ks < ksteps; ++ks) {
         const int sa = cur * STAGE + FA, sb = cur * STAGE + FB;      // (stage and wave bases are multiples of 8 KB: bits 5-6 stay F's)
 #define As_AT(t) (smem_b + (sa ^ DIGA_FOFF(t)))
 #define Bs_AT(t) (smem_b + (sb ^ DIGA_FOFF(t)))
@@ -2613,7 +2642,9 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         cur = cur == 2 ? 0 : cur + 1;
-        if (++ks_in_tile == ksteps) {
+        }
+        }
+        {
             // tile finished: accumulator register e of a 32x32 tile is row (e & 3) + 8 (e >> 2) + 4 lh, column li
             const int t = start + slot + nslots * it;
             const int tile_n = t % g.tiles_n, tile_m = t / g.tiles_n;
@@ -2626,10 +2657,11 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
             const int rows_left = g.M - (row_w + 4 * lh);                      // row offset r is valid iff r < rows_left
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const float bv = g.bias != nullptr ? g.bias[col_w + j * 32] : 0.f;
+                // (without a bias nothing is added: an accumulator that starts at +0 never holds -0, so `+ 0.f` changed no bit)
+                const float bv = BIAS ? g.bias[col_w + j * 32] : 0.f;
                 // what the BatchNorm after the conv needs, per 64-row chunk (= this wave's rows) and column: shift s = the chunk's
                 // first row (register 0 of the lower lane half), sum (y - s), sum (y - s)^2 over the valid rows
-                const float sh = __shfl(acc[0][j][0] + bv, li, 64);
+                const float sh = STATS ? __shfl(BIAS ? acc[0][j][0] + bv : acc[0][j][0], li, 64) : 0.f;
                 float sd = 0.f, sd2 = 0.f;
                 if (row_w + 64 <= g.M) {
                     // (uniform branch) all 64 rows of the wave's piece exist -- every tile but the last row tile: no per-element
@@ -2639,11 +2671,13 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
 #pragma unroll
                         for (int e = 0; e < 16; ++e) {
                             const int r = i * 32 + (e & 3) + 8 * (e >> 2);
-                            const float v = acc[i][j][e] + bv;
+                            const float v = BIAS ? acc[i][j][e] + bv : acc[i][j][e];
                             __builtin_nontemporal_store(v, DIGA_O_AT(r, j));
-                            const float d = v - sh;
-                            sd += d;
-                            sd2 += d * d;
+                            if (STATS) {
+                                const float d = v - sh;
+                                sd += d;
+                                sd2 += d * d;
+                            }
                             acc[i][j][e] = 0.f;
                         }
                 } else {
@@ -2652,17 +2686,19 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
 #pragma unroll
                         for (int e = 0; e < 16; ++e) {
                             const int r = i * 32 + (e & 3) + 8 * (e >> 2);
-                            const float v = acc[i][j][e] + bv;
+                            const float v = BIAS ? acc[i][j][e] + bv : acc[i][j][e];
                             if (r < rows_left) {
                                 __builtin_nontemporal_store(v, DIGA_O_AT(r, j));
-                                const float d = v - sh;
-                                sd += d;
-                                sd2 += d * d;
+                                if (STATS) {
+                                    const float d = v - sh;
+                                    sd += d;
+                                    sd2 += d * d;
+                                }
                             }
                             acc[i][j][e] = 0.f;
                         }
                 }
-                if (g.stats != nullptr && row_w < g.M) {
+                if (STATS && row_w < g.M) {
                     sd += __shfl_xor(sd, 32, 64);
                     sd2 += __shfl_xor(sd2, 32, 64);
                     if (lh == 0) {
@@ -2673,17 +2709,36 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
                     }
                 }
             }
-            ks_in_tile = 0;
-            ++it;
         }
     }
+}
+
+// the instantiation follows the pointers: statistics / bias arithmetic only where there is a buffer for it
+static void launch_gemm_persistent(const GemmArgs& g, hipStream_t st) {
+    const size_t sh = 3 * (256 + 128) * 128;
+#define DIGA_GEMM_P(STATS_, BIAS_)                                                                                                    \
+    do {                                                                                                                              \
+        (void)hipFuncSetAttribute((const void*)gemm_f32_persistent_kernel<STATS_, BIAS_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                  (int)sh);                                                                                           \
+        hipLaunchKernelGGL((gemm_f32_persistent_kernel<STATS_, BIAS_>), dim3(256), dim3(768), sh, st, g);                              \
+    } while (0)
+    if (g.stats != nullptr) {
+        if (g.bias != nullptr) DIGA_GEMM_P(true, true);
+        else DIGA_GEMM_P(true, false);
+    } else {
+        if (g.bias != nullptr) DIGA_GEMM_P(false, true);
+        else DIGA_GEMM_P(false, false);
+    }
+#undef DIGA_GEMM_P
 }
 
 // `batches` independent products out_b [rows x Cout] = A_b [rows x K] * W_b^T (W_b [Cout][K]) in one launch of
 // conv_fwd_dma_kernel: the operands of all batches are stacked row-wise (A [batches * rows][K], out likewise,
 // W [batches][Cout][K]); rows % 256 == 0 so that no 256-row tile straddles two batches.  Used by winograd.hip.
+// rows_valid (0 = all): the rows of each batch from this one on are ZERO rows of A (the caller's padding to the tile size) -- the
+// persistent kernel spends no MFMAs on a wave piece made of them; their output rows are +0 either way.
 int gemm_batched_f32_dma(const float* A, int64_t rows_per_batch, int batches, int64_t K, const float* W, int64_t Cout,
-                         float* out, hipStream_t st) {
+                         float* out, hipStream_t st, int64_t rows_valid) {
     DIGA_REQUIRE(rows_per_batch > 0 && rows_per_batch % 256 == 0 && K % 32 == 0 && Cout > 0 && Cout % 4 == 0, DIGA_EINVAL,
                  "gemm_batched_f32_dma: rows %% 256, K %% 32, Cout %% 4 required");
     const int64_t M = rows_per_batch * batches;
@@ -2707,8 +2762,8 @@ int gemm_batched_f32_dma(const float* A, int64_t rows_per_batch, int batches, in
         g.A = A; g.W = W; g.out = out; g.M = (int)M; g.K = (int)K; g.Cout = (int)Cout;
         g.tiles_m = (int)(M / 256); g.tiles_n = a.tiles_n; g.wb_tiles = a.wb_tiles; g.wb_stride = a.wb_stride;
         g.a_ld = K; g.out_ld = Cout; g.bias = nullptr; g.stats = nullptr;
-        (void)hipFuncSetAttribute((const void*)gemm_f32_persistent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        hipLaunchKernelGGL(gemm_f32_persistent_kernel, dim3(256), dim3(768), sh, st, g);
+        g.rows_valid = (int)(rows_valid > 0 && rows_valid < rows_per_batch ? rows_valid : rows_per_batch);
+        launch_gemm_persistent(g, st);
         return DIGA_OK;
     }
     (void)hipFuncSetAttribute((const void*)conv_fwd_dma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
@@ -2779,10 +2834,8 @@ static int conv2d_f32_impl(const float* in, const float* wgt, const float* bias,
         GemmArgs g;
         g.A = in; g.W = wgt; g.out = out; g.M = a.M; g.K = (int)Cin; g.Cout = (int)Cout;
         g.tiles_m = (int)ceil_div(a.M, 256); g.tiles_n = (int)(Cout / 128); g.wb_tiles = 0; g.wb_stride = 0;
-        g.a_ld = in_ld; g.out_ld = out_ld; g.bias = bias; g.stats = stats_partial;
-        const size_t shp = 3 * (256 + 128) * 128;
-        (void)hipFuncSetAttribute((const void*)gemm_f32_persistent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shp);
-        hipLaunchKernelGGL(gemm_f32_persistent_kernel, dim3(256), dim3(768), shp, st, g);
+        g.a_ld = in_ld; g.out_ld = out_ld; g.bias = bias; g.stats = stats_partial; g.rows_valid = a.M;
+        launch_gemm_persistent(g, st);
         return launch_status("diga_conv2d_nhwc_f32");
     }
     if (a.M >= 256 && Cout >= 256 && R * S * Cin >= 256) {

@@ -209,12 +209,16 @@ __device__ __forceinline__ void norm_split4(const float4 v, uint2& hi, uint2& lo
 // Round 5: the operand combination (residual?, ReLU?, mask bits?, twin output?, per-segment coefficients?) is a TEMPLATE parameter --
 // with run-time flags every instantiation carried the registers of its heaviest path (the split-twin output: 54) and the flag tests per
 // row; the forms the fp32 step runs need 30-40.  Same expression per element, bit for bit.
-template <bool RES, bool RELU, bool BITS, bool TWIN, bool SEG>
+// RESAB (the junction of a bottleneck with a downsample branch): the residual operand is the RAW output of the downsample
+// convolution and res_ab [2][C] the coefficients of its BatchNorm -- fma(r, ar, br), rounded to fp32, is exactly what that
+// BatchNorm's own apply pass would have written and this kernel read back (a tensor with no other reader).
+template <bool RES, bool RELU, bool BITS, bool TWIN, bool SEG, bool RESAB = false>
 __global__ __launch_bounds__(256) void affine_apply_kernel(const float* __restrict__ x, int64_t ld_x, float* __restrict__ y,
                                                            int64_t ld_y, const float* __restrict__ res, int64_t ld_r,
                                                            const float* __restrict__ a, const float* __restrict__ b,
                                                            int64_t ab_seg_stride, int64_t rows_per_seg, int64_t rows,
-                                                           int C, unsigned char* __restrict__ relu_bits) {
+                                                           int C, unsigned char* __restrict__ relu_bits,
+                                                           const float* __restrict__ res_ab = nullptr) {
     // a thread keeps its channel quad(s) and walks rows: no per-element division, coefficients in registers
     const int tq = C >> 2;
     const int tpr = tq < 256 ? tq : 256;          // threads per row
@@ -227,6 +231,11 @@ __global__ __launch_bounds__(256) void affine_apply_kernel(const float* __restri
         const int c = q * 4;
         float4 av = *reinterpret_cast<const float4*>(a + c);
         float4 bv = b != nullptr ? *reinterpret_cast<const float4*>(b + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 rav, rbv;
+        if (RESAB) {
+            rav = *reinterpret_cast<const float4*>(res_ab + c);
+            rbv = *reinterpret_cast<const float4*>(res_ab + C + c);
+        }
         int cur_seg = 0;
         for (int r = blockIdx.x * rpb + rl; r < nrows; r += rstep) {
             if (SEG) {
@@ -244,7 +253,11 @@ __global__ __launch_bounds__(256) void affine_apply_kernel(const float* __restri
             o.x = __builtin_fmaf(xv.x, av.x, bv.x); o.y = __builtin_fmaf(xv.y, av.y, bv.y);
             o.z = __builtin_fmaf(xv.z, av.z, bv.z); o.w = __builtin_fmaf(xv.w, av.w, bv.w);
             if (RES) {
-                const float4 rv = ld4s(res + (int64_t)r * ld_r + c);
+                float4 rv = ld4s(res + (int64_t)r * ld_r + c);
+                if (RESAB) {
+                    rv.x = __builtin_fmaf(rv.x, rav.x, rbv.x); rv.y = __builtin_fmaf(rv.y, rav.y, rbv.y);
+                    rv.z = __builtin_fmaf(rv.z, rav.z, rbv.z); rv.w = __builtin_fmaf(rv.w, rav.w, rbv.w);
+                }
                 o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
             }
             if (RELU) {
@@ -304,6 +317,18 @@ static void launch_affine(dim3 grid, hipStream_t st, const float* x, int64_t ld_
         } else { if (twin_out) DIGA_AFF(false, false, false, true); else DIGA_AFF(false, false, false, false); }
     }
 #undef DIGA_AFF
+}
+
+// the junction relu(fma(x, a, b) + fma(res, ar, br)) with or without mask bits (shared coefficients, fp32 output)
+static void launch_affine_resab(dim3 grid, hipStream_t st, const float* x, int64_t ld_x, float* y, int64_t ld_y, const float* res,
+                                int64_t ld_r, const float* res_ab, const float* a, const float* b, int64_t rows, int C,
+                                unsigned char* relu_bits) {
+    if (relu_bits != nullptr)
+        hipLaunchKernelGGL((affine_apply_kernel<true, true, true, false, false, true>), grid, dim3(256), 0, st, x, ld_x, y, ld_y, res, ld_r,
+                           a, b, (int64_t)0, rows, rows, C, relu_bits, res_ab);
+    else
+        hipLaunchKernelGGL((affine_apply_kernel<true, true, false, false, false, true>), grid, dim3(256), 0, st, x, ld_x, y, ld_y, res, ld_r,
+                           a, b, (int64_t)0, rows, rows, C, relu_bits, res_ab);
 }
 
 // partial[(seg*nchunk+chunk)][2][C] = { sum g, sum g*xhat },  g = dy * [y > 0] (relu) , xhat = (x-mean)*invstd
@@ -1052,8 +1077,10 @@ static int bn_fwd_from_partials(const char* who, const float* x, int64_t ld_x, f
                                 float* running_var, float* save_mean, float* save_invstd, float* save_ab, int64_t M,
                                 int64_t C, int relu, int y_twin, unsigned char* relu_bits, float momentum, float eps,
                                 const float* partial, int64_t chunk_rows, const float* counts, int64_t n_records,
-                                void* workspace, size_t workspace_bytes, void* stream) {
+                                void* workspace, size_t workspace_bytes, void* stream, const float* res_ab = nullptr) {
     DIGA_REQUIRE(!relu_bits || (relu && C % 32 == 0), DIGA_EINVAL, "%s: relu_bits needs relu and C %% 32 == 0", who);
+    DIGA_REQUIRE(!res_ab || (residual && y && relu && !y_twin && aligned16(res_ab)), DIGA_EINVAL,
+                 "%s: residual coefficients need a residual, an fp32 y and relu", who);
     DIGA_REQUIRE(x && gamma && beta && save_mean && save_invstd && partial && workspace && M > 0, DIGA_EINVAL, "%s: bad argument", who);
     DIGA_REQUIRE(counts ? (n_records > 0 && n_records < (1 << 30)) : chunk_rows > 0, DIGA_EINVAL, "%s: bad chunk_rows / record count", who);
     // y == nullptr: statistics and coefficients only (save_ab required) -- the consumer applies relu(fma(x, a, b)) on load
@@ -1088,7 +1115,9 @@ static int bn_fwd_from_partials(const char* who, const float* x, int64_t ld_x, f
     }
     hipLaunchKernelGGL(bn_finalize2_kernel, dim3((unsigned)ceil_div(C, kFinCh)), dim3(256), 0, st, partial, g, gamma, beta,
                        running_mean, running_var, save_mean, save_invstd, ab, momentum, eps, counts);
-    if (y != nullptr)
+    if (y != nullptr && res_ab != nullptr)
+        launch_affine_resab(dim3(ew_blocks(M * C / 4)), st, x, ld_x, y, ld_y, residual, ld_r, res_ab, ab, ab + C, M, (int)C, relu_bits);
+    else if (y != nullptr)
         launch_affine(dim3(ew_blocks(M * C / 4)), st, x, ld_x, y, ld_y, residual, ld_r, ab,
                            ab + C, (int64_t)0, M, M, (int)C, relu, y_twin, relu_bits);
     return launch_status(who);
@@ -1103,6 +1132,20 @@ extern "C" int diga_bn_fwd_partials(const float* x, int64_t ld_x, float* y, int6
     return bn_fwd_from_partials("diga_bn_fwd_partials", x, ld_x, y, ld_y, residual, ld_r, gamma, beta, running_mean, running_var, save_mean,
                                 save_invstd, save_ab, M, C, relu, y_twin, relu_bits, momentum, eps, partial, chunk_rows, nullptr, 0,
                                 workspace, workspace_bytes, stream);
+}
+
+// as diga_bn_fwd_partials with relu and a residual that is still RAW: residual_ab [2][C] are the coefficients (save_ab of a y = null
+// call) of the BatchNorm whose apply pass is folded into this one's -- y = relu(fma(x, a, b) + fma(residual, ar, br))
+extern "C" int diga_bn_fwd_partials_resab(const float* x, int64_t ld_x, float* y, int64_t ld_y, const float* residual,
+                                          int64_t ld_r, const float* residual_ab, const float* gamma, const float* beta,
+                                          float* running_mean, float* running_var, float* save_mean, float* save_invstd,
+                                          int64_t M, int64_t C, unsigned char* relu_bits, float momentum, float eps,
+                                          const float* partial, int64_t chunk_rows, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+    DIGA_REQUIRE(residual_ab != nullptr, DIGA_EINVAL, "diga_bn_fwd_partials_resab: null residual coefficients");
+    return bn_fwd_from_partials("diga_bn_fwd_partials_resab", x, ld_x, y, ld_y, residual, ld_r, gamma, beta, running_mean, running_var,
+                                save_mean, save_invstd, nullptr, M, C, 1, 0, relu_bits, momentum, eps, partial, chunk_rows, nullptr, 0,
+                                workspace, workspace_bytes, stream, residual_ab);
 }
 
 extern "C" int diga_bn_fwd_records(const float* x, int64_t ld_x, float* y, int64_t ld_y, const float* residual,

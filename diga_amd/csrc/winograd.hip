@@ -21,7 +21,7 @@
 namespace diga {
 
 int gemm_batched_f32_dma(const float* A, int64_t rows_per_batch, int batches, int64_t K, const float* W, int64_t Cout,
-                         float* out, hipStream_t st);     // conv.hip
+                         float* out, hipStream_t st, int64_t rows_valid);     // conv.hip
 size_t wgrad_batched_slab_bytes(int64_t rows, int batches, int64_t Cout, int64_t Cin);                                   // conv.hip
 int wgrad_batched_f32_dma(const float* Z, const float* V, float* dU, float* slab, int64_t rows, int batches, int64_t Cout,
                           int64_t Cin, hipStream_t st);                                                                 // conv.hip
@@ -1080,7 +1080,7 @@ static int winograd_impl(const float* in, const float* wgt, const float* bias, f
         hipLaunchKernelGGL(wino_weight_kernel, dim3((unsigned)ceil_div(Cout * (Cin / 4), 256)), dim3(256), 0, st, wgt, U, (int)Cout, (int)Cin,
                            flip);
     launch_input(tile, in, in_ld, tab, V, g.Tp, Cin, H, W, dilation, st, reflect);
-    int rc = gemm_batched_f32_dma(V, g.Tp, P, Cin, U, Cout, Mb, st);
+    int rc = gemm_batched_f32_dma(V, g.Tp, P, Cin, U, Cout, Mb, st, g.T);       // (rows T .. Tp of every product are the zero rows of the padding tiles)
     if (rc) return rc;
     if (epi == nullptr && stats != nullptr) {
         if (tile == 6) launch_output_stats_m<6>(Mb, tab, bias, out, out_ld, g, Cout, stats, st);

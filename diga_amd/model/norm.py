@@ -57,21 +57,33 @@ class _BnFn(torch.autograd.Function):
     output: that conv's backward-data kernel finishes this BN's incoming gradient in its epilogue -- adds the
     residual-branch gradient (`box['dres']`, put there by the backward of the BN that took this BN's output as residual),
     applies this BN's ReLU mask and reduces sum g / sum g*xhat -- and leaves (pointer, partials) in `box['premasked']`;
-    backward() then only finalises and applies.  `res_box`: the box of the BN that produced `residual`."""
+    backward() then only finalises and applies.  `res_box`: the box of the BN that produced `residual`.
+
+    `defer_apply` (a dict, or None; no ReLU, no residual, statistics from the producing conv): statistics, running statistics and
+    coefficients as always, but NO apply pass -- the result is the raw input tensor, the coefficients go to `defer_apply['ab']`, and
+    the one BatchNorm that takes the result as `residual` applies them on load (`res_ab`, diga_bn_fwd_partials_resab).  The backward is the same:
+    a BatchNorm without ReLU needs x, not y."""
 
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var, training, relu, momentum, eps,
-                partials=None, twin_out=False, dx_twin=False, box=None, res_box=None):
+                partials=None, twin_out=False, dx_twin=False, box=None, res_box=None, res_ab=None, defer_apply=None):
         _lib.require_gpu(x)
         xn = nhwc(x.detach())
         n, h, w, c = xn.shape
         m = n * h * w
         rn = None if residual is None else nhwc(residual.detach())
-        y = torch.empty_like(xn)
+        plain_partials = partials is not None and training and not isinstance(partials[1], tuple)
+        if (defer_apply is not None or res_ab is not None) and not plain_partials:
+            raise RuntimeError("DigaBatchNorm2d: the folded downsample BatchNorm needs train-mode statistics from the producing conv")
+        if defer_apply is not None and (relu or residual is not None or twin_out or box is not None):
+            raise RuntimeError("DigaBatchNorm2d: defer_apply is the form of a BatchNorm without ReLU and residual")
+        if res_ab is not None and not (relu and residual is not None and not twin_out):
+            raise RuntimeError("DigaBatchNorm2d: residual coefficients need relu and a residual")
+        y = None if defer_apply is not None else torch.empty_like(xn)
         save_mean = torch.empty(c, dtype=torch.float32, device=xn.device)
         save_invstd = torch.empty_like(save_mean)
         # ReLU without residual: the backward re-derives the mask from x and the forward coefficients (no y read)
-        save_ab = torch.empty(2 * c, dtype=torch.float32, device=xn.device) if (relu and residual is None) else None
+        save_ab = torch.empty(2 * c, dtype=torch.float32, device=xn.device) if ((relu and residual is None) or defer_apply is not None) else None
         ws = _ws(m, 1, c, xn.device)
         # a BN with residual keeps its ReLU mask as one bit per element for the backward epilogue of the conv that reads
         # y (instead of y itself: 1/32 of the bytes); DIGA_RELU_BITS=0 reads y as before
@@ -87,6 +99,12 @@ class _BnFn(torch.autograd.Function):
                       _lib.ptr(save_invstd), _lib.ptr(save_ab), m, c, 1 if relu else 0, 1 if twin_out else 0,
                       _lib.ptr(bits), float(momentum), float(eps), _lib.ptr(partials[0]),
                       _lib.C.c_void_p(partials[0].data_ptr() + recs * 3 * c * 4), recs, _lib.ptr(wsr), wsr.numel(), _lib.stream())
+        elif res_ab is not None:
+            # the junction whose skip branch arrives raw, with its BatchNorm's coefficients
+            _lib.call("diga_bn_fwd_partials_resab", _lib.ptr(xn), c, _lib.ptr(y), c, _lib.ptr(rn), c, _lib.ptr(res_ab), _lib.ptr(weight),
+                      _lib.ptr(bias), _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(save_mean), _lib.ptr(save_invstd), m, c,
+                      _lib.ptr(bits), float(momentum), float(eps), _lib.ptr(partials[0]), int(partials[1]), _lib.ptr(ws), ws.numel(),
+                      _lib.stream())
         elif partials is not None and training:
             # the producing conv already reduced its output tile by tile: finalise + apply only
             _lib.call("diga_bn_fwd_partials", _lib.ptr(xn), c, _lib.ptr(y), c, _lib.ptr(rn), c, _lib.ptr(weight),
@@ -101,6 +119,13 @@ class _BnFn(torch.autograd.Function):
                       _lib.ptr(save_ab), m, c, 1 if training else 0, 1 if relu else 0, 1 if twin_out else 0,
                       _lib.ptr(bits),
                       float(momentum), float(eps), _lib.ptr(ws), ws.numel(), _lib.stream())
+        if defer_apply is not None:
+            ctx.save_for_backward(xn, None, weight, save_mean, save_invstd, None)
+            ctx.flags = (training, False)
+            ctx.dx_twin = False
+            ctx.box, ctx.res_box = None, None
+            defer_apply["ab"] = save_ab
+            return xn.permute(0, 3, 1, 2)
         ctx.save_for_backward(xn, y if (relu and save_ab is None) else None, weight, save_mean, save_invstd, save_ab)
         ctx.flags = (training, residual is not None)
         ctx.dx_twin = bool(dx_twin and c % 8 == 0)
@@ -129,7 +154,7 @@ class _BnFn(torch.autograd.Function):
                       _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(dx), c, _lib.ptr(dgamma), _lib.ptr(dbeta), m, c,
                       1 if training else 0, _lib.ptr(ws), ws.numel(), _lib.stream())
             return (dx.permute(0, 3, 1, 2), None, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None,
-                    None, None, None, None, None, None, None, None, None, None, None)
+                    None, None, None, None, None, None, None, None, None, None, None, None, None)
         pre = ctx.box.pop("premasked", None) if ctx.box is not None else None
         # (same buffer AND untouched since the conv wrote it: autograd sums a second gradient into a NEW tensor while the
         #  box holds a reference to this one; the version check also catches an in-place accumulation)
@@ -153,7 +178,7 @@ class _BnFn(torch.autograd.Function):
             ctx.res_box["dres"] = dres
             dres = None
         return (dx.permute(0, 3, 1, 2), None if dres is None else dres.permute(0, 3, 1, 2),
-                dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None)
+                dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 class DigaBatchNorm2d(nn.BatchNorm2d):
@@ -161,8 +186,10 @@ class DigaBatchNorm2d(nn.BatchNorm2d):
     G5/model/seg_model_noaux.py:64-76) -- gradients flow to the input only.  forward(x, residual, relu)
     computes relu(bn(x) + residual) in one pass."""
 
-    def forward(self, x, residual=None, relu=False, twin_out=False, dx_twin=False):
-        """twin_out (ReLU, no residual, C % 8 == 0): the result is written as the split twin the staging-free conv
+    def forward(self, x, residual=None, relu=False, twin_out=False, dx_twin=False, defer_apply=False):
+        """defer_apply: see _BnFn (the downsample BatchNorm of a bottleneck; the caller hands the result to exactly one BatchNorm
+        as `residual`).
+        twin_out (ReLU, no residual, C % 8 == 0): the result is written as the split twin the staging-free conv
         kernels read (same 4 bytes per element, diga_make_twin's format) INSTEAD of fp32; the returned tensor has the
         usual shape and dtype but holds twin bytes (`_diga_is_twin`) -- only a DigaConv2d on the twin path may read it."""
         if self.weight.requires_grad or self.bias.requires_grad:
@@ -182,8 +209,13 @@ class DigaBatchNorm2d(nn.BatchNorm2d):
                 if rb is not None and rb.get("consumer_ready") and "res_claimed" not in rb:
                     rb["res_claimed"] = True
                     res_box = rb
+        res_ab = getattr(residual, "_diga_res_ab", None) if residual is not None else None
+        holder = {} if defer_apply else None
         y = _BnFn.apply(x, residual, self.weight, self.bias, self.running_mean, self.running_var, training, relu,
-                        self.momentum, self.eps, getattr(x, "_diga_bn_partials", None), twin_out, bool(dx_twin), box, res_box)
+                        self.momentum, self.eps, getattr(x, "_diga_bn_partials", None), twin_out, bool(dx_twin), box, res_box,
+                        res_ab, holder)
+        if holder is not None:
+            y._diga_res_ab = holder["ab"]
         if twin_out:
             y._diga_is_twin = True
         if box is not None:
@@ -239,6 +271,12 @@ def bump_batches_tracked(model):
 
 def _relu_bits_enabled():
     return config.active().relu_bits
+
+
+def fold_downsample_bn_enabled():
+    """config.fold_downsample_bn = False keeps the downsample BatchNorm's own apply pass (the two-pass form the parity tests compare
+    against)."""
+    return config.active().fold_downsample_bn
 
 
 def fuse_backward_enabled():

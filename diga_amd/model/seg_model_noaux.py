@@ -99,6 +99,15 @@ class Bottleneck(nn.Module):
         y = self.bn2(self.conv2(y, twin_grad=tw2 and grad), relu=True, twin_out=tw3, dx_twin=tw2 and grad)
         if self.downsample is None:
             skip = x
+        elif (dn.fold_downsample_bn_enabled() and len(self.downsample) == 2 and self.training and self.bn3.training
+              and self.downsample[1].training and self.conv3.training and self.downsample[0].training
+              and self.conv3.emit_bn_stats and self.downsample[0].emit_bn_stats and self.conv3.out_channels % 4 == 0
+              and not self.downsample._forward_hooks and not self.downsample[1]._forward_hooks):
+            # the downsample BatchNorm (no ReLU) has one reader, bn3's junction pass below: in train mode, where conv3 and the
+            # downsample conv both leave their BatchNorm's statistics, it only finalises them and the junction applies its two
+            # coefficients to the raw downsample output on load -- no pass that writes a tensor to have it read once
+            skip = self.downsample[0](x, chain=chain) if chain is not None else self.downsample[0](x)
+            skip = self.downsample[1](skip, defer_apply=True)
         elif chain is not None:
             skip = self.downsample[1](self.downsample[0](x, chain=chain))
         else:

@@ -512,6 +512,16 @@ int diga_bn_fwd_partials(const float* x, int64_t ld_x, float* y, int64_t ld_y, c
                          int y_twin, unsigned char* relu_bits, float momentum, float eps, const float* partial,
                          int64_t chunk_rows, void* workspace, size_t workspace_bytes, void* stream);
 
+/* diga_bn_fwd_partials as the junction of a bottleneck whose skip branch ends in a BatchNorm of its own: `residual` is that branch's
+ * RAW convolution output and residual_ab [2][C] its BatchNorm's coefficients (save_ab of a y = NULL call) --
+ * y = relu(fma(x, a, b) + fma(residual, ar, br)), bit for bit what the two apply passes give, without the applied residual ever
+ * being written.  ReLU always, fp32 y, no save_ab (a BatchNorm with residual keeps y or relu_bits for its backward). */
+int diga_bn_fwd_partials_resab(const float* x, int64_t ld_x, float* y, int64_t ld_y, const float* residual, int64_t ld_r,
+                               const float* residual_ab, const float* gamma, const float* beta, float* running_mean,
+                               float* running_var, float* save_mean, float* save_invstd, int64_t M, int64_t C,
+                               unsigned char* relu_bits, float momentum, float eps, const float* partial, int64_t chunk_rows,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ... replaced by RECORDS of unequal size: partial [n_records][3][C] {sum (x - s), sum (x - s)^2, s}, counts [n_records] = the rows
  * behind each record (0 allowed), sum of counts = M -- what the Winograd forward's output transform writes (stats_partial of
  * diga_conv2d_winograd_f32: its tile groups hold different numbers of in-image pixels).  workspace as diga_bn_fwd_partials + 96 floats. */
