@@ -55,6 +55,7 @@ SIGNATURES = {
     "diga_confusion_matrix": (INT, [P, P, P, I64, I64, P]),
     "diga_two_scale_confusion": (INT, [P, I64, I64, P, I64, I64, P, P, P, I64, I64, I64, I64, P]),
     "diga_conv2d_nhwc_f32": (INT, [P, P, P, P] + [I64] * 17 + [P, INT, P]),
+    "diga_conv2d_nhwc_f32_infer": (INT, [P, P, P, P] + [I64] * 17 + [P, INT, P]),
     "diga_conv2d_stats_floats": (SZ, [I64, I64, I64, I64]),
     "diga_conv2d_stats_chunk_rows": (INT, [I64] * 13 + [INT]),
     "diga_conv2d_epi_chunk_rows": (INT, [I64] * 13 + [INT]),
@@ -82,6 +83,7 @@ SIGNATURES = {
     "diga_im2col_nchw": (INT, [P, P] + [I64] * 11 + [P]),
     "diga_norm_workspace_bytes": (SZ, [I64, I64, I64]),
     "diga_bn_fwd": (INT, [P, I64, P, I64, P, I64, P, P, P, P, P, P, P, I64, I64, INT, INT, INT, P, F32, F32, P, SZ, P]),
+    "diga_bn_eval_coefficients": (INT, [P, P, P, P, P, I64, F32, P]),
     "diga_bn_fwd_partials": (INT, [P, I64, P, I64, P, I64, P, P, P, P, P, P, P, I64, I64, INT, INT, P, F32, F32, P, I64, P, SZ, P]),
     "diga_bn_fwd_partials_resab": (INT, [P, I64, P, I64, P, I64, P, P, P, P, P, P, P, I64, I64, P, F32, F32, P, I64, P, SZ, P]),
     "diga_bn_fwd_records": (INT, [P, I64, P, I64, P, I64, P, P, P, P, P, P, P, I64, I64, INT, INT, P, F32, F32, P, P, I64, P, SZ, P]),
@@ -101,6 +103,7 @@ SIGNATURES = {
     "diga_conv2d_winograd_f32": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [INT, P, P, INT, P]),
     "diga_conv2d_winograd_f32_opts": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P, INT, P]),
     "diga_conv2d_winograd_f32_epi": (INT, [P, P, P, P, SZ] + [I64] * 9 + [INT, P, P, INT, P]),
+    "diga_conv2d_winograd_f32_infer": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P, INT, P]),
     "diga_conv2d_wgrad_winograd_workspace_bytes": (SZ, [I64] * 7 + [INT]),
     "diga_conv2d_wgrad_winograd_f32": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P]),
     "diga_conv2d_winograd_v_floats": (SZ, [I64] * 6),
@@ -160,6 +163,11 @@ class BwdEpilogue(C.Structure):
     """diga_bwd_epilogue_t of include/diga_hip.h."""
     _fields_ = [("addend", P), ("addend_ld", I64), ("mask_y", P), ("mask_ld", I64), ("x", P), ("x_ld", I64),
                 ("relu_ab", P), ("mean", P), ("invstd", P), ("partials", P), ("mask_bits", P), ("mask_bits_ld", I64)]
+
+
+class InferEpilogue(C.Structure):
+    """diga_infer_epilogue_t of include/diga_hip.h."""
+    _fields_ = [("ab", P), ("residual", P), ("residual_ld", I64), ("relu", INT)]
 
 
 # enum order of include/diga_hip.h

@@ -59,6 +59,7 @@ class StepConfig:
     fuse_bwd: bool = True                # residual-junction add + ReLU mask + BN-backward reduce in the backward-data epilogue
     junction_chain: bool = True
     fold_downsample_bn: bool = True      # the downsample BatchNorm's apply pass inside the junction relu(bn3(c3) + skip) that alone reads it
+    fold_eval_bn: bool = False           # eval-mode BatchNorm (+ skip, + ReLU) of the trunk inside the epilogue of the fp32 conv in front of it (bit-identical; offline passes)
     # ---- data parallelism (diga_amd/ddp.py)
     ddp_bucket_mb: int = 25
     ddp_grad_views: bool = True          # gradients live in the all-reduce buckets
@@ -97,6 +98,7 @@ class StepConfig:
         c.fuse_bwd = _flag("DIGA_FUSE_BWD", c.fuse_bwd)
         c.junction_chain = _flag("DIGA_JUNCTION_CHAIN", c.junction_chain)
         c.fold_downsample_bn = _flag("DIGA_FOLD_DOWNSAMPLE_BN", c.fold_downsample_bn)
+        c.fold_eval_bn = _flag("DIGA_FOLD_EVAL_BN", c.fold_eval_bn)
         c.ddp_bucket_mb = int(e("DIGA_DDP_BUCKET_MB", c.ddp_bucket_mb))
         c.ddp_grad_views = _flag("DIGA_DDP_GRAD_VIEWS", c.ddp_grad_views)
         c.ddp_overlap = _flag("DIGA_DDP_OVERLAP", c.ddp_overlap)
@@ -114,6 +116,8 @@ class StepConfig:
             raise ValueError(f"wgrad_hold must be >= 0, not {self.wgrad_hold!r}")
         if self.conv_math not in (0, 1, 2):
             raise ValueError(f"conv_math must be 0 (fp32), 1 (split bf16) or 2 (bf16x6), not {self.conv_math!r}")
+        if not isinstance(self.fold_eval_bn, bool):
+            raise ValueError(f"fold_eval_bn must be a bool, not {self.fold_eval_bn!r}")
         if self.winograd_max_tile not in (2, 4, 6):
             raise ValueError(f"winograd_max_tile must be 2, 4 or 6, not {self.winograd_max_tile!r}")
         return self

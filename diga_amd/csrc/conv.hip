@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <atomic>
 
 #include "common.h"
@@ -84,6 +85,12 @@ struct ConvArgs {
     // batched GEMM on conv_fwd_dma_kernel (winograd.hip): 256-row tile tm multiplies weight panel tm / wb_tiles
     int wb_tiles = 0;            // 0: one weight array for every tile
     int64_t wb_stride = 0;       // floats between weight panels
+    // inference epilogue (diga_infer_epilogue_t; read by the INF instantiations only):
+    // out = [relu](fma(acc + bias, a, b) [+ residual]) -- the eval-mode BatchNorm (+ skip, + ReLU) behind the conv
+    const float* i_ab = nullptr;     // [2][Cout]: a then b
+    const float* i_res = nullptr;    // nullable [M][i_res_ld]
+    int i_res_ld = 0;
+    int i_relu = 0;
 };
 
 // Logical input coordinate (in the optionally upsampled image, before padding) -> source pixel of `in`.
@@ -114,11 +121,11 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 // what the BatchNorm after the conv needs -- per channel sum(y - s), sum((y - s)^2) and s = the tile's first row,
 // over the tile's valid rows -- in exactly the layout colstats_partial_kernel produces with 128-row chunks, so the
 // BN forward skips its own statistics pass over the conv output.
-template <int TM, int TN, bool EPI = false, int NTHR = 256>
+template <int TM, int TN, bool EPI = false, int NTHR = 256, bool INF = false>
 __device__ __forceinline__ void drain_stage(const float* stage_in, const ConvArgs& a, int m0, int n0, int t, int tile_m,
                                             bool active = true);
 
-template <int TM, int TN, bool EPI = false>
+template <int TM, int TN, bool EPI = false, bool INF = false>
 __device__ __forceinline__ void epilogue_tile(f32x16 (&acc)[TM][TN], float* __restrict__ stage, const ConvArgs& a,
                                               int m0, int n0, int wm, int wn, int lane, int t, int tile_m) {
     constexpr int BN = 64 * TN, LDS_LD = BN + 4;
@@ -132,7 +139,7 @@ __device__ __forceinline__ void epilogue_tile(f32x16 (&acc)[TM][TN], float* __re
                 stage[(wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh) * LDS_LD + wn * 32 * TN + j * 32 + li] =
                     acc[i][j][e];
     __syncthreads();
-    drain_stage<TM, TN, EPI>(stage, a, m0, n0, t, tile_m);
+    drain_stage<TM, TN, EPI, 256, INF>(stage, a, m0, n0, t, tile_m);
 }
 
 // Row loop of the backward-data epilogue (drain_stage, EPI), one instantiation per operand combination:
@@ -213,12 +220,64 @@ __device__ __forceinline__ void epi_rows(const float* __restrict__ stage, const 
     }
 }
 
+// Row loop of the inference epilogue (drain_stage, INF): per element acc, + bias, fma(v, a, b), + residual, fmaxf(v, 0) -- the
+// expressions, in the order, of the conv's own store followed by affine_apply_kernel (norm.hip) on the stored value: the same bits
+// without the raw tensor ever reaching HBM.  Residual rows are taken eight at a time, all loads in flight before the first use,
+// with the running row pointers of epi_rows.  RES: a residual is given.  Entry points guarantee Cout % 4 == 0, lds % 4 == 0,
+// 16-byte aligned pointers.
+template <int TM, int TN, int NTHR, bool RES>
+__device__ __forceinline__ void infer_rows(const float* __restrict__ stage, const ConvArgs& a, int m0, int n, int cq, int rg,
+                                           const float4 bv) {
+    constexpr int BN = 64 * TN, LDS_LD = BN + 4, CQ = BN / 4, RG = NTHR / CQ, RPT = 128 / RG;
+    constexpr int RB = RPT >= 8 ? 8 : RPT;
+    const bool col_ok = n + 3 < a.Cout;
+    const int nn = col_ok ? n : 0;
+    const float4 ca = *reinterpret_cast<const float4*>(a.i_ab + nn), cb = *reinterpret_cast<const float4*>(a.i_ab + a.Cout + nn);
+    const int mlast = a.M - 1;
+    const int mfirst = m0 + rg;
+    const int64_t r0 = mfirst < a.M ? mfirst : mlast;
+    const float* pr = RES ? a.i_res + r0 * a.i_res_ld + nn : nullptr;
+    float* po = a.out + (int64_t)mfirst * a.out_ld + n;
+    const int64_t sr = (int64_t)RG * a.i_res_ld, so = (int64_t)RG * a.out_ld;
+    const bool whole = m0 + 128 <= a.M;                         // (uniform) every row of this half-tile exists
+    const bool relu = a.i_relu != 0;                            // (uniform)
+#pragma unroll
+    for (int k0 = 0; k0 < RPT; k0 += RB) {
+        float4 vr[RB];
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+            // rows beyond M (last tile only): the pointer stops advancing past the last row -- loads stay in bounds, nothing is stored
+            if (RES) {
+                vr[u] = *reinterpret_cast<const float4*>(pr);
+                if (k0 + u + 1 < RPT) pr += (whole || m0 + rg + RG * (k0 + u + 1) <= mlast) ? sr : 0;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+            const int r = rg + RG * (k0 + u);
+            float4 v = *reinterpret_cast<const float4*>(stage + r * LDS_LD + cq * 4);
+            v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
+            v.x = __builtin_fmaf(v.x, ca.x, cb.x); v.y = __builtin_fmaf(v.y, ca.y, cb.y);
+            v.z = __builtin_fmaf(v.z, ca.z, cb.z); v.w = __builtin_fmaf(v.w, ca.w, cb.w);
+            if (RES) {
+                v.x += vr[u].x; v.y += vr[u].y; v.z += vr[u].z; v.w += vr[u].w;
+            }
+            if (relu) {
+                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            }
+            if (col_ok && (whole || m0 + r < a.M)) store4_stream(po, v.x, v.y, v.z, v.w);
+            po += so;
+        }
+    }
+}
+
 // Second half of the epilogue: 128 staged rows x 64*TN columns (row stride 64*TN + 4 floats) -> global memory
 // (+ bias, + BatchNorm partials for 128-row chunk `tile_m`).  Entered after a barrier that follows the stage writes.
 // active = false: a thread group whose 128-row half lies beyond M still walks the barriers (nothing is stored).
 // EPI: the backward-data epilogue of diga_bwd_epilogue_t (its own instantiation of every kernel, so that the plain
 // kernels keep their register budget: inlined into the 256-register kernels the extra row buffers spilled).
-template <int TM, int TN, bool EPI, int NTHR>
+// INF: the inference epilogue of diga_infer_epilogue_t (infer_rows), likewise an instantiation of its own.
+template <int TM, int TN, bool EPI, int NTHR, bool INF>
 __device__ __forceinline__ void drain_stage(const float* stage_in, const ConvArgs& a, int m0, int n0, int t, int tile_m,
                                             bool active) {
     float* stage = const_cast<float*>(stage_in);
@@ -235,6 +294,11 @@ __device__ __forceinline__ void drain_stage(const float* stage_in, const ConvArg
         bv.y = n + 1 < a.Cout ? a.bias[n + 1] : 0.f;
         bv.z = n + 2 < a.Cout ? a.bias[n + 2] : 0.f;
         bv.w = n + 3 < a.Cout ? a.bias[n + 3] : 0.f;
+    }
+    if constexpr (INF) {
+        if (a.i_res != nullptr) infer_rows<TM, TN, NTHR, true>(stage, a, m0, n, cq, rg, bv);      // (uniform over the grid)
+        else infer_rows<TM, TN, NTHR, false>(stage, a, m0, n, cq, rg, bv);
+        return;
     }
     const float4 s0 = *reinterpret_cast<const float4*>(stage + cq * 4);       // tile row 0 (always a valid row)
     const float4 sh = make_float4(s0.x + bv.x, s0.y + bv.y, s0.z + bv.z, s0.w + bv.w);
@@ -381,8 +445,9 @@ __device__ __forceinline__ void mma_kstep(const float* __restrict__ As, const fl
 // ---------------------------------------------------------------------------------------------
 // block tile 128 x (64*TN) x BK; wave tile 64 x (32*TN).  BK = 32: 2 blocks per CU (74 KB LDS each);
 // BK = 16: 37 KB LDS, 3 blocks per CU (register-limited) -> a third wave per SIMD to cover barrier stalls.
-template <int TN, int BK, bool EPI = false>
+template <int TN, int BK, bool EPI = false, bool INF = false>
 __global__ __launch_bounds__(256, (BK == 16 ? 3 : 2)) void conv_fwd_kernel(ConvArgs a) {
+    static_assert(!INF || (BK == 32 && !EPI), "the inference epilogue lives in drain_stage (BK = 32 tiles)");
     constexpr int BM = 128, BN = 64 * TN, TM = 2;
     constexpr int LD = BK + 4;
     constexpr int CPR = BK / 4;          // float4 chunks per LDS row
@@ -484,7 +549,7 @@ __global__ __launch_bounds__(256, (BK == 16 ? 3 : 2)) void conv_fwd_kernel(ConvA
 
     // epilogue: accumulator register e of a 32x32 tile is row (e&3) + 8*(e>>2) + 4*(lane>>5), col lane&31
     if constexpr (BK == 32) {
-        epilogue_tile<TM, TN, EPI>(acc, smem, a, m0, n0, wm, wn, lane, t, tile_m);
+        epilogue_tile<TM, TN, EPI, INF>(acc, smem, a, m0, n0, wm, wn, lane, t, tile_m);
     } else {
         const int li = lane & 31, lh = lane >> 5;
 #pragma unroll
@@ -1283,7 +1348,7 @@ __device__ unsigned long long g_probe_stamps[8192 * 6];
 #ifndef DIGA_FWD_DMA_MINW
 #define DIGA_FWD_DMA_MINW 3           /* (A/B knob: 4 = a 128-register cap, so that apply-pass waves of the other stream fit next to it) */
 #endif
-template <bool EPI = false>
+template <bool EPI = false, bool INF = false>
 __global__ __launch_bounds__(768, DIGA_FWD_DMA_MINW) void conv_fwd_dma_kernel(ConvArgs a) {
     constexpr int BM = 256, BN = 128;
     constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
@@ -1464,7 +1529,7 @@ __global__ __launch_bounds__(768, DIGA_FWD_DMA_MINW) void conv_fwd_dma_kernel(Co
                 stage[((wm & 1) * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh) * LDS_LD + wn * 64 + j * 32 + li] = acc[i][j][e];
     __syncthreads();
     DIGA_STAMP(4);
-    drain_stage<2, 2, EPI>(stage, a, m0 + h * 128, n0, t, tile_m * 2 + h, m0 + h * 128 < a.M);
+    drain_stage<2, 2, EPI, 256, INF>(stage, a, m0 + h * 128, n0, t, tile_m * 2 + h, m0 + h * 128 < a.M);
     DIGA_STAMP(5);
 }
 
@@ -2465,6 +2530,23 @@ static int set_bwd_epilogue(ConvArgs& a, const diga_bwd_epilogue_t* e, const cha
     return DIGA_OK;
 }
 
+// fills the inference-epilogue fields of ConvArgs from the public descriptor (nullptr = plain convolution)
+static int set_infer_epilogue(ConvArgs& a, const diga_infer_epilogue_t* e, const char* who) {
+    a.i_ab = a.i_res = nullptr;
+    a.i_res_ld = a.i_relu = 0;
+    if (e == nullptr) return DIGA_OK;
+    DIGA_REQUIRE(e->ab != nullptr && aligned16(e->ab), DIGA_EINVAL, "%s: the inference epilogue needs 16-byte aligned coefficients ab [2][Cout]", who);
+    DIGA_REQUIRE(a.Cout % 4 == 0 && a.out_ld % 4 == 0 && aligned16(a.out) && (a.bias == nullptr || aligned16(a.bias)) && a.stats == nullptr,
+                 DIGA_EINVAL, "%s: the inference epilogue needs Cout %% 4 == 0, out_ld %% 4 == 0, 16-byte aligned pointers, no statistics", who);
+    DIGA_REQUIRE(!e->residual || (aligned16(e->residual) && e->residual_ld >= a.Cout && e->residual_ld % 4 == 0 && e->residual != a.out),
+                 DIGA_EINVAL, "%s: bad residual (16-byte aligned, residual_ld %% 4 == 0 and >= Cout, not the output)", who);
+    a.i_ab = e->ab;
+    a.i_res = e->residual;
+    a.i_res_ld = e->residual ? (int)e->residual_ld : 0;
+    a.i_relu = e->relu ? 1 : 0;
+    return DIGA_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Plain fp32 GEMM out [M x Cout] = A [M x K] * W^T (W [Cout][K], one panel per `wb_tiles` 256-row tiles) as a PERSISTENT
 // version of conv_fwd_dma_kernel: 256 blocks (one per CU), each walking its share of the 256 x 128 tiles in one continuous
@@ -2486,6 +2568,11 @@ struct GemmArgs {
     int64_t a_ld, out_ld;                            // floats between rows of A / out
     const float* bias;                               // nullable [Cout]
     float* stats;                                    // nullable [ceil(M / 64)][3][Cout]: {sum (y - s), sum (y - s)^2, s = first row} per 64-row chunk
+    // inference epilogue (diga_infer_epilogue_t; the INF instantiations only): out = [relu](fma(acc + bias, a, b) [+ residual])
+    const float* i_ab = nullptr;                     // [2][Cout]
+    const float* i_res = nullptr;                    // nullable [M][i_res_ld] (M * i_res_ld < 2^32: 32-bit element offsets, as out)
+    int64_t i_res_ld = 0;
+    int i_relu = 0;
 };
 
 // A 64-row wave piece whose rows are all padding (the row tail of the last tile: 97 x 97 maps leave 16 valid rows of 256 in it, in
@@ -2493,8 +2580,15 @@ struct GemmArgs {
 // its accumulators stay the +0 the MFMAs on zero rows would have left -- and only keeps the barriers.
 // STATS / BIAS: the drain's per-element statistics arithmetic and bias add exist only in the instantiation that stores them (the
 // Winograd-domain and backward-data launches pass neither); the remaining operations are the same, in the same order.
-template <bool STATS, bool BIAS>
+// INF (1: coefficients, 2: + residual; no STATS): the inference epilogue -- a finished accumulator leaves as
+// [relu](fma(acc + bias, a, b) [+ residual]), element for element what affine_apply_kernel (norm.hip) makes of the stored conv
+// output.  The coefficients of a lane's two columns and the first 32-row piece of the residual are requested BEFORE the tile's
+// last K-step: an MFMA wave that waits on vmcnt waits for its own earlier stores too, and at that point the previous tile's have
+// long drained.  The other three pieces are requested one piece ahead of their use, in front of the stores of the piece before
+// (the wait then leaves exactly those stores outstanding): 32 extra registers instead of 64.
+template <bool STATS, bool BIAS, int INF = 0>
 __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g) {
+    static_assert(INF == 0 || !STATS, "no statistics next to the inference epilogue");
     constexpr int A_BYTES = 256 * 128, B_BYTES = 128 * 128, STAGE = A_BYTES + B_BYTES;
     extern __shared__ __align__(16) unsigned char smem_b[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2592,12 +2686,50 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
     const int FA = F + wm * 64 * 128, FB = F + A_BYTES + wn * 64 * 128;
 #define DIGA_FOFF(t) ((t) << 5)
 
+    // inference epilogue: coefficients / bias of this lane's columns (col_w, col_w + 32) and two 32 x 32 residual pieces in flight
+    float i_ca[2], i_cb[2], i_bv[2], i_rv[2][16];
+    // piece p = 2 j + i: rows i * 32 .., columns j * 32 .. of the wave's 64 x 64; loaded with the addressing of its store
+    auto infer_load_piece = [&](int it_, int p, float (&dst)[16]) {
+        const int t = start + slot + nslots * it_;
+        const int tile_n = t % g.tiles_n, tile_m = t / g.tiles_n;
+        const int row_w = tile_m * 256 + wm * 64;
+        const unsigned rb = (unsigned)(row_w + 4 * lh) * (unsigned)g.i_res_ld + (unsigned)(tile_n * 128 + wn * 64 + li + (p >> 1) * 32);
+        const int rows_left = g.M - (row_w + 4 * lh);
+        if (row_w + 64 <= g.M) {                                 // (uniform)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int r = (p & 1) * 32 + (e & 3) + 8 * (e >> 2);
+                dst[e] = __builtin_nontemporal_load(g.i_res + (size_t)(rb + (unsigned)r * (unsigned)g.i_res_ld));
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int r = (p & 1) * 32 + (e & 3) + 8 * (e >> 2);
+                dst[e] = r < rows_left ? __builtin_nontemporal_load(g.i_res + (size_t)(rb + (unsigned)r * (unsigned)g.i_res_ld)) : 0.f;
+            }
+        }
+    };
+    auto infer_prefetch = [&](int it_) {
+        const int t = start + slot + nslots * it_;
+        const int col_w = (t % g.tiles_n) * 128 + wn * 64 + li;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            i_ca[j] = g.i_ab[col_w + j * 32];
+            i_cb[j] = g.i_ab[g.Cout + col_w + j * 32];
+            i_bv[j] = BIAS ? g.bias[col_w + j * 32] : 0.f;
+        }
+        if constexpr (INF == 2) infer_load_piece(it_, 0, i_rv[0]);
+    };
+
     __builtin_amdgcn_s_barrier();                                // stage 0 has landed
     int cur = 0;
     for (int it = 0; it < nmine; ++it) {
         if (!piece_live(it)) {
             // nothing but padding in this wave's 64 rows: the tile's barriers, no reads, no MFMAs
             for (int ks = 0; ks < ksteps; ++ks) {
+                if constexpr (INF != 0) {
+                    if (ks == ksteps - 1) infer_prefetch(it);
+                }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 cur = cur == 2 ? 0 : cur + 1;
@@ -2608,6 +2740,9 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
         // the <true, false> instantiation)
         __builtin_amdgcn_s_waitcnt(0xC07F);
         for (int ks = 0; ks < ksteps; ++ks) {
+        if constexpr (INF != 0) {
+            if (ks == ksteps - 1) infer_prefetch(it);
+        }
         const int sa = cur * STAGE + FA, sb = cur * STAGE + FB;      // (stage and wave bases are multiples of 8 KB: bits 5-6 stay F's)
 #define As_AT(t) (smem_b + (sa ^ DIGA_FOFF(t)))
 #define Bs_AT(t) (smem_b + (sb ^ DIGA_FOFF(t)))
@@ -2655,6 +2790,29 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
             const unsigned ob = (unsigned)(row_w + 4 * lh) * (unsigned)g.out_ld + (unsigned)col_w;
 #define DIGA_O_AT(r, j) (g.out + (size_t)(ob + (unsigned)(r) * (unsigned)g.out_ld + (unsigned)((j) * 32)))
             const int rows_left = g.M - (row_w + 4 * lh);                      // row offset r is valid iff r < rows_left
+            if constexpr (INF != 0) {
+                auto infer_drain = [&](auto full) {
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const int j = p >> 1, i = p & 1;
+                        if constexpr (INF == 2) {
+                            if (p + 1 < 4) infer_load_piece(it, p + 1, i_rv[(p + 1) & 1]);
+                        }
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) {
+                            const int r = i * 32 + (e & 3) + 8 * (e >> 2);
+                            float v = BIAS ? acc[i][j][e] + i_bv[j] : acc[i][j][e];
+                            v = __builtin_fmaf(v, i_ca[j], i_cb[j]);
+                            if constexpr (INF == 2) v += i_rv[p & 1][e];
+                            if (g.i_relu) v = fmaxf(v, 0.f);
+                            if (decltype(full)::value || r < rows_left) __builtin_nontemporal_store(v, DIGA_O_AT(r, j));
+                            acc[i][j][e] = 0.f;
+                        }
+                    }
+                };
+                if (row_w + 64 <= g.M) infer_drain(std::true_type{});          // (uniform branch, as below)
+                else infer_drain(std::false_type{});
+            } else {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 // (without a bias nothing is added: an accumulator that starts at +0 never holds -0, so `+ 0.f` changed no bit)
@@ -2709,6 +2867,7 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
                     }
                 }
             }
+            }
         }
     }
 }
@@ -2722,7 +2881,21 @@ static void launch_gemm_persistent(const GemmArgs& g, hipStream_t st) {
                                   (int)sh);                                                                                           \
         hipLaunchKernelGGL((gemm_f32_persistent_kernel<STATS_, BIAS_>), dim3(256), dim3(768), sh, st, g);                              \
     } while (0)
-    if (g.stats != nullptr) {
+#define DIGA_GEMM_PI(BIAS_, INF_)                                                                                                     \
+    do {                                                                                                                              \
+        (void)hipFuncSetAttribute((const void*)gemm_f32_persistent_kernel<false, BIAS_, INF_>,                                        \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);                                               \
+        hipLaunchKernelGGL((gemm_f32_persistent_kernel<false, BIAS_, INF_>), dim3(256), dim3(768), sh, st, g);                         \
+    } while (0)
+    if (g.i_ab != nullptr) {                          // the inference epilogue (no statistics: checked by the entry point)
+        if (g.i_res != nullptr) {
+            if (g.bias != nullptr) DIGA_GEMM_PI(true, 2);
+            else DIGA_GEMM_PI(false, 2);
+        } else {
+            if (g.bias != nullptr) DIGA_GEMM_PI(true, 1);
+            else DIGA_GEMM_PI(false, 1);
+        }
+    } else if (g.stats != nullptr) {
         if (g.bias != nullptr) DIGA_GEMM_P(true, true);
         else DIGA_GEMM_P(true, false);
     } else {
@@ -2730,6 +2903,7 @@ static void launch_gemm_persistent(const GemmArgs& g, hipStream_t st) {
         else DIGA_GEMM_P(false, false);
     }
 #undef DIGA_GEMM_P
+#undef DIGA_GEMM_PI
 }
 
 // `batches` independent products out_b [rows x Cout] = A_b [rows x K] * W_b^T (W_b [Cout][K]) in one launch of
@@ -2788,7 +2962,7 @@ static int conv2d_f32_impl(const float* in, const float* wgt, const float* bias,
                                     int64_t Cout, int64_t out_ld, int64_t R, int64_t S, int64_t stride_y,
                                     int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
                                     float* stats_partial, int prof_tag, void* stream, const diga_bwd_epilogue_t* epi,
-                                    const diga_conv_options_t* opts = nullptr) {
+                                    const diga_conv_options_t* opts = nullptr, const diga_infer_epilogue_t* inf = nullptr) {
     DIGA_REQUIRE(in && wgt && out, DIGA_EINVAL, "conv2d: null pointer");
     DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && Cout > 0 && R > 0 && S > 0, DIGA_EINVAL, "conv2d: bad shape");
     int rc = check_conv_common("conv2d", Cin, in_ld, out_ld, Cout, in, wgt, out);
@@ -2808,6 +2982,10 @@ static int conv2d_f32_impl(const float* in, const float* wgt, const float* bias,
     set_options(a, opts);
     rc = set_bwd_epilogue(a, epi, "conv2d");
     if (rc) return rc;
+    rc = set_infer_epilogue(a, inf, "conv2d_infer");
+    if (rc) return rc;
+    DIGA_REQUIRE(!inf || (!epi && !opts && (int64_t)a.M * (inf->residual ? inf->residual_ld : 0) < (1ll << 32)), DIGA_EINVAL,
+                 "conv2d_infer: not combinable with a backward epilogue / options; residual beyond 2^32 elements");
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD, st,
                    2.0 * (double)a.M * (double)Cout * (double)(R * S) * (double)Cin);
@@ -2820,6 +2998,7 @@ static int conv2d_f32_impl(const float* in, const float* wgt, const float* bias,
     do {                                                                                                               \
         const size_t sh = (size_t)(2 * 128 * (BK_ + 4) + 2 * 64 * TN_ * (BK_ + 4)) * sizeof(float);                     \
         if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_kernel<TN_, 32, true>), 256, sh);                                   \
+        else if (inf != nullptr) DIGA_LAUNCH_K((conv_fwd_kernel<TN_, 32, false, true>), 256, sh);                       \
         else DIGA_LAUNCH_K((conv_fwd_kernel<TN_, BK_, false>), 256, sh);                                                \
     } while (0)
     // 256 x 128 tiles, LDS-DMA operands (conv_fwd_dma_kernel): one block per CU, so nothing overlaps a tile's epilogue --
@@ -2835,6 +3014,7 @@ static int conv2d_f32_impl(const float* in, const float* wgt, const float* bias,
         g.A = in; g.W = wgt; g.out = out; g.M = a.M; g.K = (int)Cin; g.Cout = (int)Cout;
         g.tiles_m = (int)ceil_div(a.M, 256); g.tiles_n = (int)(Cout / 128); g.wb_tiles = 0; g.wb_stride = 0;
         g.a_ld = in_ld; g.out_ld = out_ld; g.bias = bias; g.stats = stats_partial; g.rows_valid = a.M;
+        g.i_ab = a.i_ab; g.i_res = a.i_res; g.i_res_ld = a.i_res_ld; g.i_relu = a.i_relu;
         launch_gemm_persistent(g, st);
         return launch_status("diga_conv2d_nhwc_f32");
     }
@@ -2846,6 +3026,9 @@ static int conv2d_f32_impl(const float* in, const float* wgt, const float* bias,
         if (epi != nullptr) {
             (void)hipFuncSetAttribute((const void*)conv_fwd_dma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
             hipLaunchKernelGGL(conv_fwd_dma_kernel<true>, dim3(grid), dim3(768), sh, st, a);
+        } else if (inf != nullptr) {
+            (void)hipFuncSetAttribute((const void*)conv_fwd_dma_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+            hipLaunchKernelGGL((conv_fwd_dma_kernel<false, true>), dim3(grid), dim3(768), sh, st, a);
         } else {
             (void)hipFuncSetAttribute((const void*)conv_fwd_dma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
             hipLaunchKernelGGL(conv_fwd_dma_kernel<false>, dim3(grid), dim3(768), sh, st, a);
@@ -2869,6 +3052,16 @@ extern "C" int diga_conv2d_nhwc_f32(const float* in, const float* wgt, const flo
                                     float* stats_partial, int prof_tag, void* stream) {
     return conv2d_f32_impl(in, wgt, bias, out, N, Hi, Wi, Cin, in_ld, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0, off_x0,
                            off_dy, off_dx, stats_partial, prof_tag, stream, nullptr);
+}
+
+extern "C" int diga_conv2d_nhwc_f32_infer(const float* in, const float* wgt, const float* bias, float* out, int64_t N,
+                                          int64_t Hi, int64_t Wi, int64_t Cin, int64_t in_ld, int64_t Ho, int64_t Wo,
+                                          int64_t Cout, int64_t out_ld, int64_t R, int64_t S, int64_t stride_y,
+                                          int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
+                                          const diga_infer_epilogue_t* infer, int prof_tag, void* stream) {
+    DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_infer: null epilogue descriptor");
+    return conv2d_f32_impl(in, wgt, bias, out, N, Hi, Wi, Cin, in_ld, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0, off_x0,
+                           off_dy, off_dx, nullptr, prof_tag, stream, nullptr, nullptr, infer);
 }
 
 extern "C" int diga_conv2d_nhwc_f32_epi(const float* in, const float* wgt, float* out, int64_t N, int64_t Hi, int64_t Wi,

@@ -151,8 +151,10 @@ __global__ void bn_eval_ab_kernel(const float* __restrict__ gamma, const float* 
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const float invstd = 1.f / sqrtf(running_var[c] + eps);
-    save_mean[c] = running_mean[c];
-    save_invstd[c] = invstd;
+    if (save_mean != nullptr) {                  // (null: diga_bn_eval_coefficients wants a, b only)
+        save_mean[c] = running_mean[c];
+        save_invstd[c] = invstd;
+    }
     const float a = invstd * gamma[c];
     ab[c] = a;
     ab[C + c] = beta[c] - running_mean[c] * a;
@@ -1070,6 +1072,15 @@ extern "C" int diga_bn_fwd(const float* x, int64_t ld_x, float* y, int64_t ld_y,
         launch_affine(dim3(ew_blocks(M * C / 4)), st, x, ld_x, y, ld_y, residual, ld_r, ab,
                            ab + C, (int64_t)0, M, M, (int)C, relu, y_twin, relu_bits);
     return launch_status("diga_bn_fwd");
+}
+
+extern "C" int diga_bn_eval_coefficients(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                         float* ab, int64_t C, float eps, void* stream) {
+    DIGA_REQUIRE(gamma && beta && running_mean && running_var && ab && C > 0 && C < (1ll << 31), DIGA_EINVAL,
+                 "bn_eval_coefficients: bad argument");
+    hipLaunchKernelGGL(bn_eval_ab_kernel, dim3((unsigned)ceil_div(C, 128)), dim3(128), 0, (hipStream_t)stream, gamma, beta, running_mean,
+                       running_var, (float*)nullptr, (float*)nullptr, ab, (int)C, eps);
+    return launch_status("diga_bn_eval_coefficients");
 }
 
 static int bn_fwd_from_partials(const char* who, const float* x, int64_t ld_x, float* y, int64_t ld_y, const float* residual,

@@ -637,6 +637,59 @@ __global__ __launch_bounds__(256) void winoM_output_kernel(const float* __restri
     }
 }
 
+// The inference epilogue of diga_infer_epilogue_t on one output vector: v (= transform + bias) -> [relu](fma(v, a, b) [+ residual]),
+// per component the expressions of affine_apply_kernel (norm.hip) on the value winoM_output_kernel would have stored.
+template <bool RES>
+__device__ __forceinline__ float infer_apply(float v, float a, float b, float r, bool relu) {
+    v = __builtin_fmaf(v, a, b);
+    if (RES) v += r;
+    return relu ? fmaxf(v, 0.f) : v;
+}
+template <bool RES>
+__device__ __forceinline__ float2 infer_apply(float2 v, float2 a, float2 b, float2 r, bool relu) {
+    return make_float2(infer_apply<RES>(v.x, a.x, b.x, r.x, relu), infer_apply<RES>(v.y, a.y, b.y, r.y, relu));
+}
+
+// winoM_output_kernel with the inference epilogue (a sibling, so that the plain kernel keeps its registers): the eval-mode
+// BatchNorm (+ residual, + ReLU) behind the layer applied before the store.  RES: a residual [N*H*W][res_ld] is given.
+template <int M, typename V, bool RES>
+__global__ __launch_bounds__(256) void winoM_output_infer_kernel(const float* __restrict__ Mb, const int4* __restrict__ tab,
+                                                                 const float* __restrict__ bias, float* __restrict__ y, int64_t ld,
+                                                                 int64_t T, int64_t Tp, int K, int H, int W, int d,
+                                                                 const float* __restrict__ ab, const float* __restrict__ res,
+                                                                 int64_t res_ld, int relu) {
+    constexpr int A = M + 2;
+    constexpr int VW = sizeof(V) / 4;
+    const int k4n = K / VW;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= T * k4n) return;
+    const int64_t t = idx / k4n;
+    const int k = (int)(idx - t * k4n) * VW;
+    const int4 e = tab[t];
+    V s[M][A];
+    winoM_load_rows<M, V>(Mb + t * K + k, Tp * K, s);
+    const V b = bias != nullptr ? *reinterpret_cast<const V*>(bias + k) : vzero<V>();
+    const V ca = *reinterpret_cast<const V*>(ab + k), cb = *reinterpret_cast<const V*>(ab + K + k);
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        const int yy = e.y + i * d;
+        if (yy >= H) continue;
+        V o[M];
+        Xf<M>::at(s[i], o);
+        const int64_t pix = (int64_t)(e.x * H + yy) * W;
+        float* row = y + pix * ld + k;
+        const float* rrow = RES ? res + pix * res_ld + k : nullptr;
+        V rv[M];
+#pragma unroll
+        for (int j = 0; j < M; ++j)
+            rv[j] = (RES && e.z + j * d < W) ? *reinterpret_cast<const V*>(rrow + (int64_t)(e.z + j * d) * res_ld) : vzero<V>();
+#pragma unroll
+        for (int j = 0; j < M; ++j)
+            if (e.z + j * d < W)
+                *reinterpret_cast<V*>(row + (int64_t)(e.z + j * d) * ld) = infer_apply<RES>(f4add(o[j], b), ca, cb, rv[j], relu != 0);
+    }
+}
+
 // winoM_output_kernel that also leaves the BatchNorm behind the layer its column statistics (round 5: the Winograd layers used to take a
 // separate statistics pass over y, 80 launches and ~9.5 GB per C2 step).  Block b = tiles [b * tpb, (b + 1) * tpb) x CG channel
 // groups of VW channels; thread (tl, q) walks tiles t0 + tl, t0 + tl + TL, ... (TL = 256 / CG tile lanes; a wave never spans two
@@ -925,6 +978,19 @@ static void launch_output_m(const float* Mb, const int4* tab, const float* bias,
     hipLaunchKernelGGL((winoM_output_kernel<M, VT>), dim3((unsigned)ceil_div(g.T * (Cout / VW), 256)), dim3(256), 0, st, Mb, tab, bias, out,
                        out_ld, g.T, g.Tp, (int)Cout, g.H, g.W, g.d);
 }
+template <int M>
+static void launch_output_infer_m(const float* Mb, const int4* tab, const float* bias, float* out, int64_t out_ld, const WinoGeom& g,
+                                  int64_t Cout, const diga_infer_epilogue_t& e, hipStream_t st) {
+    using VT = typename Vec<M>::Out;
+    constexpr int VW = sizeof(VT) / 4;
+    const dim3 grid((unsigned)ceil_div(g.T * (Cout / VW), 256));
+    if (e.residual != nullptr)
+        hipLaunchKernelGGL((winoM_output_infer_kernel<M, VT, true>), grid, dim3(256), 0, st, Mb, tab, bias, out, out_ld, g.T, g.Tp, (int)Cout,
+                           g.H, g.W, g.d, e.ab, e.residual, e.residual_ld, e.relu);
+    else
+        hipLaunchKernelGGL((winoM_output_infer_kernel<M, VT, false>), grid, dim3(256), 0, st, Mb, tab, bias, out, out_ld, g.T, g.Tp, (int)Cout,
+                           g.H, g.W, g.d, e.ab, (const float*)nullptr, (int64_t)0, e.relu);
+}
 // statistics records of the forward output transform: tiles per block and channel groups per block (see winoM_output_stats_kernel)
 struct WinoStatsPlan {
     int tpb, CG, TL;
@@ -1043,7 +1109,9 @@ static int winograd_impl(const float* in, const float* wgt, const float* bias, f
                          size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld,
                          int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile, int flip, const diga_bwd_epilogue_t* epi, int prof_tag,
                          void* stream, float* v_keep = nullptr, float* stats = nullptr,
-                         const void* tile_table = nullptr, int reflect = 0) {
+                         const void* tile_table = nullptr, int reflect = 0, const diga_infer_epilogue_t* inf = nullptr) {
+    DIGA_REQUIRE(!inf || ((tile == 4 || tile == 6) && !flip && !epi && !stats && !reflect), DIGA_EINVAL,
+                 "conv2d_winograd_infer: the inference epilogue comes with the plain forward of 4x4 / 6x6 tiles");
     DIGA_REQUIRE(!reflect || (tile != 2 && !flip && !epi && dilation < H && dilation < W), DIGA_EINVAL,
                  "conv2d_winograd: reflection padding comes with the forward of 4x4 / 6x6 tiles (pad < H, W)");
     DIGA_REQUIRE(in && wgt && out && workspace, DIGA_EINVAL, "conv2d_winograd: null pointer");
@@ -1085,6 +1153,9 @@ static int winograd_impl(const float* in, const float* wgt, const float* bias, f
     if (epi == nullptr && stats != nullptr) {
         if (tile == 6) launch_output_stats_m<6>(Mb, tab, bias, out, out_ld, g, Cout, stats, st);
         else launch_output_stats_m<4>(Mb, tab, bias, out, out_ld, g, Cout, stats, st);
+    } else if (epi == nullptr && inf != nullptr) {
+        if (tile == 6) launch_output_infer_m<6>(Mb, tab, bias, out, out_ld, g, Cout, *inf, st);
+        else launch_output_infer_m<4>(Mb, tab, bias, out, out_ld, g, Cout, *inf, st);
     } else if (epi == nullptr) {
         if (tile == 6) launch_output_m<6>(Mb, tab, bias, out, out_ld, g, Cout, st);
         else if (tile == 4) launch_output_m<4>(Mb, tab, bias, out, out_ld, g, Cout, st);
@@ -1150,6 +1221,20 @@ extern "C" int diga_conv2d_winograd_f32_opts(const float* in, const float* wgt, 
                  "conv2d_winograd_opts: only reflect_pad is folded on the Winograd path (upsampling / tanh: the direct `_opts` kernels)");
     return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, 0, nullptr,
                          prof_tag, stream, nullptr, nullptr, tile_table, opts->reflect_pad ? 1 : 0);
+}
+
+extern "C" int diga_conv2d_winograd_f32_infer(const float* in, const float* wgt, const float* bias, float* out, void* workspace,
+                                              size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld,
+                                              int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile,
+                                              const diga_infer_epilogue_t* infer, const void* tile_table, int prof_tag, void* stream) {
+    DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_winograd_infer: null epilogue descriptor");
+    DIGA_REQUIRE(infer->ab != nullptr && aligned16(infer->ab), DIGA_EINVAL,
+                 "conv2d_winograd_infer: the inference epilogue needs 16-byte aligned coefficients ab [2][Cout]");
+    DIGA_REQUIRE(!infer->residual || (aligned16(infer->residual) && infer->residual_ld >= Cout && infer->residual_ld % 4 == 0 &&
+                                      infer->residual != out),
+                 DIGA_EINVAL, "conv2d_winograd_infer: bad residual (16-byte aligned, residual_ld %% 4 == 0 and >= Cout, not the output)");
+    return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, 0, nullptr,
+                         prof_tag, stream, nullptr, nullptr, tile_table, 0, infer);
 }
 
 extern "C" size_t diga_conv2d_winograd_v_floats(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t dilation, int64_t tile) {

@@ -7,9 +7,17 @@ The upsample / max / argmax / confusion chain runs in one kernel (`diga_two_scal
 [N,19,1024,2048] upsampled tensors of the reference (159 MB each, per image) are never materialised and the
 prediction never leaves the device.
 """
+import contextlib
+
 import torch
 
-from diga_amd import _lib
+from diga_amd import _lib, config
+
+
+def _fold_ctx(fold_bn):
+    """fold_bn of the offline passes: None follows the active configuration (config.fold_eval_bn); True / False run the body with the
+    eval-mode BatchNorms of the trunk folded into the conv epilogues / as modules of their own (bit-identical results)."""
+    return contextlib.nullcontext() if fold_bn is None else config.override(fold_eval_bn=bool(fold_bn))
 
 
 def resize_bilinear_ac(x, size):
@@ -42,39 +50,42 @@ def two_scale_prediction(pred, pred_ds, size, gt=None, running=None, want_pred=T
 
 
 @torch.no_grad()
-def evaluate_two_scale(model, images, labels, running, ds_size=None, want_pred=False):
+def evaluate_two_scale(model, images, labels, running, ds_size=None, want_pred=False, fold_bn=None):
     """One validation batch: images [N,3,H,W], labels [N,H,W].  The model must be in eval() mode (the caller
-    decides, as the reference scripts do)."""
+    decides, as the reference scripts do).  fold_bn: see _fold_ctx."""
     H, W = labels.shape[-2:]
     ds_size = ds_size or (images.shape[-2] // 2, images.shape[-1] // 2)
     image_ds = resize_bilinear_ac(images, ds_size)
-    pred = model(images)[2]
-    pred_ds = model(image_ds)[2]
+    with _fold_ctx(fold_bn):
+        pred = model(images)[2]
+        pred_ds = model(image_ds)[2]
     return two_scale_prediction(pred, pred_ds, (H, W), labels, running, want_pred)
 
 
 @torch.no_grad()
-def generate_pseudo_labels(model, images, size=None, ds_size=None):
+def generate_pseudo_labels(model, images, size=None, ds_size=None, fold_bn=None):
     """Offline pseudo-label pass (G5/pseudolabel_generator.py:69-86): argmax of the softmax of the two-scale
     max-logits (softmax is monotone, so the argmax is taken on the fused logits directly) as uint8 train ids,
     ready to be written as palette PNGs by the caller."""
     size = size or tuple(images.shape[-2:])
     ds_size = ds_size or (images.shape[-2] // 2, images.shape[-1] // 2)
-    pred = model(images)[2]
-    pred_ds = model(resize_bilinear_ac(images, ds_size))[2]
+    with _fold_ctx(fold_bn):
+        pred = model(images)[2]
+        pred_ds = model(resize_bilinear_ac(images, ds_size))[2]
     return two_scale_prediction(pred, pred_ds, size).to(torch.uint8)
 
 
 @torch.no_grad()
-def initial_centroids(model, target_batches, class_features=None, epochs=5):
+def initial_centroids(model, target_batches, class_features=None, epochs=5, fold_bn=None):
     """Initial class centroids on the target domain (G5/calc_centroids.py:17-81, target branch): per batch the
     class-mean feature vectors of the model's own predictions update the bank in 'mean' mode.  `target_batches`
     is a re-iterable of image tensors; returns the Class_Features (its objective_vectors is what the reference
     torch.save()s to <centroid_dir>/feat_centroids)."""
     from diga_amd.calc_centroids import Class_Features
     cf = class_features or Class_Features(numbers=19)
-    for _ in range(epochs):
-        for images in target_batches:
-            _, _, out, feat = model(images)
-            cf.update_from_batch(feat, out, name='mean')
+    with _fold_ctx(fold_bn):
+        for _ in range(epochs):
+            for images in target_batches:
+                _, _, out, feat = model(images)
+                cf.update_from_batch(feat, out, name='mean')
     return cf

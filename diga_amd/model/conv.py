@@ -101,7 +101,8 @@ flop_log = None
 
 
 # a test or tool sets this to a dict to learn which kernels ran: (pass, arithmetic) -> launches, pass in "fwd" / "dgrad" / "wgrad",
-# arithmetic in "f32" / "bf16x3" / "bf16x6" / "winograd"
+# arithmetic in "f32" / "bf16x3" / "bf16x6" / "winograd"; "f32+bn" / "winograd+bn": a forward with the eval-mode BatchNorm behind it
+# folded into its epilogue (config.fold_eval_bn)
 path_log = None
 
 
@@ -239,11 +240,48 @@ def _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo):
     return ratio <= cfg.winograd_ratio and n * hi * wi * ratio * 9.0 / 256.0 < 32000
 
 
+def infer_kernel(n, hi, wi, cin, k, r, s, stride, padding, dilation, ho, wo, pointwise_ok=True):
+    """The forward kernel family with the inference epilogue (diga_infer_epilogue_t) a layer would run on under the active
+    configuration -- "f32+bn" (direct / LDS-DMA / persistent GEMM) or "winograd+bn" (4x4 / 6x6 tiles) -- or None where there is none:
+    a layer whose arithmetic is not exact fp32 (conv_math 1; pointwise layers in mode 2), Cout % 4 != 0, Winograd capped at 2x2 tiles.
+    cin: the padded input channel count."""
+    if k % 4 != 0 or _layer_math(r, s, cin, pointwise_ok) != 0:
+        return None
+    if _winograd_ok(n, hi, wi, cin, k, r, s, stride, (-padding[0], -padding[1]), tuple(dilation), ho, wo):
+        return "winograd+bn" if _wino_plan(hi, wi, dilation[0])[0] >= 4 else None
+    return "f32+bn"
+
+
+def _infer_epilogue(infer, out):
+    """(coefficients [2][K], residual NCHW-shaped or None, relu) -> (_lib.InferEpilogue, the tensors it points to)."""
+    ab, residual, relu = infer
+    e = _lib.InferEpilogue()
+    e.ab = _lib.ptr(ab)
+    rn = None
+    e.residual, e.residual_ld = None, 0
+    if residual is not None:
+        rn = residual.detach().permute(0, 2, 3, 1)
+        if tuple(rn.shape) != tuple(out.shape):
+            raise RuntimeError(f"DigaConv2d: residual {tuple(rn.shape)} does not match the output {tuple(out.shape)}")
+        if rn.dtype != torch.float32:
+            rn = rn.float()
+        ld = rn.stride(2)
+        if not (rn.stride(3) == 1 and ld >= rn.shape[3] and ld % 4 == 0 and rn.stride(1) == rn.shape[2] * ld
+                and rn.stride(0) == rn.shape[1] * rn.stride(1) and rn.data_ptr() % 16 == 0):
+            rn = rn.contiguous()
+            ld = rn.shape[3]
+        e.residual, e.residual_ld = _lib.ptr(rn), ld
+    e.relu = 1 if relu else 0
+    return e, (ab, rn)
+
+
 def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin_box=None, must_twin=False, epi=None,
-                 opts=None, keep_v=None, wino_stats=False, x6_ok=True):
+                 opts=None, keep_v=None, wino_stats=False, x6_ok=True, infer=None):
     """x [N,Hi,Wi,Cin] (contiguous or a channel slice of a contiguous tensor), w_krsc [K,R,S,Cin],
     out [N,Ho,Wo,K] (same rule).  twin_box: a one-element list shared by the convs that read the very same x.
     (In bf16x6 mode the box holds the three-plane triplet of x instead.)  x6_ok=False keeps a pointwise call off bf16x6 (the stem).
+    infer: (ab, residual, relu) -- forward only: the `_infer` entry points apply the eval-mode BatchNorm behind the conv (+ residual,
+    + ReLU) in the epilogue (diga_infer_epilogue_t); a layer without such a kernel (infer_kernel is None) raises.
     epi: a _lib.BwdEpilogue (backward-data only, bias-free): the `_epi` entry points finish the gradient in the epilogue.
     opts: (reflect_pad, upsample_shift, activation) = a diga_conv_options_t handed to the `_opts` entry points -- x is then the SOURCE tensor of the
     (virtually) upsampled / mirrored input."""
@@ -258,6 +296,12 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
     _, ho, wo, k = out.shape
     _, r, s, _ = w_krsc.shape
     math = _layer_math(r, s, cin, x6_ok and copt is None)
+    inf = keep_inf = None
+    if infer is not None:
+        if math != 0 or copt is not None or stats is not None or epi is not None or tag != _TAG_FWD or k % 4 != 0:
+            raise RuntimeError("DigaConv2d: no kernel with the inference epilogue for this call (exact-fp32 forward without statistics, "
+                               "Cout % 4 == 0; check infer_kernel / folds_eval_bn first)")
+        inf, keep_inf = _infer_epilogue(infer, out)
     if math == 2:
         # bf16x6: both operands pre-split into three bf16 planes, copied global -> LDS by LDS-DMA (csrc/conv_bf16x6.h)
         trip = twin_box[0] if twin_box is not None else None
@@ -351,11 +395,17 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
         tile, ratio = _wino_plan(hi, wi, d)
         if stats is not None and (tile < 4 or epi is not None or doff[0] < 0):
             raise RuntimeError("DigaConv2d: Winograd statistics come with the forward output transform of 4x4 / 6x6 tiles")
+        if inf is not None and tile < 4:
+            raise RuntimeError("DigaConv2d: the inference epilogue comes with Winograd tiles of 4x4 / 6x6 (winograd_max_tile = 2)")
         _log_flops(name, direct, direct * ratio)
-        _log_path(tag, "winograd")
+        _log_path(tag, "winograd+bn" if inf is not None else "winograd")
         nbytes = _lib.lib.diga_conv2d_winograd_workspace_bytes(n, hi, wi, cin, k, d, tile)
         ws = _lib.workspace(nbytes, x.device, "winograd")
         tab = _tile_table(n, hi, wi, d, tile, x.device)
+        if inf is not None:
+            _lib.call("diga_conv2d_winograd_f32_infer", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                      n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile, ctypes.byref(inf), _lib.ptr(tab), tag, _lib.stream())
+            return None
         if epi is not None:
             _lib.call("diga_conv2d_winograd_f32_epi", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
                       n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile, 1 if doff[0] < 0 else 0, ctypes.byref(epi), _lib.ptr(tab), tag,
@@ -374,7 +424,12 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
                   _lib.stream())
         return None
     _log_flops(name, direct, direct)
-    _log_path(tag, "f32")
+    _log_path(tag, "f32+bn" if inf is not None else "f32")
+    if inf is not None:
+        _lib.call("diga_conv2d_nhwc_f32_infer", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin,
+                  x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1],
+                  ctypes.byref(inf), tag, _lib.stream())
+        return None
     if epi is not None:
         _lib.call("diga_conv2d_nhwc_f32_epi", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(out), n, hi, wi, cin,
                   x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1],
@@ -395,7 +450,7 @@ class _StemConvFn(torch.autograd.Function):
     floats, then a 1x1 conv on the GEMM kernels.  No gradient wrt the input (it is the image)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, padding, dilation, stats=None, uses=None, twin_box=None):
+    def forward(ctx, x, weight, bias, stride, padding, dilation, stats=None, uses=None, twin_box=None, infer=None):
         _lib.require_gpu(x, weight)
         xc = x.detach().float().contiguous()                      # NCHW
         n, c, h, w_ = xc.shape
@@ -424,7 +479,7 @@ class _StemConvFn(torch.autograd.Function):
         w2 = _pad_last(weight.detach().permute(0, 2, 3, 1).reshape(k, 1, 1, kk).contiguous(), kp)
         out = torch.empty((n, ho, wo, k), dtype=torch.float32, device=x.device)
         b = None if bias is None else bias.detach().float().contiguous()
-        _conv_launch(xcol, w2, b, out, (1, 1), (0, 0), (1, 1), _TAG_FWD, stats, x6_ok=False)     # (bf16x6 mode: the stem stays exact fp32)
+        _conv_launch(xcol, w2, b, out, (1, 1), (0, 0), (1, 1), _TAG_FWD, stats, x6_ok=False, infer=infer)     # (bf16x6 mode: the stem stays exact fp32)
         ctx.save_for_backward(xcol)
         ctx.geom = (k, c, r, s, kk, kp, bias is not None, weight.stride())
         return out.permute(0, 3, 1, 2)
@@ -454,7 +509,7 @@ class _StemConvFn(torch.autograd.Function):
             dw.copy_(dwp[:k, 0, 0, :kk].reshape(k, r, s, c).permute(0, 3, 1, 2))
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(gy)
-        return None, dw, db, None, None, None, None, None, None
+        return None, dw, db, None, None, None, None, None, None, None
 
 
 def _set_mask(epi, box, xn, cp):
@@ -472,7 +527,7 @@ def _set_mask(epi, box, xn, cp):
 class _Conv2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding, dilation, stats=None, uses=None, twin_box=None, x_is_twin=False,
-                dy_is_twin=False, bn_box=None, opts=None, chain=None):
+                dy_is_twin=False, bn_box=None, opts=None, chain=None, infer=None):
         # x: NCHW-shaped; weight: [K,C,R,S] (any dense layout); returns an NCHW-shaped channels_last tensor
         _lib.require_gpu(x, weight)
         if x_is_twin:          # the producer wrote the split twin instead of fp32 (same bytes per element): hand it on
@@ -510,7 +565,7 @@ class _Conv2dFn(torch.autograd.Function):
                 and _winograd_ok(n, hi, wi, cp, k, r, s, stride, (-padding[0], -padding[1]), dilation, ho, wo)):
             keep_v = [None]
         x_twin = _conv_launch(xn, w, b, out, stride, (-padding[0], -padding[1]), dilation, _TAG_FWD, stats, twin_box,
-                              must_twin=bool(x_is_twin), opts=opts, keep_v=keep_v, wino_stats=wino_stats)
+                              must_twin=bool(x_is_twin), opts=opts, keep_v=keep_v, wino_stats=wino_stats, infer=infer)
         ctx.wino_v = keep_v[0] if keep_v is not None else None
         ctx.max_tile = config.active().winograd_max_tile      # (the kept transform's layout is the forward's tile: checked in backward)
         ctx.save_for_backward(xn, w)
@@ -781,7 +836,7 @@ class _Conv2dFn(torch.autograd.Function):
                                      + ((wino_v,) if wino_v is not None else ()))
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(gy)
-        return dx, dw, db, None, None, None, None, None, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class DigaConv2d(nn.Conv2d):
@@ -802,14 +857,60 @@ class DigaConv2d(nn.Conv2d):
             self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
         return self
 
-    def forward(self, x, twin_grad=False, opts=None, chain=None):
+    def _stem_path(self, x):
+        """image-like input: the few channels of all taps are gathered into the K dimension (_StemConvFn)"""
+        return (self.in_channels < 8 and not x.requires_grad and tuple(self.dilation) == (1, 1)
+                and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1])
+
+    def folds_eval_bn(self, x, bn, residual=None):
+        """True when this conv on `x` may run as conv + eval-mode BatchNorm `bn` (+ residual, + ReLU) in ONE kernel
+        (forward(..., infer=)): config.fold_eval_bn is on; nothing here is differentiated (grad mode off, or neither the input, the
+        residual nor this conv's parameters require grad); `bn` is in eval mode with running statistics; the layer's arithmetic is
+        exact fp32 on a kernel that has the inference epilogue (infer_kernel); Cout % 4 == 0; and neither module carries forward or
+        forward-pre hooks (a hook would see a tensor that no longer exists).  Bit-identical to the two-module form either way."""
+        if not config.active().fold_eval_bn:
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad) or self.weight.requires_grad
+                                        or (self.bias is not None and self.bias.requires_grad)):
+            return False
+        if (not isinstance(bn, nn.BatchNorm2d) or bn.training or bn.running_mean is None or bn.running_var is None or not bn.affine
+                or bn.num_features != self.out_channels or self.out_channels % 4 != 0):
+            return False
+        if self._forward_hooks or self._forward_pre_hooks or bn._forward_hooks or bn._forward_pre_hooks:
+            return False
+        if self.share_twin or getattr(x, "_diga_is_twin", False) or x.dim() != 4 or not x.is_cuda:
+            return False
+        n, _, h, w = x.shape
+        r, s = self.kernel_size
+        ho = (h + 2 * self.padding[0] - self.dilation[0] * (r - 1) - 1) // self.stride[0] + 1
+        wo = (w + 2 * self.padding[1] - self.dilation[1] * (s - 1) - 1) // self.stride[1] + 1
+        if self._stem_path(x):           # the im2col GEMM: a pointwise layer that stays exact fp32 in bf16x6 mode
+            return infer_kernel(n, ho, wo, _pad_to(r * s * self.in_channels), self.out_channels, 1, 1, (1, 1), (0, 0), (1, 1), ho, wo,
+                                pointwise_ok=False) is not None
+        return infer_kernel(n, h, w, _pad_to(self.in_channels), self.out_channels, r, s, tuple(self.stride), tuple(self.padding),
+                            tuple(self.dilation), ho, wo) is not None
+
+    def forward(self, x, twin_grad=False, opts=None, chain=None, infer=None):
         """twin_grad: the gradient of this conv's output will arrive as a split twin (the BatchNorm that consumes the
         output was called with dx_twin=True).  opts = (reflect_pad, upsample_shift, activation): inference-only input
-        map / output activation folded into the kernel (diga_conv_options_t, the `_opts` entry points)."""
+        map / output activation folded into the kernel (diga_conv_options_t, the `_opts` entry points).
+        infer = (bn_module, residual_or_None, relu): returns relu(bn(conv(x)) + residual) of an eval-mode BatchNorm from one kernel
+        (the `_infer` entry points; the caller has checked folds_eval_bn)."""
         fn = _Conv2dFn
-        if (self.in_channels < 8 and not x.requires_grad and tuple(self.dilation) == (1, 1)
-                and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1]):
+        if self._stem_path(x):
             fn = _StemConvFn           # image-like input: gather the few channels of all taps into the K dimension
+        if infer is not None:
+            from diga_amd.model.norm import eval_coefficients
+            if twin_grad or chain is not None or (opts is not None and any(opts)) or getattr(x, "_diga_is_twin", False):
+                raise RuntimeError("DigaConv2d: infer= is a plain forward (no twin gradient, chain, options or twin input)")
+            bn, residual, relu = infer
+            inf = (eval_coefficients(bn), residual, bool(relu))
+            with torch.no_grad():
+                if fn is _StemConvFn:
+                    return fn.apply(x, self.weight, self.bias, tuple(self.stride), tuple(self.padding), tuple(self.dilation), None, None,
+                                    None, inf)
+                return fn.apply(x, self.weight, self.bias, tuple(self.stride), tuple(self.padding), tuple(self.dilation), None, None,
+                                None, False, False, None, None, None, inf)
         stats = None
         if self.emit_bn_stats and self.training and self.out_channels % 4 == 0:
             n, _, h, w = x.shape

@@ -40,7 +40,9 @@ class SegModel(nn.Module):
         if self.training:
             dn.bump_batches_tracked(self)                     # one launch for the 104 BatchNorm step counters
         conv1, bn1, _relu, maxpool = self.layer0              # ReLU is fused into the BN kernel
-        shallow = self.layer2(self.layer1(maxpool(bn1(conv1(x), relu=True))))
+        # (config.fold_eval_bn: the eval-mode BatchNorm + ReLU of the stem inside the im2col GEMM's epilogue, as in the bottlenecks)
+        stem = conv1(x, infer=(bn1, None, True)) if conv1.folds_eval_bn(x, bn1) else bn1(conv1(x), relu=True)
+        shallow = self.layer2(self.layer1(maxpool(stem)))
         deep = self.layer4(self.layer3(shallow))
         if self.bn_clr:
             deep = self.bn_pretrain(deep)

@@ -181,6 +181,26 @@ class _BnFn(torch.autograd.Function):
                 dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
+def eval_coefficients(bn):
+    """[2][C] coefficients a, b of an eval-mode BatchNorm (y = fma(x, a, b)) from diga_bn_eval_coefficients -- the kernel
+    diga_bn_fwd(training = 0) runs, so the convolutions that fold the BatchNorm into their epilogue apply the very same bits.  Cached
+    on the module; the key is (_version, data_ptr) of weight, bias, running_mean, running_var and eps, so load_state_dict, .to() or an
+    in-place update recompute it (a train-mode forward, whose kernel updates the running statistics behind torch's back, drops the
+    cache itself): a steady offline pass launches nothing here."""
+    ts = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    key = tuple((t._version, t.data_ptr()) for t in ts) + (float(bn.eps),)
+    hit = bn.__dict__.get("_diga_eval_ab")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    c = bn.num_features
+    _lib.require_gpu(*ts)
+    ab = torch.empty(2 * c, dtype=torch.float32, device=bn.weight.device)
+    _lib.call("diga_bn_eval_coefficients", _lib.ptr(bn.weight.detach()), _lib.ptr(bn.bias.detach()), _lib.ptr(bn.running_mean),
+              _lib.ptr(bn.running_var), _lib.ptr(ab), c, float(bn.eps), _lib.stream())
+    bn.__dict__["_diga_eval_ab"] = (key, ab)
+    return ab
+
+
 class DigaBatchNorm2d(nn.BatchNorm2d):
     """BatchNorm2d whose affine parameters are frozen (the reference sets requires_grad=False on every BN,
     G5/model/seg_model_noaux.py:64-76) -- gradients flow to the input only.  forward(x, residual, relu)
@@ -196,6 +216,8 @@ class DigaBatchNorm2d(nn.BatchNorm2d):
             raise RuntimeError("DigaBatchNorm2d implements the frozen-affine BN of the DiGA path; "
                                "set requires_grad=False on weight and bias")
         training = self.training or self.running_mean is None
+        if training:
+            self.__dict__.pop("_diga_eval_ab", None)  # (the kernel below updates the running statistics: eval_coefficients' cache is stale)
         if getattr(self, "_nbt_external", False):
             self._nbt_external = False                # the model's forward bumped this counter for THIS call (bump_batches_tracked)
         elif self.training and self.num_batches_tracked is not None:

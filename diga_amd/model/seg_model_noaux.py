@@ -92,13 +92,25 @@ class Bottleneck(nn.Module):
         #  weight gradient -- the no-grad teacher takes it too; config.twin_conv3 = "2" restricts it to autograd passes as in round 1)
         c3 = config.active().twin_conv3
         tw3 = (grad or c3 != "2") and c3 != "0" and takes_twin_only_input(self.conv3, pointwise_ok=True)
-        y1 = self.conv1(x, chain=chain)
-        # (two forward fusions were built, measured slower and retired in round 6 -- tools/experiments/: bn1's apply pass inside conv2's
-        #  Winograd input transform, +5 ms per C2 step; bn3's residual junction inside the next block's conv1 GEMM, +5 ms)
-        y = self.bn1(y1, relu=True, twin_out=tw2)
-        y = self.bn2(self.conv2(y, twin_grad=tw2 and grad), relu=True, twin_out=tw3, dx_twin=tw2 and grad)
+        # Inference (config.fold_eval_bn, eval-mode BatchNorm, nothing differentiated): per (conv, BatchNorm) site the BatchNorm,
+        # its ReLU and -- at the junction -- the residual add run in the conv's epilogue (DigaConv2d.folds_eval_bn; bit-identical to
+        # the two-module form, which every site that does not qualify keeps)
+        if self.conv1.folds_eval_bn(x, self.bn1):
+            y = self.conv1(x, infer=(self.bn1, None, True))
+        else:
+            y1 = self.conv1(x, chain=chain)
+            # (two forward fusions were built, measured slower and retired in round 6 -- tools/experiments/: bn1's apply pass inside conv2's
+            #  Winograd input transform, +5 ms per C2 step; bn3's residual junction inside the next block's conv1 GEMM, +5 ms)
+            y = self.bn1(y1, relu=True, twin_out=tw2)
+        if self.conv2.folds_eval_bn(y, self.bn2):
+            y = self.conv2(y, infer=(self.bn2, None, True))
+        else:
+            y = self.bn2(self.conv2(y, twin_grad=tw2 and grad), relu=True, twin_out=tw3, dx_twin=tw2 and grad)
         if self.downsample is None:
             skip = x
+        elif (len(self.downsample) == 2 and not self.downsample._forward_hooks and not self.downsample._forward_pre_hooks
+              and self.downsample[0].folds_eval_bn(x, self.downsample[1])):
+            skip = self.downsample[0](x, infer=(self.downsample[1], None, False))
         elif (dn.fold_downsample_bn_enabled() and len(self.downsample) == 2 and self.training and self.bn3.training
               and self.downsample[1].training and self.conv3.training and self.downsample[0].training
               and self.conv3.emit_bn_stats and self.downsample[0].emit_bn_stats and self.conv3.out_channels % 4 == 0
@@ -112,6 +124,8 @@ class Bottleneck(nn.Module):
             skip = self.downsample[1](self.downsample[0](x, chain=chain))
         else:
             skip = self.downsample(x)
+        if self.conv3.folds_eval_bn(y, self.bn3, residual=skip):
+            return self.conv3(y, infer=(self.bn3, skip, True))
         return self.bn3(self.conv3(y, twin_grad=tw3), residual=skip, relu=True, dx_twin=tw3)
 
 
@@ -224,6 +238,8 @@ class ResNetMulti(nn.Module):
         return nn.Sequential(*seq)
 
     def stem(self, x):
+        if self.conv1.folds_eval_bn(x, self.bn1):
+            return self.maxpool(self.conv1(x, infer=(self.bn1, None, True)))
         return self.maxpool(self.bn1(self.conv1(x), relu=True))
 
     def forward(self, x):

@@ -289,6 +289,31 @@ int diga_conv2d_nhwc_twin_epi(const void* in_twin, const void* wgt_img, float* o
                               int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
                               int64_t off_dx, const diga_bwd_epilogue_t* epi, int prof_tag, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Forward with a fused INFERENCE epilogue: an eval-mode BatchNorm (running statistics: its a, b are constants of the checkpoint),
+ * the residual add and the ReLU behind a convolution applied to the accumulators on their way out, instead of the conv storing its
+ * raw output and diga_bn_fwd(training = 0) reading it back (one launch and two or three passes over the tensor per BatchNorm).
+ * Per element, in this order:  v = acc;  v += bias (where a bias is given, as the plain entry points add it);
+ * v = fma(v, a[c], b[c]);  v += residual;  v = fmaxf(v, 0) -- the expressions of the plain forward followed by diga_bn_fwd's apply
+ * pass on the stored fp32 value, so the result is bit-identical to that pair of calls with ab = diga_bn_eval_coefficients(...).
+ * Exact-fp32 kernels only (the direct / LDS-DMA / persistent-GEMM kernels and the Winograd output transform of 4x4 / 6x6 tiles).
+ * Cout % 4 == 0, out_ld % 4 == 0, residual_ld % 4 == 0 and >= Cout, all pointers 16-byte aligned, ab non-null; the residual may
+ * alias nothing the kernel writes; no statistics output.  Anything else: DIGA_EINVAL.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    const float* ab;        /* [2][Cout]: a then b, 16-byte aligned -- y = fma(acc (+ bias), a, b) */
+    const float* residual;  /* nullable [M][residual_ld], added after the fma */
+    int64_t residual_ld;
+    int relu;               /* fmaxf(., 0) last */
+} diga_infer_epilogue_t;
+
+/* diga_conv2d_nhwc_f32 without stats_partial, with the inference epilogue (non-null). */
+int diga_conv2d_nhwc_f32_infer(const float* in, const float* wgt, const float* bias, float* out,
+                               int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t in_ld,
+                               int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
+                               int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
+                               int64_t off_dy, int64_t off_dx, const diga_infer_epilogue_t* infer, int prof_tag, void* stream);
+
 /* Options of ONE forward convolution call (the `_opts` entry points below) -- the non-conv ops around the translator's
  * convolutions (G5/model/model_util.py:21-61: ReflectionPad2d -> Conv2d -> [norm] -> [activation];
  * G5/model/model_noaux.py:100-117: nn.Upsample(scale_factor=2) in front of a block) folded into the kernel's addressing
@@ -391,6 +416,12 @@ int diga_conv2d_winograd_f32_epi(const float* in, const float* wgt, float* out, 
                                  int64_t H, int64_t W, int64_t Cin, int64_t in_ld, int64_t Cout, int64_t out_ld, int64_t dilation,
                                  int64_t tile, int flip, const diga_bwd_epilogue_t* epi, const void* tile_table, int prof_tag,
                                  void* stream);
+/* Forward (flip = 0, no statistics) with the inference epilogue of diga_infer_epilogue_t in the output transform; tile = 4 or 6
+ * (tile 2: DIGA_EINVAL -- the caller runs the plain forward and diga_bn_fwd there). */
+int diga_conv2d_winograd_f32_infer(const float* in, const float* wgt, const float* bias, float* out, void* workspace,
+                                   size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld, int64_t Cout,
+                                   int64_t out_ld, int64_t dilation, int64_t tile, const diga_infer_epilogue_t* infer,
+                                   const void* tile_table, int prof_tag, void* stream);
 /* Backward-weight of the same layer through Winograd (dw [Cout][3][3][Cin] = G^T [sum over tiles (A dY A^T) (.) (B^T d B)] G):
  * transforms of dy and x, the 16 (tile 2) / 36 (tile 4) products contracted over the tiles in one launch of the fp32 LDS-DMA
  * backward-weight kernel (fixed-order split-K: bit-reproducible), the transform back to 3x3.  Cout % 256 == 0, Cin % 128 == 0. */
@@ -503,6 +534,11 @@ int diga_bn_fwd(const float* x, int64_t ld_x, float* y, int64_t ld_y, const floa
                 float* save_mean, float* save_invstd, float* save_ab, int64_t M, int64_t C, int training, int relu,
                 int y_twin, unsigned char* relu_bits, float momentum, float eps, void* workspace, size_t workspace_bytes,
                 void* stream);
+
+/* The coefficients diga_bn_fwd(training = 0) applies: ab [2][C], a = gamma / sqrt(running_var + eps), b = beta - running_mean * a --
+ * one launch of the very kernel diga_bn_fwd runs in eval mode, so that a caller of the `_infer` convolutions gets the same bits. */
+int diga_bn_eval_coefficients(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                              float* ab, int64_t C, float eps, void* stream);
 
 /* Train-mode diga_bn_fwd whose statistics pass is replaced by partials the producing conv already wrote
  * (`partial` = stats_partial of diga_conv2d_nhwc_*, `chunk_rows` = 128). */
