@@ -105,7 +105,16 @@ __global__ __launch_bounds__(256) void split_image3_kernel(const float* __restri
 // wave tile 64 x (32*TN), + 4 LDS-DMA loader waves; two-stage ring, one raw barrier per K-step (barrier k + 1 says both
 // "step k's MFMAs are done" and "stage k + 1 has landed").  Epilogue = conv_fwd_x3t8_kernel's (drain_stage).
 // ---------------------------------------------------------------------------------------------
-template <int TN, bool EPI = false>
+//
+// LS ("loader split", the `_f32in` entry points): a.in is the fp32 tensor itself ([pixel][in_ld], a channel slice of a wider
+// NHWC buffer included).  The loader lanes keep their rows, their k-slot and their 16-byte LDS slot; per row a lane reads its 8
+// channels as two float4 (a wave instruction covers 16 rows x 128 contiguous bytes), runs split3x4 -- the pass form's function, so
+// the planes are the same bits -- and writes the three planes with ds_write_b128 where the DMA form lands them.  The LDS image is
+// byte-identical: MFMA waves, fold accumulator and drain_stage are shared.  Weights stay pre-split images staged by LDS-DMA.
+// Schedule per K-step: loads of step k + 1 into registers + the weight DMA, vmcnt(0), split, ds_write, lgkmcnt(0), barrier (the
+// stage written was last read in step k - 1, behind the previous barrier).  No triplet pass and 4 instead of 6 B per element
+// through L2; the price is ~6 VALU instructions per element in the loader waves.
+template <int TN, bool EPI = false, bool LS = false>
 __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
     constexpr int BM = 256, BN = 64 * TN, NT = 2 * TN, MT = 4;
     constexpr int A_PLANE = BM * 64, B_PLANE = BN * 64, STAGE = 3 * A_PLANE + 3 * B_PLANE;
@@ -117,7 +126,72 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int ksteps = a.Cin / 32;
 
-    if (loader) {
+    if constexpr (LS) {
+      if (loader) {
+        const int lw = wv - 8;                                   // 0..3: A rows lw*64 + 16 j + (lane >> 2)
+        const int lrow = lane >> 2;
+        const int kslot = (lane & 3) ^ lds_swz(lrow);
+        const int HoWo = a.Ho * a.Wo;
+        const float* pa[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int m = min(m0 + lw * 64 + 16 * j + lrow, a.M - 1);
+            const int img = m / HoWo, rem = m - img * HoWo;
+            const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
+            const int iy = ho * a.sy + a.oy0, ix = wo * a.sx + a.ox0;
+            const bool ok = (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
+            pa[j] = ok ? a.in + ((int64_t)img * a.Hi * a.Wi + (int64_t)iy * a.Wi + ix) * a.in_ld + kslot * 8 : nullptr;
+        }
+        const unsigned char* bimg = a.wgt_img + (int64_t)tile_n * ksteps * (3 * B_PLANE) + (lw * 3 * TN) * 1024 + lane * 16;
+        float4 v[4][2];
+        auto issue = [&](int ks, int buf) {                      // global loads of step ks into registers + its weight DMA
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (pa[j] != nullptr) {
+                    v[j][0] = *reinterpret_cast<const float4*>(pa[j] + ks * 32);
+                    v[j][1] = *reinterpret_cast<const float4*>(pa[j] + ks * 32 + 4);
+                }
+            }
+            const unsigned char* bsrc = bimg + (int64_t)ks * (3 * B_PLANE);
+            unsigned char* bdst = smem_b + buf * STAGE + 3 * A_PLANE + (lw * 3 * TN) * 1024;
+#pragma unroll
+            for (int c = 0; c < 3 * TN; ++c) DIGA_LDS_DMA16(bsrc + c * 1024, bdst + c * 1024);
+        };
+        auto write = [&](int buf) {                              // split + three ds_write_b128 per row, then wait for them
+            unsigned char* stage = smem_b + buf * STAGE;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // a pixel outside the image: zero planes
+                if (pa[j] != nullptr) {
+                    uint2 a0, a1, a2, b0, b1, b2;
+                    split3x4(v[j][0], a0, a1, a2);
+                    split3x4(v[j][1], b0, b1, b2);
+                    q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
+                    q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
+                    q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
+                }
+                unsigned char* dst = stage + (lw * 64 + 16 * j) * 64 + lane * 16;
+                *reinterpret_cast<uint4*>(dst) = q0;
+                *reinterpret_cast<uint4*>(dst + A_PLANE) = q1;
+                *reinterpret_cast<uint4*>(dst + 2 * A_PLANE) = q2;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        };
+        issue(0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        write(0);
+        __builtin_amdgcn_s_barrier();                            // stage 0 has landed
+        for (int ks = 0; ks < ksteps; ++ks) {
+            if (ks + 1 < ksteps) {                               // (its stage was read by step ks - 1: behind the last barrier)
+                issue(ks + 1, (ks + 1) & 1);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                write((ks + 1) & 1);
+            }
+            __builtin_amdgcn_s_barrier();
+        }
+        return;
+      }
+    } else if (loader) {
         const int lw = wv - 8;                                   // 0..3: A rows lw*64 + 16 j + (lane >> 2)
         const unsigned char* trip = reinterpret_cast<const unsigned char*>(a.in);
         const int lrow = lane >> 2;
@@ -230,6 +304,11 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
 // with the fold accumulator, and a two-stage ring (72 KB stages).  256 (Cout) x 128 (Cin) tile per pixel range; four
 // MFMA waves (wave tile 128 x 64) + four loader waves; fragments through the transposing LDS reads.
 // ---------------------------------------------------------------------------------------------
+//
+// LS (diga_conv2d_wgrad_bf16x6_f32in): dy and x are the fp32 tensors ([pixel][dy_ld] / [pixel][x_ld]); the loader lanes keep row,
+// destination chunk, source-side swizzle and clamps, read their chunk's 8 channels as two float4, split (split3x4) and write the
+// three planes into the lane-linear LDS slots of the DMA form -- the same LDS bytes, so the same dw bits.
+template <bool LS = false>
 __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
     constexpr int BM = 256, BN = 128, MT = 8, NT = 4;
     constexpr int A_ROW = BM * 2, B_ROW = BN * 2;                       // bytes per pixel row and plane
@@ -252,7 +331,82 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
     if (p_end > a.M) p_end = a.M;
     const int ksteps = p_end > p_begin ? (p_end - p_begin + kBK - 1) / kBK : 0;
 
-    if (loader) {
+    if constexpr (LS) {
+      if (loader) {
+        const int* tab = a.ptab + (int64_t)tap * a.M_pad;
+        const int a_chunk_dst = lane & 31, b_chunk_dst = lane & 15;
+        const int kgrp = k0 / 8, cgrp = c0 / 8, kmax = a.Cout / 8 - 1, cmax = a.Cin / 8 - 1;
+        float4 va[4][2], vb[2][2];
+        bool okb[2];
+        auto issue = [&](int ks) {                          // global loads of step ks into registers
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int row = 8 * wv + 2 * j + (lane >> 5);
+                const int p = min(p_begin + ks * kBK + row, a.M - 1);
+                const int chunk = min(kgrp + (a_chunk_dst ^ (tr_key(row) << 1)), kmax);
+                const float* src = a.dy + (int64_t)p * a.dy_ld + chunk * 8;
+                va[j][0] = *reinterpret_cast<const float4*>(src);
+                va[j][1] = *reinterpret_cast<const float4*>(src + 4);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int row = 8 * wv + 4 * j + (lane >> 4);
+                const int p = p_begin + ks * kBK + row;
+                const int xi = p < p_end ? tab[p] : -1;
+                okb[j] = xi >= 0;
+                if (okb[j]) {
+                    const int chunk = min(cgrp + (b_chunk_dst ^ (tr_key(row) << 1)), cmax);
+                    const float* src = a.x + (int64_t)xi * a.x_ld + chunk * 8;
+                    vb[j][0] = *reinterpret_cast<const float4*>(src);
+                    vb[j][1] = *reinterpret_cast<const float4*>(src + 4);
+                }
+            }
+        };
+        auto write = [&](int stg) {                         // split + ds_write_b128 of the three planes, then wait for them
+            unsigned char* stage = smem_b + stg * STAGE;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint2 a0, a1, a2, b0, b1, b2;
+                split3x4(va[j][0], a0, a1, a2);
+                split3x4(va[j][1], b0, b1, b2);
+                unsigned char* dst = stage + (8 * wv + 2 * j) * A_ROW + lane * 16;
+                *reinterpret_cast<uint4*>(dst) = make_uint4(a0.x, a0.y, b0.x, b0.y);
+                *reinterpret_cast<uint4*>(dst + A_PLANE) = make_uint4(a1.x, a1.y, b1.x, b1.y);
+                *reinterpret_cast<uint4*>(dst + 2 * A_PLANE) = make_uint4(a2.x, a2.y, b2.x, b2.y);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // outside the image / past the pixel range: zero planes
+                if (okb[j]) {
+                    uint2 a0, a1, a2, b0, b1, b2;
+                    split3x4(vb[j][0], a0, a1, a2);
+                    split3x4(vb[j][1], b0, b1, b2);
+                    q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
+                    q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
+                    q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
+                }
+                unsigned char* dst = stage + 3 * A_PLANE + (8 * wv + 4 * j) * B_ROW + lane * 16;
+                *reinterpret_cast<uint4*>(dst) = q0;
+                *reinterpret_cast<uint4*>(dst + B_PLANE) = q1;
+                *reinterpret_cast<uint4*>(dst + 2 * B_PLANE) = q2;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        };
+        if (ksteps > 0) {
+            issue(0);
+            write(0);
+        }
+        __builtin_amdgcn_s_barrier();                      // stage 0 has landed
+        for (int ks = 0; ks < ksteps; ++ks) {
+            if (ks + 1 < ksteps) {                         // (its stage was read by step ks - 1: behind the last barrier)
+                issue(ks + 1);
+                write((ks + 1) & 1);
+            }
+            __builtin_amdgcn_s_barrier();
+        }
+        return;
+      }
+    } else if (loader) {
         const unsigned char* dyt = reinterpret_cast<const unsigned char*>(a.dy);
         const unsigned char* xt = reinterpret_cast<const unsigned char*>(a.x);
         const int64_t dy_rowb = (int64_t)a.Cout * 6, x_rowb = (int64_t)a.Cin * 6;
@@ -399,7 +553,8 @@ extern "C" int diga_split_bf16x6_image(const float* w, void* img, int64_t K, int
     return launch_status("diga_split_bf16x6_image");
 }
 
-static int conv2d_bf16x6_impl(const void* in_triplet, const void* wgt_img, const float* bias, float* out, int64_t N, int64_t Hi,
+// in_ld < 0: `in_triplet` is a triplet image (the pass form); else it is the fp32 tensor with that row pitch (the loader form)
+static int conv2d_bf16x6_impl(const void* in_triplet, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N, int64_t Hi,
                               int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
                               int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
                               float* stats_partial, int prof_tag, void* stream, const diga_bwd_epilogue_t* epi) {
@@ -407,6 +562,9 @@ static int conv2d_bf16x6_impl(const void* in_triplet, const void* wgt_img, const
     DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && Cout > 0, DIGA_EINVAL, "conv2d_bf16x6: bad shape");
     DIGA_REQUIRE(R == 1 && S == 1 && stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv2d_bf16x6: pointwise (1x1) convolutions only");
     DIGA_REQUIRE(Cin > 0 && Cin % 32 == 0 && out_ld >= Cout, DIGA_EINVAL, "conv2d_bf16x6: Cin must be a multiple of 32");
+    const bool f32in = in_ld >= 0;
+    DIGA_REQUIRE(!f32in || (in_ld >= Cin && in_ld % 4 == 0 && in_ld < (1ll << 31)), DIGA_EINVAL,
+                 "conv2d_bf16x6_f32in: in_ld must be at least Cin and a multiple of 4");
     DIGA_REQUIRE(aligned16(in_triplet) && aligned16(wgt_img) && ((uintptr_t)out & 3u) == 0, DIGA_EALIGN, "conv2d_bf16x6: alignment");
     DIGA_REQUIRE(N * Hi * Wi < (1ll << 31) && N * Ho * Wo < (1ll << 31), DIGA_EINVAL, "conv2d_bf16x6: too many pixels");
     // every output pixel reads an input pixel inside the image or zeros: the loader checks the coordinate, so any
@@ -414,7 +572,7 @@ static int conv2d_bf16x6_impl(const void* in_triplet, const void* wgt_img, const
     ConvArgs a;
     a.in = reinterpret_cast<const float*>(in_triplet); a.wgt = nullptr; a.wgt_hi = nullptr; a.wgt_lo = nullptr;
     a.wgt_img = reinterpret_cast<const unsigned char*>(wgt_img); a.bias = bias; a.out = out; a.stats = stats_partial;
-    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.in_ld = (int)Cin;
+    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.in_ld = f32in ? (int)in_ld : (int)Cin;
     a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.out_ld = (int)out_ld;
     a.R = 1; a.S = 1; a.sy = (int)stride_y; a.sx = (int)stride_x;
     a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
@@ -434,6 +592,16 @@ static int conv2d_bf16x6_impl(const void* in_triplet, const void* wgt_img, const
     const size_t ring = (size_t)2 * (3 * 256 * 64 + 3 * 64 * tn * 64);
     const size_t stg = (size_t)2 * 128 * (64 * tn + 4) * sizeof(float);
     const size_t sh = ring > stg ? ring : stg;
+    if (f32in) {
+        if (tn == 2) {
+            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, true, true>), 768, sh);
+            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true>), 768, sh);
+        } else {
+            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, true, true>), 768, sh);
+            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, true>), 768, sh);
+        }
+        return launch_status("diga_conv2d_nhwc_bf16x6_f32in");
+    }
     if (tn == 2) {
         if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, true>), 768, sh);
         else DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false>), 768, sh);
@@ -448,7 +616,7 @@ extern "C" int diga_conv2d_nhwc_bf16x6(const void* in_triplet, const void* wgt_i
                                        int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
                                        int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
                                        int64_t off_dy, int64_t off_dx, float* stats_partial, int prof_tag, void* stream) {
-    return conv2d_bf16x6_impl(in_triplet, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
+    return conv2d_bf16x6_impl(in_triplet, -1, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
                               off_x0, off_dy, off_dx, stats_partial, prof_tag, stream, nullptr);
 }
 
@@ -457,7 +625,28 @@ extern "C" int diga_conv2d_nhwc_bf16x6_epi(const void* in_triplet, const void* w
                                            int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
                                            int64_t off_dx, const diga_bwd_epilogue_t* epi, int prof_tag, void* stream) {
     DIGA_REQUIRE(epi != nullptr, DIGA_EINVAL, "conv2d_bf16x6_epi: null epilogue descriptor");
-    return conv2d_bf16x6_impl(in_triplet, wgt_img, nullptr, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
+    return conv2d_bf16x6_impl(in_triplet, -1, wgt_img, nullptr, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
+                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi);
+}
+
+extern "C" int diga_conv2d_nhwc_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out,
+                                             int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout,
+                                             int64_t out_ld, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0,
+                                             int64_t off_x0, int64_t off_dy, int64_t off_dx, float* stats_partial, int prof_tag,
+                                             void* stream) {
+    DIGA_REQUIRE(in_ld >= 0, DIGA_EINVAL, "conv2d_bf16x6_f32in: in_ld must be at least Cin and a multiple of 4");
+    return conv2d_bf16x6_impl(in, in_ld, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
+                              off_x0, off_dy, off_dx, stats_partial, prof_tag, stream, nullptr);
+}
+
+extern "C" int diga_conv2d_nhwc_bf16x6_f32in_epi(const float* in, int64_t in_ld, const void* wgt_img, float* out, int64_t N, int64_t Hi,
+                                                 int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
+                                                 int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0,
+                                                 int64_t off_x0, int64_t off_dy, int64_t off_dx, const diga_bwd_epilogue_t* epi,
+                                                 int prof_tag, void* stream) {
+    DIGA_REQUIRE(epi != nullptr, DIGA_EINVAL, "conv2d_bf16x6_f32in_epi: null epilogue descriptor");
+    DIGA_REQUIRE(in_ld >= 0, DIGA_EINVAL, "conv2d_bf16x6_f32in_epi: in_ld must be at least Cin and a multiple of 4");
+    return conv2d_bf16x6_impl(in, in_ld, wgt_img, nullptr, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
                               off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi);
 }
 
@@ -490,14 +679,18 @@ extern "C" size_t diga_conv2d_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho
     return wgrad_slab_bytes(plan_wgrad_x6(M, Cout, Cin), Cout, Cin, RS) + (size_t)RS * wgrad_mpad(M) * sizeof(int) + 64;
 }
 
-extern "C" int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_triplet, float* dw, void* workspace,
-                                        size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
-                                        int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
-                                        int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
+// dy_ld < 0: the operands are triplet images (the pass form); else the fp32 tensors with these row pitches (the loader form)
+static int conv2d_wgrad_bf16x6_impl(const void* dy_triplet, int64_t dy_ld, const void* x_triplet, int64_t x_ld, float* dw,
+                                    void* workspace, size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin,
+                                    int64_t Ho, int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
+                                    int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
+    const bool f32in = dy_ld >= 0;
     DIGA_REQUIRE(dy_triplet && x_triplet && dw && workspace, DIGA_EINVAL, "conv2d_wgrad_bf16x6: null pointer");
     DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: bad shape");
     DIGA_REQUIRE(R == 1 && S == 1 && stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: pointwise (1x1) convolutions only");
     DIGA_REQUIRE(Cin > 0 && Cin % 8 == 0 && Cout > 0 && Cout % 8 == 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: channel counts must be multiples of 8");
+    DIGA_REQUIRE(!f32in || (dy_ld >= Cout && dy_ld % 4 == 0 && x_ld >= Cin && x_ld % 4 == 0 && dy_ld < (1ll << 31) && x_ld < (1ll << 31)),
+                 DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count and multiples of 4");
     DIGA_REQUIRE(aligned16(dy_triplet) && aligned16(x_triplet) && aligned16(dw) && aligned16(workspace), DIGA_EALIGN, "conv2d_wgrad_bf16x6: alignment");
     DIGA_REQUIRE(N * Hi * Wi < (1ll << 31) && N * Ho * Wo < (1ll << 31), DIGA_EINVAL, "conv2d_wgrad_bf16x6: too many pixels");
     const int64_t RS = 1, M = N * Ho * Wo, M_pad = wgrad_mpad(M);
@@ -507,8 +700,8 @@ extern "C" int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_tr
     WgradArgs a;
     a.dy = reinterpret_cast<const float*>(dy_triplet); a.x = reinterpret_cast<const float*>(x_triplet);
     a.slab = p.splits > 1 ? (float*)workspace : dw;
-    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.x_ld = (int)Cin;
-    a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.dy_ld = (int)Cout;
+    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.x_ld = f32in ? (int)x_ld : (int)Cin;
+    a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.dy_ld = f32in ? (int)dy_ld : (int)Cout;
     a.R = 1; a.S = 1; a.sy = (int)stride_y; a.sx = (int)stride_x;
     a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
     a.M = (int)M; a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.splits = p.splits; a.steps_per_split = p.steps_per_split;
@@ -525,12 +718,34 @@ extern "C" int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_tr
     a.zeros = zeros;
     const unsigned grid = (unsigned)((int64_t)p.tiles_m * p.tiles_n * RS * p.splits);
     const size_t sh = (size_t)2 * (3 * kBK * 512 + 3 * kBK * 256);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_x6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    hipLaunchKernelGGL(conv_wgrad_x6_kernel, dim3(grid), dim3(512), sh, st, a);
+    if (f32in) {
+        (void)hipFuncSetAttribute((const void*)conv_wgrad_x6_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+        hipLaunchKernelGGL(conv_wgrad_x6_kernel<true>, dim3(grid), dim3(512), sh, st, a);
+    } else {
+        (void)hipFuncSetAttribute((const void*)conv_wgrad_x6_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+        hipLaunchKernelGGL(conv_wgrad_x6_kernel<false>, dim3(grid), dim3(512), sh, st, a);
+    }
     if (p.splits > 1) {
         const int64_t n4 = Cout * RS * Cin / 4;
         hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)workspace, dw, n4,
                            p.splits);
     }
-    return launch_status("diga_conv2d_wgrad_bf16x6");
+    return launch_status(f32in ? "diga_conv2d_wgrad_bf16x6_f32in" : "diga_conv2d_wgrad_bf16x6");
+}
+
+extern "C" int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_triplet, float* dw, void* workspace,
+                                        size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
+                                        int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
+                                        int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
+    return conv2d_wgrad_bf16x6_impl(dy_triplet, -1, x_triplet, -1, dw, workspace, workspace_bytes, N, Hi, Wi, Cin, Ho, Wo, Cout, R, S,
+                                    stride_y, stride_x, off_y0, off_x0, off_dy, off_dx, stream);
+}
+
+extern "C" int diga_conv2d_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
+                                              size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
+                                              int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
+                                              int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
+    DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
+    return conv2d_wgrad_bf16x6_impl(dy, dy_ld, x, x_ld, dw, workspace, workspace_bytes, N, Hi, Wi, Cin, Ho, Wo, Cout, R, S, stride_y,
+                                    stride_x, off_y0, off_x0, off_dy, off_dx, stream);
 }

@@ -71,6 +71,22 @@ def _use_x6(cin, r, s):
     return r == 1 and s == 1 and cin % 32 == 0
 
 
+def _x6_loader():
+    """bf16x6 operand form of the active configuration (config.x6_split, read per call): True = "loader", the GEMMs' loader waves
+    split the fp32 tensors themselves (the `_f32in` entry points: no triplet pass, no triplet buffer, channel slices read in place);
+    False = "pass", diga_make_triplet + the triplet entry points.  Bit-identical results."""
+    return config.active().x6_split == "loader"
+
+
+def _nhwc_ld(t):
+    """Row pitch (floats between pixels) of an NHWC tensor the `_f32in` kernels can read in place -- unit channel stride, dense pixel
+    order, pitch % 4 == 0, 16-byte aligned base: a contiguous tensor or a channel slice of one -- else None."""
+    ld = t.stride(2)
+    ok = (t.dtype == torch.float32 and t.stride(3) == 1 and ld >= t.shape[3] and ld % 4 == 0 and t.stride(1) == t.shape[2] * ld
+          and t.stride(0) == t.shape[1] * t.stride(1) and t.data_ptr() % 16 == 0)
+    return ld if ok else None
+
+
 def _layer_math(r, s, cin, pointwise_ok=True):
     """The arithmetic ONE layer runs in under the active conv_math: 0 / 1 as set; in mode 2 (bf16x6) 2 for an eligible layer
     (_use_x6) and 0 -- the exact-fp32 paths, Winograd included -- for every other one.  Every path decision and every `math`
@@ -101,7 +117,8 @@ flop_log = None
 
 
 # a test or tool sets this to a dict to learn which kernels ran: (pass, arithmetic) -> launches, pass in "fwd" / "dgrad" / "wgrad",
-# arithmetic in "f32" / "bf16x3" / "bf16x6" / "winograd"; "f32+bn" / "winograd+bn": a forward with the eval-mode BatchNorm behind it
+# arithmetic in "f32" / "bf16x3" / "bf16x6" / "bf16x6/ls" (bf16x6 with the operands split by the loader waves, config.x6_split = "loader") /
+# "winograd"; "f32+bn" / "winograd+bn": a forward with the eval-mode BatchNorm behind it
 # folded into its epilogue (config.fold_eval_bn)
 path_log = None
 
@@ -302,6 +319,26 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
             raise RuntimeError("DigaConv2d: no kernel with the inference epilogue for this call (exact-fp32 forward without statistics, "
                                "Cout % 4 == 0; check infer_kernel / folds_eval_bn first)")
         inf, keep_inf = _infer_epilogue(infer, out)
+    if math == 2 and _x6_loader():
+        # bf16x6, loader form: the weights as a pre-split image, the activations read as fp32 (in place: contiguous or a channel
+        # slice) and split by the loader waves -- no triplet is built, returned or looked for in the box
+        ld = _nhwc_ld(x)
+        if ld is None:
+            x = x.contiguous()
+            ld = cin
+        img = torch.empty(_lib.lib.diga_split_bf16x6_image_bytes(k, 1, cin), dtype=torch.uint8, device=x.device)
+        _lib.call("diga_split_bf16x6_image", _lib.ptr(w_krsc), _lib.ptr(img), k, 1, cin, _lib.stream())
+        _log_path(tag, "bf16x6/ls")
+        _log_flops("conv_bwd_data" if tag == _TAG_BWD_DATA else "conv_fwd", 2.0 * n * ho * wo * k * cin, 2.0 * n * ho * wo * k * cin)
+        if epi is not None:
+            _lib.call("diga_conv2d_nhwc_bf16x6_f32in_epi", _lib.ptr(x), ld, _lib.ptr(img), _lib.ptr(out), n, hi, wi, cin, ho, wo, k,
+                      out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], ctypes.byref(epi), tag,
+                      _lib.stream())
+            return None
+        _lib.call("diga_conv2d_nhwc_bf16x6_f32in", _lib.ptr(x), ld, _lib.ptr(img), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin, ho,
+                  wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], _lib.ptr(stats), tag,
+                  _lib.stream())
+        return None
     if math == 2:
         # bf16x6: both operands pre-split into three bf16 planes, copied global -> LDS by LDS-DMA (csrc/conv_bf16x6.h)
         trip = twin_box[0] if twin_box is not None else None
@@ -536,10 +573,14 @@ class _Conv2dFn(torch.autograd.Function):
                 raise RuntimeError("DigaConv2d: a twin-only input must be a dense NHWC float32-shaped buffer")
             twin_box = [xt.reshape(-1).view(torch.uint8)]
         xn = x.detach().permute(0, 2, 3, 1)
-        if not xn.is_contiguous() or xn.dtype != torch.float32:
-            xn = xn.contiguous().float()
         k, c, r, s = weight.shape
         cp = _pad_to(c)
+        # bf16x6 with the split in the loader waves reads a channel slice of a wider NHWC buffer in place (and saves that view for the
+        # weight gradient); every other path gets a dense copy
+        in_place = (cp == c and not x_is_twin and bn_box is None and chain is None and _x6_loader()
+                    and _layer_math(r, s, cp, opts is None or not any(opts)) == 2 and _nhwc_ld(xn) is not None)
+        if not in_place and (not xn.is_contiguous() or xn.dtype != torch.float32):
+            xn = xn.contiguous().float()
         xn = _pad_last(xn, cp)
         w = weight.detach().permute(0, 2, 3, 1)
         if not w.is_contiguous():
@@ -634,8 +675,9 @@ class _Conv2dFn(torch.autograd.Function):
         dy_box = [None] if use_tw else None            # the twin of dy: built once, read by backward-data and -weight
         lm = _layer_math(r, s, cp)                     # this layer's arithmetic (bf16x6 mode: 2 for pointwise layers, else 0)
         use_x6 = lm == 2
+        x6_ls = use_x6 and _x6_loader()                # ... with the operands split by the loader waves: no triplets (read per call)
         if use_x6:
-            dy_box = [None]                            # the triplet of dy, shared the same way
+            dy_box = [None]                            # the triplet of dy, shared the same way (stays empty in the loader form)
         if ctx.dy_is_twin:          # the BatchNorm after this conv wrote its dx as a twin (same bytes per element)
             if not (kp == k and _lib.get_conv_math() == 1 and cp > 64 and (use_tw or not ctx.needs_input_grad[1])):
                 raise RuntimeError("DigaConv2d: twin gradient on a layer that is not on the twin kernels")
@@ -769,21 +811,28 @@ class _Conv2dFn(torch.autograd.Function):
                     dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
 
             dy_trip = x_tr = None
-            if use_x6:
+            if use_x6 and not x6_ls:
                 dy_trip, x_tr = dy_box[0], x_trip
                 if dy_trip is None:                 # backward-data did not build it (no input gradient wanted)
                     dy_trip = torch.empty(n * ho * wo * kp * 6, dtype=torch.uint8, device=w.device)
                     _lib.call("diga_make_triplet", _lib.ptr(gyp), kp, _lib.ptr(dy_trip), n * ho * wo, kp, st)
                 if x_tr is None:                    # the forward ran in another arithmetic and saved none
                     x_tr = torch.empty(n * hi * wi * cp * 6, dtype=torch.uint8, device=w.device)
-                    _lib.call("diga_make_triplet", _lib.ptr(xn), cp, _lib.ptr(x_tr), n * hi * wi, cp, st)
+                    _lib.call("diga_make_triplet", _lib.ptr(xn), xn.stride(2), _lib.ptr(x_tr), n * hi * wi, cp, st)     # (xn may be a channel slice saved by the loader form)
             ctx.x_trip = None
 
             def run_x6():
-                _log_path("wgrad", "bf16x6")
+                _log_path("wgrad", "bf16x6/ls" if x6_ls else "bf16x6")
                 _log_flops("conv_bwd_weight", 2.0 * n * ho * wo * kp * cp, 2.0 * n * ho * wo * kp * cp)
                 nbytes = _lib.lib.diga_conv2d_wgrad_bf16x6_workspace_bytes(n, ho, wo, kp, cp, 1, 1)
                 ws = _lib.workspace(nbytes, w.device, "wgrad")
+                if x6_ls:                           # fp32 dy and x as they are (a saved triplet of x, if any, is ignored)
+                    _lib.call("diga_conv2d_wgrad_bf16x6_f32in", _lib.ptr(gyp), gyp.stride(2), _lib.ptr(xn), xn.stride(2), _lib.ptr(dwp),
+                              _lib.ptr(ws), ws.numel(), n, hi, wi, cp, ho, wo, kp, 1, 1, stride[0], stride[1], -padding[0], -padding[1],
+                              dilation[0], dilation[1], _lib.stream())
+                    if not alias:
+                        dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
+                    return
                 _lib.call("diga_conv2d_wgrad_bf16x6", _lib.ptr(dy_trip), _lib.ptr(x_tr), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(),
                           n, hi, wi, cp, ho, wo, kp, 1, 1, stride[0], stride[1], -padding[0], -padding[1], dilation[0],
                           dilation[1], _lib.stream())
@@ -832,7 +881,7 @@ class _Conv2dFn(torch.autograd.Function):
                 with torch.cuda.stream(side):
                     run()
                 dw.record_stream(side)          # (a returned gradient: never held, see _lib.release_to_side)
-                _lib.release_to_side(side, (gyp, xn) + (() if alias else (dwp,)) + ((dy_twin, x_twin) if use_tw else ()) + ((dy_trip, x_tr) if use_x6 else ())
+                _lib.release_to_side(side, (gyp, xn) + (() if alias else (dwp,)) + ((dy_twin, x_twin) if use_tw else ()) + ((dy_trip, x_tr) if (use_x6 and not x6_ls) else ())
                                      + ((wino_v,) if wino_v is not None else ()))
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(gy)

@@ -504,6 +504,26 @@ int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_triplet, floa
                              int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
                              int64_t off_dx, void* stream);
 
+/* bf16x6 straight from fp32 tensors ("loader split"): the same kernels with the three-plane split done by their loader waves on
+ * the way into LDS -- no diga_make_triplet pass, no triplet buffer, and the operands may be channel slices of wider NHWC buffers.
+ * `in` / `dy` / `x` are fp32 [pixel][ld] with ld >= the channel count, ld % 4 == 0 (else DIGA_EINVAL) and 16-byte aligned base
+ * pointers (else DIGA_EALIGN); wgt_img, bias, stats_partial, epi, the geometry, the channel-count rules (forward Cin % 32 == 0,
+ * weight gradient Cin % 8 == 0 and Cout % 8 == 0) and the workspace (diga_conv2d_wgrad_bf16x6_workspace_bytes) are those of the
+ * triplet forms above.  The planes and the order of the products are the same: results are bit-identical to diga_make_triplet
+ * followed by the triplet form. */
+int diga_conv2d_nhwc_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N,
+                                  int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
+                                  int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
+                                  int64_t off_dy, int64_t off_dx, float* stats_partial, int prof_tag, void* stream);
+int diga_conv2d_nhwc_bf16x6_f32in_epi(const float* in, int64_t in_ld, const void* wgt_img, float* out, int64_t N, int64_t Hi,
+                                      int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R,
+                                      int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
+                                      int64_t off_dx, const diga_bwd_epilogue_t* epi, int prof_tag, void* stream);
+int diga_conv2d_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
+                                   size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo,
+                                   int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0,
+                                   int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream);
+
 /* Stem (7x7/2 on the 3-channel NCHW image, G5/model/seg_model_noaux.py:221): out[n,ho,wo][(r*S+s)*C + c] =
  * x[n,c,ho*stride-pad+r,wo*stride-pad+s] (zero outside / beyond R*S*C up to Kpad), after which the conv is a
  * 1x1 conv with Cin = Kpad on the kernels above. */

@@ -2,11 +2,13 @@
 """Per-shape timing of the conv kernels (forward, backward-data, backward-weight) on the layer
 geometries of ResNet-101 DeepLabV2 at the C2 size (16 images of 768x768 -> 193x193 / 97x97 maps).
 
-    python tools/bench_conv.py [--images 16] [--reps 5] [--math f32|bf16x3|bf16x6]
+    python tools/bench_conv.py [--images 16] [--reps 5] [--math f32|bf16x3|bf16x6] [--x6-split pass|loader] [--pointwise-only]
 Prints one line per (shape, pass): ms, TFLOP/s, fraction of the 157.3 TFLOP/s fp32 MFMA peak, and the
 share of a training step's conv time that shape accounts for (count x time).
 --math bf16x6: the pointwise layers run on bf16x6, the rest on the exact-fp32 paths; the operand split passes are part of the
 figures (forward: inside the timed call; backward: the elementwise launches -- triplet of dy, weight images -- are added to dgrad).
+--x6-split loader: the bf16x6 GEMMs split their fp32 operands in the loader waves (config.x6_split): no triplet passes, the weight
+images remain.
 """
 import argparse
 import os
@@ -16,7 +18,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from diga_amd import _lib  # noqa: E402
+from diga_amd import _lib, config  # noqa: E402
 from diga_amd.model.conv import DigaConv2d  # noqa: E402
 
 PEAK = 157.3          # fp32 MFMA peak; the split-bf16 mode is priced against 2500 / 3 = 833.3, bf16x6 against 2500 / 6 (see --math)
@@ -55,15 +57,18 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", default=None)
     ap.add_argument("--math", default="f32", choices=["f32", "bf16x3", "bf16x6"])
+    ap.add_argument("--pointwise-only", action="store_true", help="time the 1x1 rows only (what --math bf16x6 changes)")
+    ap.add_argument("--x6-split", default="pass", choices=["pass", "loader"], help="bf16x6 operand form (config.x6_split)")
     a = ap.parse_args()
     _lib.set_conv_math(a.math)
+    config.active().x6_split = a.x6_split
     global PEAK
     PEAK = {"bf16x3": 2500.0 / 3.0, "bf16x6": 2500.0 / 6.0}.get(a.math, 157.3)
     dev = "cuda"
     rows, tot = [], {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}
     pw = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the pointwise (1x1) rows alone
     for name, count, cin, cout, k, stride, dil, hw in SHAPES:
-        if a.only and a.only not in name:
+        if (a.only and a.only not in name) or (a.pointwise_only and k != 1):
             continue
         pad = dil * (k - 1) // 2
         m = DigaConv2d(cin, cout, k, stride=stride, padding=pad, dilation=dil, bias=False).to(dev)
@@ -119,7 +124,7 @@ def main():
               f"{t_w:8.3f} {tf(t_w):6.1f} | {100 * count * t_f / tot['fwd']:.1f}% {100 * count * t_d / max(tot['dgrad'], 1e-9):.1f}% "
               f"{100 * count * t_w / max(tot['wgrad'], 1e-9):.1f}%")
     print(f"sum over one forward: fwd {tot['fwd']:.1f} ms, dgrad {tot['dgrad']:.1f} ms, wgrad {tot['wgrad']:.1f} ms")
-    print(f"pointwise rows, count-weighted ({a.math}): fwd {pw['fwd']:.2f} ms, dgrad {pw['dgrad']:.2f} ms, wgrad {pw['wgrad']:.2f} ms")
+    print(f"pointwise rows, count-weighted ({a.math}{'/' + a.x6_split if a.math == 'bf16x6' else ''}): fwd {pw['fwd']:.2f} ms, dgrad {pw['dgrad']:.2f} ms, wgrad {pw['wgrad']:.2f} ms")
 
 
 if __name__ == "__main__":

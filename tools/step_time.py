@@ -3,9 +3,13 @@
 synthetic data -- the figure bench.py reports for its headline leg, for arithmetics bench.py cannot select (bf16x6).
 
     python tools/step_time.py [--math f32 bf16x6] [--batch 8] [--size 768 768] [--steps 5] [--warmup 2] [--rounds 2] [--serial-streams]
+                              [--x6-split pass loader]
 The arithmetics are run alternately, `rounds` times each, in one process; every run builds fresh models from the same seed.
 --serial-streams switches the teacher / weight-gradient side streams off (kernel times add up: what the arithmetic changes by itself).
-Prints ms per step and crops/s per run and the last step's losses (the arithmetics must agree on them to rounding)."""
+--x6-split: the operand form(s) of bf16x6 (config.x6_split; "pass" = triplet passes, "loader" = split in the GEMMs' loader waves); with both,
+bf16x6 runs once per form in every round (the two must agree on the losses bit for bit).
+Prints ms per step and crops/s per run, the run's peak allocated / reserved device memory and the last step's losses (the arithmetics
+must agree on them to rounding)."""
 import argparse
 import os
 import random
@@ -23,14 +27,16 @@ from diga_amd.train_step import DigaTrainer  # noqa: E402
 MATH = {"f32": 0, "bf16x3": 1, "bf16x6": 2}
 
 
-def run(math, batch, h, w, steps, warmup, serial=False, dev="cuda"):
-    cfg = config.DEFAULTS.replace(conv_math=MATH[math])
+def run(math, batch, h, w, steps, warmup, serial=False, dev="cuda", x6_split="pass"):
+    cfg = config.DEFAULTS.replace(conv_math=MATH[math], x6_split=x6_split)
     if serial:
         cfg = cfg.serial_streams()
     prev = _lib.get_conv_math()
     _lib.set_conv_math(cfg.conv_math)
     try:
         torch.manual_seed(0)
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
         student, teacher = SegModel(arch=sm.RESNET101).to(dev), SegModel(arch=sm.RESNET101).to(dev)
         teacher.train()
         tr = DigaTrainer(student, teacher, rng=random.Random(1234), config=cfg)
@@ -48,7 +54,8 @@ def run(math, batch, h, w, steps, warmup, serial=False, dev="cuda"):
         e.record()
         torch.cuda.synchronize()
         _lib.join_side()
-        return s.elapsed_time(e) / steps, {k: round(float(v), 6) for k, v in out.items()}
+        mem = (torch.cuda.max_memory_allocated() / 2 ** 30, torch.cuda.max_memory_reserved() / 2 ** 30)
+        return s.elapsed_time(e) / steps, {k: round(float(v), 6) for k, v in out.items()}, mem
     finally:
         _lib.set_conv_math(prev)
 
@@ -62,12 +69,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--serial-streams", action="store_true")
+    ap.add_argument("--x6-split", nargs="+", default=["pass"], choices=["pass", "loader"], help="bf16x6 operand form(s) (config.x6_split)")
     a = ap.parse_args()
     for r in range(a.rounds):
         for math in a.math:
-            ms, out = run(math, a.batch, a.size[0], a.size[1], a.steps, a.warmup, a.serial_streams)
-            torch.cuda.empty_cache()
-            print(f"round {r + 1} {math:7s}: {ms:8.2f} ms per step = {a.batch * 1e3 / ms:6.2f} crops/s | last step: {out}", flush=True)
+            for form in (a.x6_split if math == "bf16x6" else ["pass"]):
+                ms, out, mem = run(math, a.batch, a.size[0], a.size[1], a.steps, a.warmup, a.serial_streams, x6_split=form)
+                torch.cuda.empty_cache()
+                label = math + ("/" + form if math == "bf16x6" else "")
+                print(f"round {r + 1} {label:13s}: {ms:8.2f} ms per step = {a.batch * 1e3 / ms:6.2f} crops/s | peak {mem[0]:.2f} GiB allocated, "
+                      f"{mem[1]:.2f} GiB reserved | last step: {out}", flush=True)
 
 
 if __name__ == "__main__":
