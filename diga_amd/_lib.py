@@ -111,6 +111,13 @@ SIGNATURES = {
     "diga_conv2d_wgrad_winograd_f32": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P]),
     "diga_conv2d_winograd_v_floats": (SZ, [I64] * 6),
     "diga_conv2d_winograd_f32_keep": (INT, [P, P, P, P, P, P, SZ] + [I64] * 9 + [P, P, INT, P]),
+    "diga_gemm_batched_bf16x6_f32in": (INT, [P, I64, I64, I64, P, I64, P, P]),
+    "diga_wgrad_batched_bf16x6_workspace_bytes": (SZ, [I64] * 4),
+    "diga_wgrad_batched_bf16x6_f32in": (INT, [P, P, P, P, SZ] + [I64] * 4 + [P]),
+    "diga_conv2d_winograd_bf16x6_workspace_bytes": (SZ, [I64] * 7),
+    "diga_conv2d_winograd_bf16x6": (INT, [P, P, P, P, P, P, SZ] + [I64] * 9 + [INT, P, P, P, INT, P]),
+    "diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes": (SZ, [I64] * 7 + [INT]),
+    "diga_conv2d_wgrad_winograd_bf16x6": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P]),
     "diga_conv2d_nhwc_bf16x3_epi": (INT, [P, P, P, P] + [I64] * 17 + [P, INT, P]),
     "diga_conv2d_nhwc_twin_epi": (INT, [P, P, P] + [I64] * 16 + [P, INT, P]),
     "diga_gn_fwd": (INT, [P, I64, P, I64, P, P, P, P, P, I64, I64, I64, I64, INT, F32, P, SZ, P]),

@@ -96,6 +96,32 @@ __global__ __launch_bounds__(256) void split_image3_kernel(const float* __restri
     }
 }
 
+// split_image3_kernel on `gridDim.y` stacked weight arrays (the Winograd-domain U [batches][K][C], RS = 1): batch b reads
+// w + b * w_stride floats and writes img + b * img_stride bytes -- each image byte for byte what the kernel above makes of U_b.
+__global__ __launch_bounds__(256) void split_image3_batched_kernel(const float* __restrict__ w, unsigned char* __restrict__ img,
+                                                                   int K, int C, int bn, int64_t total, int64_t w_stride,
+                                                                   int64_t img_stride) {
+    const int ksteps = C / 32;
+    w += (int64_t)blockIdx.y * w_stride;
+    img += (int64_t)blockIdx.y * img_stride;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int s = (int)(i & 3);
+        const int r = (int)((i >> 2) % bn);
+        const int64_t tk = (i >> 2) / bn;               // tile * ksteps + ks
+        const int ks = (int)(tk % ksteps), tile = (int)(tk / ksteps);
+        const int n = min(tile * bn + r, K - 1);
+        const float* src = w + (int64_t)n * C + ks * 32 + 8 * s;
+        uint2 a0, a1, a2, b0, b1, b2;
+        split3x4(*reinterpret_cast<const float4*>(src), a0, a1, a2);
+        split3x4(*reinterpret_cast<const float4*>(src + 4), b0, b1, b2);
+        const int64_t plane = (int64_t)bn * 64;
+        unsigned char* dst = img + tk * (3 * plane) + r * 64 + ((s ^ lds_swz(r)) << 4);
+        *reinterpret_cast<uint4*>(dst) = make_uint4(a0.x, a0.y, b0.x, b0.y);
+        *reinterpret_cast<uint4*>(dst + plane) = make_uint4(a1.x, a1.y, b1.x, b1.y);
+        *reinterpret_cast<uint4*>(dst + 2 * plane) = make_uint4(a2.x, a2.y, b2.x, b2.y);
+    }
+}
+
 #define DIGA_LDS_DMA16(src_, dst_)                                                                   \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_),         \
                                      (__attribute__((address_space(3))) void*)(dst_), 16, 0, 0)
@@ -114,7 +140,12 @@ __global__ __launch_bounds__(256) void split_image3_kernel(const float* __restri
 // Schedule per K-step: loads of step k + 1 into registers + the weight DMA, vmcnt(0), split, ds_write, lgkmcnt(0), barrier (the
 // stage written was last read in step k - 1, behind the previous barrier).  No triplet pass and 4 instead of 6 B per element
 // through L2; the price is ~6 VALU instructions per element in the loader waves.
-template <int TN, bool EPI = false, bool LS = false>
+//
+// WB ("weight batches", the Winograd-domain GEMMs: gemm_batched_bf16x6): the rows are `batches` stacked products of a.wb_tiles row
+// tiles each and row tile tile_m takes its weight image from batch tile_m / a.wb_tiles (a.wb_stride BYTES between the images; the
+// fp32 kernels use the two fields the same way, in floats).  Rows per batch are a multiple of 256, so no tile straddles two
+// batches; rows, slots, swizzle, ring, K-step order, MFMA waves and drain_stage are the un-batched kernel's -- so are a tile's bits.
+template <int TN, bool EPI = false, bool LS = false, bool WB = false>
 __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
     constexpr int BM = 256, BN = 64 * TN, NT = 2 * TN, MT = 4;
     constexpr int A_PLANE = BM * 64, B_PLANE = BN * 64, STAGE = 3 * A_PLANE + 3 * B_PLANE;
@@ -142,7 +173,9 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
             const bool ok = (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
             pa[j] = ok ? a.in + ((int64_t)img * a.Hi * a.Wi + (int64_t)iy * a.Wi + ix) * a.in_ld + kslot * 8 : nullptr;
         }
-        const unsigned char* bimg = a.wgt_img + (int64_t)tile_n * ksteps * (3 * B_PLANE) + (lw * 3 * TN) * 1024 + lane * 16;
+        const unsigned char* wimg = a.wgt_img;
+        if constexpr (WB) wimg += (int64_t)(tile_m / a.wb_tiles) * a.wb_stride;
+        const unsigned char* bimg = wimg + (int64_t)tile_n * ksteps * (3 * B_PLANE) + (lw * 3 * TN) * 1024 + lane * 16;
         float4 v[4][2];
         auto issue = [&](int ks, int buf) {                      // global loads of step ks into registers + its weight DMA
 #pragma unroll
@@ -308,7 +341,12 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
 // LS (diga_conv2d_wgrad_bf16x6_f32in): dy and x are the fp32 tensors ([pixel][dy_ld] / [pixel][x_ld]); the loader lanes keep row,
 // destination chunk, source-side swizzle and clamps, read their chunk's 8 channels as two float4, split (split3x4) and write the
 // three planes into the lane-linear LDS slots of the DMA form -- the same LDS bytes, so the same dw bits.
-template <bool LS = false>
+//
+// WB (wgrad_batched_bf16x6, the Winograd-domain weight gradient): `R * S` independent products dU_b = Z_b^T V_b, the batch riding
+// on the tap index as in conv_wgrad_dma_kernel -- tap b reads dy + b * a.dy_tap_stride and x + b * a.x_tap_stride (a.M rows each),
+// the pixel table is the identity (a.ptab is null and not read), and a block's pixel range is clamped (dy) and zero-filled (x)
+// within its batch's a.M rows.  The store is the un-batched one: slab [Cout][batches][Cin].
+template <bool LS = false, bool WB = false>
 __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
     constexpr int BM = 256, BN = 128, MT = 8, NT = 4;
     constexpr int A_ROW = BM * 2, B_ROW = BN * 2;                       // bytes per pixel row and plane
@@ -333,7 +371,13 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
 
     if constexpr (LS) {
       if (loader) {
-        const int* tab = a.ptab + (int64_t)tap * a.M_pad;
+        const int* tab = WB ? nullptr : a.ptab + (int64_t)tap * a.M_pad;
+        const float* dyb = a.dy;
+        const float* xb = a.x;
+        if constexpr (WB) {
+            dyb += (int64_t)tap * a.dy_tap_stride;
+            xb += (int64_t)tap * a.x_tap_stride;
+        }
         const int a_chunk_dst = lane & 31, b_chunk_dst = lane & 15;
         const int kgrp = k0 / 8, cgrp = c0 / 8, kmax = a.Cout / 8 - 1, cmax = a.Cin / 8 - 1;
         float4 va[4][2], vb[2][2];
@@ -344,7 +388,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
                 const int row = 8 * wv + 2 * j + (lane >> 5);
                 const int p = min(p_begin + ks * kBK + row, a.M - 1);
                 const int chunk = min(kgrp + (a_chunk_dst ^ (tr_key(row) << 1)), kmax);
-                const float* src = a.dy + (int64_t)p * a.dy_ld + chunk * 8;
+                const float* src = dyb + (int64_t)p * a.dy_ld + chunk * 8;
                 va[j][0] = *reinterpret_cast<const float4*>(src);
                 va[j][1] = *reinterpret_cast<const float4*>(src + 4);
             }
@@ -352,11 +396,15 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
             for (int j = 0; j < 2; ++j) {
                 const int row = 8 * wv + 4 * j + (lane >> 4);
                 const int p = p_begin + ks * kBK + row;
-                const int xi = p < p_end ? tab[p] : -1;
+                int xi = -1;
+                if (p < p_end) {
+                    if constexpr (WB) xi = p;
+                    else xi = tab[p];
+                }
                 okb[j] = xi >= 0;
                 if (okb[j]) {
                     const int chunk = min(cgrp + (b_chunk_dst ^ (tr_key(row) << 1)), cmax);
-                    const float* src = a.x + (int64_t)xi * a.x_ld + chunk * 8;
+                    const float* src = xb + (int64_t)xi * a.x_ld + chunk * 8;
                     vb[j][0] = *reinterpret_cast<const float4*>(src);
                     vb[j][1] = *reinterpret_cast<const float4*>(src + 4);
                 }
@@ -656,13 +704,14 @@ namespace {
 // rounded twice per K-step, the slabs are then added in fixed order by slab_reduce_kernel.  (plan_wgrad_wide, tuned for the
 // widest layers, leaves a narrow layer on ONE block walking every pixel: measured 5x the fp32 kernel's error on a 64 -> 64
 // layer over 37 636 pixels.)
-WgradPlan plan_wgrad_x6(int64_t M, int64_t Cout, int64_t Cin) {
+// RS: independent products sharing the launch (the batched Winograd-domain form; 1 for a pointwise layer).
+WgradPlan plan_wgrad_x6(int64_t M, int64_t Cout, int64_t Cin, int64_t RS = 1) {
     WgradPlan p;
     p.tm = 4;
     p.tn = 2;
     p.tiles_m = (int)ceil_div(Cout, 256);
     p.tiles_n = (int)ceil_div(Cin, 128);
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n, ksteps = ceil_div(M, kBK);
+    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n * RS, ksteps = ceil_div(M, kBK);
     int64_t splits = ceil_div(512, tiles);
     const int64_t max_splits = ksteps / 8 > 0 ? ksteps / 8 : 1;
     if (splits > max_splits) splits = max_splits;
@@ -748,4 +797,133 @@ extern "C" int diga_conv2d_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, co
     DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
     return conv2d_wgrad_bf16x6_impl(dy, dy_ld, x, x_ld, dw, workspace, workspace_bytes, N, Hi, Wi, Cin, Ho, Wo, Cout, R, S, stride_y,
                                     stride_x, off_y0, off_x0, off_dy, off_dx, stream);
+}
+
+// ---- the Winograd-domain GEMMs on bf16x6 (winograd.hip: diga_conv2d_winograd_bf16x6 / diga_conv2d_wgrad_winograd_bf16x6)
+namespace diga {
+
+// `batches` weight images, consecutive: image b = diga_split_bf16x6_image(U + b * Cout * K, ..., Cout, 1, K), one launch.
+int split_image3_batched(const float* U, void* imgs, int batches, int64_t Cout, int64_t K, hipStream_t st) {
+    const int64_t bn = image_bn(Cout);
+    const int64_t total = ceil_div(Cout, bn) * (K / 32) * bn * 4;
+    int64_t blocks = ceil_div(total, 256);
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(split_image3_batched_kernel, dim3((unsigned)blocks, (unsigned)batches), dim3(256), 0, st, U, (unsigned char*)imgs,
+                       (int)Cout, (int)K, (int)bn, total, Cout * K, (int64_t)diga_split_bf16x6_image_bytes(Cout, 1, K));
+    return DIGA_OK;
+}
+
+// shape rules of gemm_batched_bf16x6 (shared by the entry points' checks and the workspace queries)
+bool gemm_batched_bf16x6_ok(int64_t rows_per_batch, int64_t batches, int64_t K, int64_t Cout) {
+    if (rows_per_batch <= 0 || rows_per_batch % 256 != 0 || batches <= 0 || batches >= 65536 || K <= 0 || K % 32 != 0 || Cout <= 64 ||
+        Cout % 4 != 0)
+        return false;
+    const int64_t M = rows_per_batch * batches;
+    return M < (1ll << 31) && (M / 256) * ceil_div(Cout, 128) < (1ll << 31);
+}
+
+// out_b [rows x Cout] = A_b [rows x K] * W_b^T for `batches` products stacked row-wise (A [batches * rows][K] fp32, read in place
+// and split by the loader waves; out likewise; W_b as the b-th pre-split image of `imgs`) in one launch of
+// conv_fwd_x6_kernel<2, false, true, true>.  The arguments must pass gemm_batched_bf16x6_ok.
+int gemm_batched_bf16x6(const float* A, int64_t rows_per_batch, int batches, int64_t K, const void* imgs, int64_t Cout, float* out,
+                        hipStream_t st) {
+    DIGA_REQUIRE(gemm_batched_bf16x6_ok(rows_per_batch, batches, K, Cout), DIGA_EINVAL,
+                 "gemm_batched_bf16x6: rows %% 256, K %% 32, Cout %% 4 (> 64) required; rows * batches and the tile count below 2^31");
+    const int64_t M = rows_per_batch * batches;
+    ConvArgs a;
+    a.in = A; a.wgt = nullptr; a.wgt_hi = nullptr; a.wgt_lo = nullptr;
+    a.wgt_img = reinterpret_cast<const unsigned char*>(imgs); a.bias = nullptr; a.out = out; a.stats = nullptr;
+    a.N = 1; a.Hi = (int)(M / 256); a.Wi = 256; a.Cin = (int)K; a.in_ld = (int)K;
+    a.Ho = a.Hi; a.Wo = 256; a.Cout = (int)Cout; a.out_ld = (int)Cout;
+    a.R = 1; a.S = 1; a.sy = 1; a.sx = 1; a.oy0 = 0; a.ox0 = 0; a.ody = 1; a.odx = 1;
+    a.M = (int)M;
+    a.tiles_m = (int)(M / 256);
+    a.tiles_n = (int)ceil_div(Cout, 128);
+    a.all_inside = 1;
+    set_options(a, nullptr);
+    {
+        const int rc = set_bwd_epilogue(a, nullptr, "gemm_batched_bf16x6");
+        if (rc) return rc;
+    }
+    a.wb_tiles = (int)(rows_per_batch / 256);
+    a.wb_stride = (int64_t)diga_split_bf16x6_image_bytes(Cout, 1, K);        // (bytes: the images are byte arrays)
+    const size_t ring = (size_t)2 * (3 * 256 * 64 + 3 * 128 * 64);
+    const size_t stg = (size_t)2 * 128 * (128 + 4) * sizeof(float);
+    const size_t sh = ring > stg ? ring : stg;
+    DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true, true>), 768, sh);
+    return DIGA_OK;
+}
+
+bool wgrad_batched_bf16x6_ok(int64_t rows, int64_t batches, int64_t Cout, int64_t Cin) {
+    if (rows <= 0 || rows % 32 != 0 || rows >= (1ll << 31) || batches <= 0 || batches >= 65536 || Cout <= 0 || Cout % 256 != 0 ||
+        Cin <= 0 || Cin % 128 != 0)
+        return false;
+    const WgradPlan p = plan_wgrad_x6(rows, Cout, Cin, batches);
+    return (int64_t)p.tiles_m * p.tiles_n * batches * p.splits < (1ll << 31);
+}
+size_t wgrad_batched_bf16x6_slab_bytes(int64_t rows, int batches, int64_t Cout, int64_t Cin) {
+    return wgrad_slab_bytes(plan_wgrad_x6(rows, Cout, Cin, batches), Cout, Cin, batches);
+}
+// dU_b [Cout x Cin] = Z_b^T V_b (contraction over the rows) for `batches` products in one launch of
+// conv_wgrad_x6_kernel<true, true>: Z [batches][rows][Cout], V [batches][rows][Cin] fp32, dU [Cout][batches][Cin]; split-K by
+// plan_wgrad_x6 (at least 8 K-steps per block, about two rounds of blocks), partial sums in `slab`
+// (wgrad_batched_bf16x6_slab_bytes), added in fixed order.  The arguments must pass wgrad_batched_bf16x6_ok.
+int wgrad_batched_bf16x6(const float* Z, const float* V, float* dU, float* slab, int64_t rows, int batches, int64_t Cout, int64_t Cin,
+                         hipStream_t st) {
+    DIGA_REQUIRE(wgrad_batched_bf16x6_ok(rows, batches, Cout, Cin), DIGA_EINVAL,
+                 "wgrad_batched_bf16x6: rows %% 32, Cout %% 256, Cin %% 128 required; rows and the block count below 2^31");
+    const WgradPlan p = plan_wgrad_x6(rows, Cout, Cin, batches);
+    WgradArgs a;
+    a.dy = Z; a.x = V; a.slab = p.splits > 1 ? slab : dU;
+    a.N = 1; a.Hi = 1; a.Wi = (int)rows; a.Cin = (int)Cin; a.x_ld = (int)Cin;
+    a.Ho = 1; a.Wo = (int)rows; a.Cout = (int)Cout; a.dy_ld = (int)Cout;
+    a.R = 1; a.S = batches; a.sy = 1; a.sx = 1; a.oy0 = 0; a.ox0 = 0; a.ody = 1; a.odx = 1;
+    a.M = (int)rows; a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.splits = p.splits; a.steps_per_split = p.steps_per_split;
+    a.ptab = nullptr; a.zeros = nullptr; a.M_pad = (int)rows;
+    a.dy_tap_stride = rows * Cout;
+    a.x_tap_stride = rows * Cin;
+    const unsigned grid = (unsigned)((int64_t)p.tiles_m * p.tiles_n * batches * p.splits);
+    const size_t sh = (size_t)2 * (3 * kBK * 512 + 3 * kBK * 256);
+    (void)hipFuncSetAttribute((const void*)conv_wgrad_x6_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    hipLaunchKernelGGL((conv_wgrad_x6_kernel<true, true>), dim3(grid), dim3(512), sh, st, a);
+    if (p.splits > 1) {
+        const int64_t n4 = Cout * batches * Cin / 4;
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)slab, dU, n4, p.splits);
+    }
+    return DIGA_OK;
+}
+
+}  // namespace diga
+
+extern "C" int diga_gemm_batched_bf16x6_f32in(const float* A, int64_t rows_per_batch, int64_t batches, int64_t K, const void* wgt_imgs,
+                                              int64_t Cout, float* out, void* stream) {
+    DIGA_REQUIRE(A && wgt_imgs && out, DIGA_EINVAL, "gemm_batched_bf16x6_f32in: null pointer");
+    DIGA_REQUIRE(gemm_batched_bf16x6_ok(rows_per_batch, batches, K, Cout), DIGA_EINVAL,
+                 "gemm_batched_bf16x6_f32in: rows_per_batch %% 256, K %% 32, Cout %% 4 (> 64) required; rows_per_batch * batches and "
+                 "the tile count below 2^31");
+    DIGA_REQUIRE(aligned16(A) && aligned16(wgt_imgs) && aligned16(out), DIGA_EALIGN, "gemm_batched_bf16x6_f32in: pointers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof(DIGA_PROF_CONV_FWD, st, 2.0 * (double)(rows_per_batch * batches) * (double)Cout * (double)K);
+    const int rc = gemm_batched_bf16x6(A, rows_per_batch, (int)batches, K, wgt_imgs, Cout, out, st);
+    return rc ? rc : launch_status("diga_gemm_batched_bf16x6_f32in");
+}
+
+extern "C" size_t diga_wgrad_batched_bf16x6_workspace_bytes(int64_t rows, int64_t batches, int64_t Cout, int64_t Cin) {
+    if (!wgrad_batched_bf16x6_ok(rows, batches, Cout, Cin)) return 0;
+    return wgrad_batched_bf16x6_slab_bytes(rows, (int)batches, Cout, Cin) + 64;
+}
+
+extern "C" int diga_wgrad_batched_bf16x6_f32in(const float* Z, const float* V, float* dU, void* workspace, size_t workspace_bytes,
+                                               int64_t rows, int64_t batches, int64_t Cout, int64_t Cin, void* stream) {
+    DIGA_REQUIRE(Z && V && dU && workspace, DIGA_EINVAL, "wgrad_batched_bf16x6_f32in: null pointer");
+    DIGA_REQUIRE(wgrad_batched_bf16x6_ok(rows, batches, Cout, Cin), DIGA_EINVAL,
+                 "wgrad_batched_bf16x6_f32in: rows %% 32, Cout %% 256, Cin %% 128 required; rows and the block count below 2^31");
+    DIGA_REQUIRE(aligned16(Z) && aligned16(V) && aligned16(dU) && aligned16(workspace), DIGA_EALIGN,
+                 "wgrad_batched_bf16x6_f32in: pointers must be 16-byte aligned");
+    DIGA_REQUIRE(workspace_bytes >= diga_wgrad_batched_bf16x6_workspace_bytes(rows, batches, Cout, Cin), DIGA_EWORKSPACE,
+                 "wgrad_batched_bf16x6_f32in: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)(rows * batches) * (double)Cout * (double)Cin);
+    const int rc = wgrad_batched_bf16x6(Z, V, dU, (float*)workspace, rows, (int)batches, Cout, Cin, st);
+    return rc ? rc : launch_status("diga_wgrad_batched_bf16x6_f32in");
 }

@@ -25,6 +25,15 @@ int gemm_batched_f32_dma(const float* A, int64_t rows_per_batch, int batches, in
 size_t wgrad_batched_slab_bytes(int64_t rows, int batches, int64_t Cout, int64_t Cin);                                   // conv.hip
 int wgrad_batched_f32_dma(const float* Z, const float* V, float* dU, float* slab, int64_t rows, int batches, int64_t Cout,
                           int64_t Cin, hipStream_t st);                                                                 // conv.hip
+// the same two products on bf16x6 (conv_bf16x6.h): fp32 operands split by the loader waves, the weights as pre-split images
+int split_image3_batched(const float* U, void* imgs, int batches, int64_t Cout, int64_t K, hipStream_t st);
+bool gemm_batched_bf16x6_ok(int64_t rows_per_batch, int64_t batches, int64_t K, int64_t Cout);
+int gemm_batched_bf16x6(const float* A, int64_t rows_per_batch, int batches, int64_t K, const void* imgs, int64_t Cout, float* out,
+                        hipStream_t st);
+bool wgrad_batched_bf16x6_ok(int64_t rows, int64_t batches, int64_t Cout, int64_t Cin);
+size_t wgrad_batched_bf16x6_slab_bytes(int64_t rows, int batches, int64_t Cout, int64_t Cin);
+int wgrad_batched_bf16x6(const float* Z, const float* V, float* dU, float* slab, int64_t rows, int batches, int64_t Cout, int64_t Cin,
+                         hipStream_t st);
 
 namespace wino {
 
@@ -1068,26 +1077,29 @@ static void launch_dw_m(const float* dU, float* dw, int64_t Cout, int64_t Cin, h
 struct WinoWgradLayout {
     size_t tab, V, Z, dU, slab, total;
 };
-WinoWgradLayout wino_wgrad_layout(const WinoGeom& g, int64_t Cin, int64_t Cout, bool with_v) {
+WinoWgradLayout wino_wgrad_layout(const WinoGeom& g, int64_t Cin, int64_t Cout, bool with_v, bool x6 = false) {
     WinoWgradLayout l;
     size_t o = 0;
     l.tab = o; o += (size_t)g.Tp * sizeof(int4);
     l.V = o; o += with_v ? (size_t)products(g.m) * g.Tp * Cin * sizeof(float) : 0;        // (not when the forward's V was kept)
     l.Z = o; o += (size_t)products(g.m) * g.Tp * Cout * sizeof(float);
     l.dU = o; o += (size_t)products(g.m) * Cout * Cin * sizeof(float);
-    l.slab = o; o += wgrad_batched_slab_bytes(g.Tp, products(g.m), Cout, Cin);
+    l.slab = o; o += x6 ? wgrad_batched_bf16x6_slab_bytes(g.Tp, products(g.m), Cout, Cin)          // (the bf16x6 family's own split-K plan)
+                        : wgrad_batched_slab_bytes(g.Tp, products(g.m), Cout, Cin);
     l.total = o + 64;
     return l;
 }
 
 struct WinoLayout {
-    size_t tab, U, V, M, total;
+    size_t tab, U, img, V, M, total;
 };
-WinoLayout wino_layout(const WinoGeom& g, int64_t Cin, int64_t Cout) {
+// x6: + the three-plane weight images of U (one per product, consecutive), which the bf16x6 GEMM reads instead of U
+WinoLayout wino_layout(const WinoGeom& g, int64_t Cin, int64_t Cout, bool x6 = false) {
     WinoLayout l;
     size_t o = 0;
     l.tab = o; o += (size_t)g.Tp * sizeof(int4);
     l.U = o; o += (size_t)products(g.m) * Cout * Cin * sizeof(float);
+    l.img = o; o += x6 ? (size_t)products(g.m) * diga_split_bf16x6_image_bytes(Cout, 1, Cin) : 0;
     l.V = o; o += (size_t)products(g.m) * g.Tp * Cin * sizeof(float);
     l.M = o; o += (size_t)products(g.m) * g.Tp * Cout * sizeof(float);
     l.total = o + 64;
@@ -1109,7 +1121,11 @@ static int winograd_impl(const float* in, const float* wgt, const float* bias, f
                          size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld,
                          int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile, int flip, const diga_bwd_epilogue_t* epi, int prof_tag,
                          void* stream, float* v_keep = nullptr, float* stats = nullptr,
-                         const void* tile_table = nullptr, int reflect = 0, const diga_infer_epilogue_t* inf = nullptr) {
+                         const void* tile_table = nullptr, int reflect = 0, const diga_infer_epilogue_t* inf = nullptr,
+                         bool x6 = false) {
+    // x6 (diga_conv2d_winograd_bf16x6): the products on the bf16x6 GEMM; tile table, transforms, v_keep, statistics and the backward
+    // epilogue as below.  Not with the inference epilogue or reflection padding (those stay exact fp32).
+    DIGA_REQUIRE(!x6 || (!inf && !reflect), DIGA_EINVAL, "conv2d_winograd_bf16x6: no inference epilogue / reflection padding");
     DIGA_REQUIRE(!inf || ((tile == 4 || tile == 6) && !flip && !epi && !stats && !reflect), DIGA_EINVAL,
                  "conv2d_winograd_infer: the inference epilogue comes with the plain forward of 4x4 / 6x6 tiles");
     DIGA_REQUIRE(!reflect || (tile != 2 && !flip && !epi && dilation < H && dilation < W), DIGA_EINVAL,
@@ -1124,8 +1140,10 @@ static int winograd_impl(const float* in, const float* wgt, const float* bias, f
     DIGA_REQUIRE(N * H * W < (1ll << 31), DIGA_EINVAL, "conv2d_winograd: too many pixels");
     const WinoGeom g = make_wino(N, H, W, dilation, tile);
     const int P = products(tile);
-    DIGA_REQUIRE(P * g.Tp / 256 < 32768, DIGA_EINVAL, "conv2d_winograd: too many tiles for one launch");
-    const WinoLayout l = wino_layout(g, Cin, Cout);
+    DIGA_REQUIRE(x6 || P * g.Tp / 256 < 32768, DIGA_EINVAL, "conv2d_winograd: too many tiles for one launch");
+    DIGA_REQUIRE(!x6 || gemm_batched_bf16x6_ok(g.Tp, P, Cin, Cout), DIGA_EINVAL,
+                 "conv2d_winograd_bf16x6: products * padded tiles and the GEMM's tile count must stay below 2^31");
+    const WinoLayout l = wino_layout(g, Cin, Cout, x6);
     DIGA_REQUIRE(workspace_bytes >= l.total, DIGA_EWORKSPACE, "conv2d_winograd: workspace too small (%zu < %zu)", workspace_bytes, l.total);
     DIGA_REQUIRE(!stats || (epi == nullptr && tile != 2 && aligned16(stats)), DIGA_EINVAL,
                  "conv2d_winograd: statistics come with the forward output transform of 4x4 / 6x6 tiles (16-byte aligned buffer)");
@@ -1148,7 +1166,14 @@ static int winograd_impl(const float* in, const float* wgt, const float* bias, f
         hipLaunchKernelGGL(wino_weight_kernel, dim3((unsigned)ceil_div(Cout * (Cin / 4), 256)), dim3(256), 0, st, wgt, U, (int)Cout, (int)Cin,
                            flip);
     launch_input(tile, in, in_ld, tab, V, g.Tp, Cin, H, W, dilation, st, reflect);
-    int rc = gemm_batched_f32_dma(V, g.Tp, P, Cin, U, Cout, Mb, st, g.T);       // (rows T .. Tp of every product are the zero rows of the padding tiles)
+    int rc;
+    if (x6) {
+        void* imgs = ws + l.img;
+        split_image3_batched(U, imgs, P, Cout, Cin, st);
+        rc = gemm_batched_bf16x6(V, g.Tp, P, Cin, imgs, Cout, Mb, st);
+    } else {
+        rc = gemm_batched_f32_dma(V, g.Tp, P, Cin, U, Cout, Mb, st, g.T);   // (rows T .. Tp of every product are the zero rows of the padding tiles)
+    }
     if (rc) return rc;
     if (epi == nullptr && stats != nullptr) {
         if (tile == 6) launch_output_stats_m<6>(Mb, tab, bias, out, out_ld, g, Cout, stats, st);
@@ -1177,7 +1202,7 @@ static int winograd_impl(const float* in, const float* wgt, const float* bias, f
             hipLaunchKernelGGL(wino_output_epi_kernel, dim3((unsigned)G, (unsigned)ceil_div(Cout, 256)), dim3(256), 0, st, Mb, tab, out,
                                out_ld, g.T, g.Tp, (int)Cout, (int)H, (int)W, (int)dilation, tpb, ep);
     }
-    return launch_status("diga_conv2d_winograd_f32");
+    return launch_status(x6 ? "diga_conv2d_winograd_bf16x6" : "diga_conv2d_winograd_f32");
 }
 
 extern "C" size_t diga_conv2d_winograd_tile_table_bytes(int64_t N, int64_t H, int64_t W, int64_t dilation, int64_t tile) {
@@ -1278,7 +1303,8 @@ extern "C" size_t diga_conv2d_wgrad_winograd_workspace_bytes(int64_t N, int64_t 
 
 static int wgrad_winograd_impl(const float* dy, const float* x, const float* v_kept, float* dw, void* workspace,
                                size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t x_ld,
-                               int64_t Cout, int64_t dy_ld, int64_t dilation, int64_t tile, const void* tile_table, void* stream) {
+                               int64_t Cout, int64_t dy_ld, int64_t dilation, int64_t tile, const void* tile_table, void* stream,
+                               bool x6 = false) {
     DIGA_REQUIRE(!tile_table || aligned16(tile_table), DIGA_EALIGN, "conv2d_wgrad_winograd: tile_table must be 16-byte aligned");
     DIGA_REQUIRE(dy && (x || v_kept) && dw && workspace, DIGA_EINVAL, "conv2d_wgrad_winograd: null pointer");
     DIGA_REQUIRE(!v_kept || aligned16(v_kept), DIGA_EALIGN, "conv2d_wgrad_winograd: v_kept must be 16-byte aligned");
@@ -1289,7 +1315,9 @@ static int wgrad_winograd_impl(const float* dy, const float* x, const float* v_k
     DIGA_REQUIRE(aligned16(dy) && (!x || aligned16(x)) && aligned16(dw) && aligned16(workspace), DIGA_EALIGN,
                  "conv2d_wgrad_winograd: pointers must be 16-byte aligned");
     const WinoGeom g = make_wino(N, H, W, dilation, tile);
-    const WinoWgradLayout l = wino_wgrad_layout(g, Cin, Cout, v_kept == nullptr);
+    DIGA_REQUIRE(!x6 || wgrad_batched_bf16x6_ok(g.Tp, products(tile), Cout, Cin), DIGA_EINVAL,
+                 "conv2d_wgrad_winograd_bf16x6: padded tiles and the GEMM's block count must stay below 2^31");
+    const WinoWgradLayout l = wino_wgrad_layout(g, Cin, Cout, v_kept == nullptr, x6);
     DIGA_REQUIRE(workspace_bytes >= l.total, DIGA_EWORKSPACE, "conv2d_wgrad_winograd: workspace too small (%zu < %zu)", workspace_bytes,
                  l.total);
     char* ws = static_cast<char*>(workspace);
@@ -1309,13 +1337,14 @@ static int wgrad_winograd_impl(const float* dy, const float* x, const float* v_k
     else
         hipLaunchKernelGGL(wino_dy_kernel, dim3((unsigned)ceil_div(g.Tp * (Cout / 4), 256)), dim3(256), 0, st, dy, dy_ld, tab, Z, g.Tp,
                            (int)Cout, (int)H, (int)W, (int)dilation);
-    int rc = wgrad_batched_f32_dma(Z, V, dU, slab, g.Tp, products(tile), Cout, Cin, st);
+    int rc = x6 ? wgrad_batched_bf16x6(Z, V, dU, slab, g.Tp, products(tile), Cout, Cin, st)
+                : wgrad_batched_f32_dma(Z, V, dU, slab, g.Tp, products(tile), Cout, Cin, st);
     if (rc) return rc;
     if (tile == 6) launch_dw_m<6>(dU, dw, Cout, Cin, st);
     else if (tile == 4) launch_dw_m<4>(dU, dw, Cout, Cin, st);
     else
         hipLaunchKernelGGL(wino_dw_kernel, dim3((unsigned)ceil_div(Cout * (Cin / 4), 256)), dim3(256), 0, st, dU, dw, (int)Cout, (int)Cin);
-    return launch_status("diga_conv2d_wgrad_winograd_f32");
+    return launch_status(x6 ? "diga_conv2d_wgrad_winograd_bf16x6" : "diga_conv2d_wgrad_winograd_f32");
 }
 
 extern "C" int diga_conv2d_wgrad_winograd_f32(const float* dy, const float* x, const float* v_kept, float* dw, void* workspace,
@@ -1324,4 +1353,57 @@ extern "C" int diga_conv2d_wgrad_winograd_f32(const float* dy, const float* x, c
                                               void* stream) {
     return wgrad_winograd_impl(dy, x, v_kept, dw, workspace, workspace_bytes, N, H, W, Cin, x_ld, Cout, dy_ld, dilation, tile,
                                tile_table, stream);
+}
+
+// ---- the same layers with the Winograd-domain products on bf16x6 (conv_bf16x6.h; include/diga_hip.h)
+extern "C" size_t diga_conv2d_winograd_bf16x6_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                                                              int64_t dilation, int64_t tile) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % 32 != 0 || Cout <= 64 || Cout % 4 != 0 || dilation <= 0 || dilation >= 4096 ||
+        !tile_ok(tile) || N * H * W >= (1ll << 31))
+        return 0;
+    const WinoGeom g = make_wino(N, H, W, dilation, tile);
+    if (!gemm_batched_bf16x6_ok(g.Tp, products(tile), Cin, Cout)) return 0;
+    return wino_layout(g, Cin, Cout, true).total;
+}
+
+extern "C" int diga_conv2d_winograd_bf16x6(const float* in, const float* wgt, const float* bias, float* out, float* v_keep,
+                                           void* workspace, size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin,
+                                           int64_t in_ld, int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile, int flip,
+                                           float* stats_partial, const diga_bwd_epilogue_t* e, const void* tile_table, int prof_tag,
+                                           void* stream) {
+    DIGA_REQUIRE(!v_keep || aligned16(v_keep), DIGA_EALIGN, "conv2d_winograd_bf16x6: v_keep must be 16-byte aligned");
+    DIGA_REQUIRE(!v_keep || (!flip && !e), DIGA_EINVAL, "conv2d_winograd_bf16x6: v_keep comes with the forward (flip = 0, no epilogue)");
+    if (e != nullptr) {
+        DIGA_REQUIRE(!bias && !stats_partial, DIGA_EINVAL, "conv2d_winograd_bf16x6: a backward epilogue takes no bias and no statistics");
+        DIGA_REQUIRE(e->addend || e->mask_y || e->mask_bits || e->x, DIGA_EINVAL, "conv2d_winograd_bf16x6: empty epilogue descriptor");
+        DIGA_REQUIRE(!e->addend || (aligned16(e->addend) && e->addend_ld >= Cout && e->addend_ld % 4 == 0), DIGA_EINVAL, "conv2d_winograd_bf16x6: bad addend");
+        DIGA_REQUIRE(!e->mask_y || (aligned16(e->mask_y) && e->mask_ld >= Cout && e->mask_ld % 4 == 0), DIGA_EINVAL, "conv2d_winograd_bf16x6: bad mask_y");
+        DIGA_REQUIRE(!e->x || (aligned16(e->x) && e->x_ld >= Cout && e->x_ld % 4 == 0), DIGA_EINVAL, "conv2d_winograd_bf16x6: bad x");
+        DIGA_REQUIRE((e->mask_y != nullptr) + (e->relu_ab != nullptr) + (e->mask_bits != nullptr) <= 1, DIGA_EINVAL,
+                     "conv2d_winograd_bf16x6: give one of mask_y, mask_bits, relu_ab");
+        DIGA_REQUIRE(!e->mask_bits || e->mask_bits_ld * 8 >= Cout, DIGA_EINVAL, "conv2d_winograd_bf16x6: bad mask_bits");
+        DIGA_REQUIRE(!e->relu_ab || (e->x && aligned16(e->relu_ab)), DIGA_EINVAL, "conv2d_winograd_bf16x6: relu_ab needs x");
+        DIGA_REQUIRE(!e->partials || (e->x && e->mean && e->invstd && aligned16(e->mean) && aligned16(e->invstd)), DIGA_EINVAL,
+                     "conv2d_winograd_bf16x6: partials need x, mean and invstd");
+    }
+    return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, flip, e, prof_tag,
+                         stream, v_keep, stats_partial, tile_table, 0, nullptr, true);
+}
+
+extern "C" size_t diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                                                                    int64_t dilation, int64_t tile, int v_kept) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || dilation <= 0 || dilation >= 4096 || Cout % 256 != 0 || Cin % 128 != 0 ||
+        !tile_ok(tile) || N * H * W >= (1ll << 31))
+        return 0;
+    const WinoGeom g = make_wino(N, H, W, dilation, tile);
+    if (!wgrad_batched_bf16x6_ok(g.Tp, products(tile), Cout, Cin)) return 0;
+    return wino_wgrad_layout(g, Cin, Cout, v_kept == 0, true).total;
+}
+
+extern "C" int diga_conv2d_wgrad_winograd_bf16x6(const float* dy, const float* x, const float* v_kept, float* dw, void* workspace,
+                                                 size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t x_ld,
+                                                 int64_t Cout, int64_t dy_ld, int64_t dilation, int64_t tile, const void* tile_table,
+                                                 void* stream) {
+    return wgrad_winograd_impl(dy, x, v_kept, dw, workspace, workspace_bytes, N, H, W, Cin, x_ld, Cout, dy_ld, dilation, tile,
+                               tile_table, stream, true);
 }

@@ -109,6 +109,14 @@ def takes_twin_only_input(conv, pointwise_ok=False):
             and tuple(conv.stride) == (1, 1) and conv.groups == 1)
 
 
+def _wino_x6():
+    """_layer_math's sibling for the layers it sends to 0 in mode 2: True when a call that takes the fp32 Winograd path runs its
+    Winograd-domain GEMMs on bf16x6 instead (conv_math = 2 and config.x6_winograd, both read per call; the `_bf16x6` Winograd entry
+    points -- same tile table, transforms, keep-V, statistics and backward epilogue).  Path selection itself never reads this: only
+    the arithmetic of the products changes, and a kept V is fp32 either way, so forward and backward may differ."""
+    return _lib.get_conv_math() == 2 and config.active().x6_winograd
+
+
 INLINE_WGRAD = "inline"       # `uses` of a functional _Conv2dFn call whose weight is a non-leaf tensor (see backward)
 _WINO_CACHE = {}
 # bench.py sets this to a dict to learn what the convolutions of a step multiply: name -> [FLOPs of the direct
@@ -118,7 +126,7 @@ flop_log = None
 
 # a test or tool sets this to a dict to learn which kernels ran: (pass, arithmetic) -> launches, pass in "fwd" / "dgrad" / "wgrad",
 # arithmetic in "f32" / "bf16x3" / "bf16x6" / "bf16x6/ls" (bf16x6 with the operands split by the loader waves, config.x6_split = "loader") /
-# "winograd"; "f32+bn" / "winograd+bn": a forward with the eval-mode BatchNorm behind it
+# "winograd" / "winograd/x6" (the Winograd path with its products on bf16x6, config.x6_winograd); "f32+bn" / "winograd+bn": a forward with the eval-mode BatchNorm behind it
 # folded into its epilogue (config.fold_eval_bn)
 path_log = None
 
@@ -435,10 +443,25 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
         if inf is not None and tile < 4:
             raise RuntimeError("DigaConv2d: the inference epilogue comes with Winograd tiles of 4x4 / 6x6 (winograd_max_tile = 2)")
         _log_flops(name, direct, direct * ratio)
-        _log_path(tag, "winograd+bn" if inf is not None else "winograd")
-        nbytes = _lib.lib.diga_conv2d_winograd_workspace_bytes(n, hi, wi, cin, k, d, tile)
+        x6w = inf is None and _wino_x6()              # (the inference epilogue stays exact fp32)
+        _log_path(tag, "winograd+bn" if inf is not None else "winograd/x6" if x6w else "winograd")
+        if x6w:
+            nbytes = _lib.lib.diga_conv2d_winograd_bf16x6_workspace_bytes(n, hi, wi, cin, k, d, tile)
+        else:
+            nbytes = _lib.lib.diga_conv2d_winograd_workspace_bytes(n, hi, wi, cin, k, d, tile)
         ws = _lib.workspace(nbytes, x.device, "winograd")
         tab = _tile_table(n, hi, wi, d, tile, x.device)
+        if x6w:
+            # one entry point for the plain forward / backward-data, the forward with statistics, the forward that keeps V and
+            # backward-data with the epilogue
+            vk = None
+            if epi is None and keep_v is not None and doff[0] > 0:
+                vk = keep_v[0] = _alloc_keep_v(_lib.lib.diga_conv2d_winograd_v_floats(n, hi, wi, cin, d, tile), x.device)
+            _lib.call("diga_conv2d_winograd_bf16x6", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out),
+                      _lib.ptr(vk), _lib.ptr(ws), ws.numel(), n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile,
+                      1 if doff[0] < 0 else 0, _lib.ptr(stats), ctypes.byref(epi) if epi is not None else None,
+                      _lib.ptr(tab), tag, _lib.stream())
+            return None
         if inf is not None:
             _lib.call("diga_conv2d_winograd_f32_infer", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
                       n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile, ctypes.byref(inf), _lib.ptr(tab), tag, _lib.stream())
@@ -848,12 +871,15 @@ class _Conv2dFn(torch.autograd.Function):
                 if (lm == 0 and kp % 256 == 0 and cp % 128 == 0 and gyp.stride(2) % 4 == 0
                         and _winograd_ok(n, hi, wi, cp, kp, r, s, stride, (-padding[0], -padding[1]), dilation, ho, wo)):
                     tile, ratio = _wino_plan(hi, wi, dilation[0])
-                    _log_path("wgrad", "winograd")
+                    x6w = _wino_x6()                # (read per call: the kept V is fp32 whichever arithmetic the forward ran)
+                    sfx = "bf16x6" if x6w else "f32"
+                    _log_path("wgrad", "winograd/x6" if x6w else "winograd")
                     _log_flops("conv_bwd_weight", 2.0 * n * ho * wo * kp * 9 * cp, 2.0 * n * ho * wo * kp * 9 * cp * ratio)
-                    nb = _lib.lib.diga_conv2d_wgrad_winograd_workspace_bytes(n, hi, wi, cp, kp, dilation[0], tile, 1 if wino_v is not None else 0)
+                    nb = getattr(_lib.lib, "diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes" if x6w else "diga_conv2d_wgrad_winograd_workspace_bytes")(
+                        n, hi, wi, cp, kp, dilation[0], tile, 1 if wino_v is not None else 0)
                     wsw = _lib.workspace(nb, w.device, "winograd_wgrad")
                     tab = _tile_table(n, hi, wi, dilation[0], tile, w.device)
-                    _lib.call("diga_conv2d_wgrad_winograd_f32", _lib.ptr(gyp), _lib.ptr(xn), _lib.ptr(wino_v), _lib.ptr(dwp), _lib.ptr(wsw),
+                    _lib.call("diga_conv2d_wgrad_winograd_" + sfx, _lib.ptr(gyp), _lib.ptr(xn), _lib.ptr(wino_v), _lib.ptr(dwp), _lib.ptr(wsw),
                               wsw.numel(), n, hi, wi, cp, xn.stride(2), kp, gyp.stride(2), dilation[0], tile, _lib.ptr(tab), _lib.stream())
                     if not alias:
                         dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))

@@ -524,6 +524,48 @@ int diga_conv2d_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* 
                                    int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0,
                                    int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream);
 
+/* bf16x6 for the Winograd-domain GEMMs of the stride-1 3x3 layers (opt-in: StepConfig.x6_winograd under conv_math = 2).  The
+ * Winograd transforms stay fp32; the (tile + 2)^2 products per layer run on the loader-split bf16x6 kernels in ONE batched launch.
+ *
+ * diga_gemm_batched_bf16x6_f32in: out_b [rows x Cout] = A_b [rows x K] * W_b^T for b < batches.  A is [batches * rows_per_batch][K]
+ *   fp32 (dense, read in place), out [batches * rows_per_batch][Cout]; wgt_imgs holds `batches` consecutive images of
+ *   diga_split_bf16x6_image_bytes(Cout, 1, K) bytes, image b = diga_split_bf16x6_image(W_b [Cout][K], ..., Cout, 1, K).  A 256-row tile
+ *   runs the K-steps of diga_conv2d_nhwc_bf16x6_f32in in the same order: each batch's block is bit-identical to that entry point on
+ *   the batch alone.  rows_per_batch % 256 == 0, K % 32 == 0, Cout % 4 == 0 and Cout > 64, batches < 65536 (else DIGA_EINVAL);
+ *   16-byte aligned pointers (else DIGA_EALIGN).  Index limits of the kernel: tile and row indices are 32-bit, so
+ *   batches * rows_per_batch < 2^31 and (batches * rows_per_batch / 256) * ceil(Cout / 128) < 2^31 (else DIGA_EINVAL); element
+ *   offsets are 64-bit.
+ * diga_wgrad_batched_bf16x6_f32in: dU_b [Cout x Cin] = Z_b^T V_b (contraction over the rows).  Z [batches][rows][Cout],
+ *   V [batches][rows][Cin] fp32 dense, dU [Cout][batches][Cin].  rows % 32 == 0, Cout % 256 == 0, Cin % 128 == 0, batches < 65536,
+ *   rows < 2^31 and (Cout / 256) * (Cin / 128) * batches * splits < 2^31 blocks (else DIGA_EINVAL).  Split over row ranges of at
+ *   least 8 K-steps (about two rounds of blocks), partial sums in `workspace` (diga_wgrad_batched_bf16x6_workspace_bytes; 0 for a
+ *   rejected shape) added in fixed order: bit-reproducible.
+ * diga_conv2d_winograd_bf16x6: diga_conv2d_winograd_f32 / _keep / _epi in one entry point with the products on the first GEMM:
+ *   v_keep (nullable, forward only) as in `_keep`, stats_partial (nullable, tile 4 / 6, forward) as in `_f32`, epi (nullable) as in
+ *   `_epi`; same tile table, transforms, shape rules (Cin % 32 == 0, Cout % 4 == 0 and > 64, leading dimensions % 4 == 0, tiles 2 / 4
+ *   / 6) and the GEMM's index limits above on (tile + 2)^2 batches of the padded tile count.  Workspace
+ *   (diga_conv2d_winograd_bf16x6_workspace_bytes; 0 for a rejected shape) = the fp32 form's + the weight images.  No inference epilogue
+ *   and no reflection padding: those forms stay exact fp32.
+ * diga_conv2d_wgrad_winograd_bf16x6: diga_conv2d_wgrad_winograd_f32 (same arguments, Cout % 256 == 0, Cin % 128 == 0) with the
+ *   products on the second GEMM; workspace diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes. */
+int diga_gemm_batched_bf16x6_f32in(const float* A, int64_t rows_per_batch, int64_t batches, int64_t K, const void* wgt_imgs,
+                                   int64_t Cout, float* out, void* stream);
+size_t diga_wgrad_batched_bf16x6_workspace_bytes(int64_t rows, int64_t batches, int64_t Cout, int64_t Cin);
+int diga_wgrad_batched_bf16x6_f32in(const float* Z, const float* V, float* dU, void* workspace, size_t workspace_bytes, int64_t rows,
+                                    int64_t batches, int64_t Cout, int64_t Cin, void* stream);
+size_t diga_conv2d_winograd_bf16x6_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t dilation,
+                                                   int64_t tile);
+int diga_conv2d_winograd_bf16x6(const float* in, const float* wgt, const float* bias, float* out, float* v_keep /* nullable */,
+                                void* workspace, size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld,
+                                int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile, int flip,
+                                float* stats_partial /* nullable */, const diga_bwd_epilogue_t* epi /* nullable */,
+                                const void* tile_table, int prof_tag, void* stream);
+size_t diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t dilation,
+                                                         int64_t tile, int v_kept);
+int diga_conv2d_wgrad_winograd_bf16x6(const float* dy, const float* x, const float* v_kept, float* dw, void* workspace,
+                                      size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t x_ld, int64_t Cout,
+                                      int64_t dy_ld, int64_t dilation, int64_t tile, const void* tile_table, void* stream);
+
 /* Stem (7x7/2 on the 3-channel NCHW image, G5/model/seg_model_noaux.py:221): out[n,ho,wo][(r*S+s)*C + c] =
  * x[n,c,ho*stride-pad+r,wo*stride-pad+s] (zero outside / beyond R*S*C up to Kpad), after which the conv is a
  * 1x1 conv with Cin = Kpad on the kernels above. */

@@ -3,12 +3,15 @@
 geometries of ResNet-101 DeepLabV2 at the C2 size (16 images of 768x768 -> 193x193 / 97x97 maps).
 
     python tools/bench_conv.py [--images 16] [--reps 5] [--math f32|bf16x3|bf16x6] [--x6-split pass|loader] [--pointwise-only]
+                                 [--x6-winograd] [--winograd-only]
 Prints one line per (shape, pass): ms, TFLOP/s, fraction of the 157.3 TFLOP/s fp32 MFMA peak, and the
 share of a training step's conv time that shape accounts for (count x time).
 --math bf16x6: the pointwise layers run on bf16x6, the rest on the exact-fp32 paths; the operand split passes are part of the
 figures (forward: inside the timed call; backward: the elementwise launches -- triplet of dy, weight images -- are added to dgrad).
 --x6-split loader: the bf16x6 GEMMs split their fp32 operands in the loader waves (config.x6_split): no triplet passes, the weight
 images remain.
+--x6-winograd (with --math bf16x6): the Winograd-domain GEMMs of the stride-1 3x3 layers on bf16x6 too (config.x6_winograd); the batched
+weight-image split is inside the timed calls.  --winograd-only: time the rows that take the Winograd path only.
 """
 import argparse
 import os
@@ -59,16 +62,21 @@ def main():
     ap.add_argument("--math", default="f32", choices=["f32", "bf16x3", "bf16x6"])
     ap.add_argument("--pointwise-only", action="store_true", help="time the 1x1 rows only (what --math bf16x6 changes)")
     ap.add_argument("--x6-split", default="pass", choices=["pass", "loader"], help="bf16x6 operand form (config.x6_split)")
+    ap.add_argument("--x6-winograd", action="store_true", help="bf16x6 for the Winograd-domain GEMMs as well (config.x6_winograd)")
+    ap.add_argument("--winograd-only", action="store_true", help="time the stride-1 3x3 rows of >= 128 channels only (what --x6-winograd changes)")
     a = ap.parse_args()
     _lib.set_conv_math(a.math)
     config.active().x6_split = a.x6_split
+    config.active().x6_winograd = a.x6_winograd
     global PEAK
     PEAK = {"bf16x3": 2500.0 / 3.0, "bf16x6": 2500.0 / 6.0}.get(a.math, 157.3)
     dev = "cuda"
     rows, tot = [], {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}
     pw = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the pointwise (1x1) rows alone
+    wn = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the rows on the Winograd path (aspp.d24 stays direct: its ratio)
     for name, count, cin, cout, k, stride, dil, hw in SHAPES:
-        if (a.only and a.only not in name) or (a.pointwise_only and k != 1):
+        wino_row = k == 3 and stride == 1 and cin >= 128 and cout >= 128 and name != "aspp.d24"
+        if (a.only and a.only not in name) or (a.pointwise_only and k != 1) or (a.winograd_only and not wino_row):
             continue
         pad = dil * (k - 1) // 2
         m = DigaConv2d(cin, cout, k, stride=stride, padding=pad, dilation=dil, bias=False).to(dev)
@@ -114,6 +122,10 @@ def main():
             pw["fwd"] += count * t_f
             pw["dgrad"] += count * t_d
             pw["wgrad"] += count * t_w
+        if wino_row:
+            wn["fwd"] += count * t_f
+            wn["dgrad"] += count * t_d
+            wn["wgrad"] += count * t_w
         del m, x, y, gy
         torch.cuda.empty_cache()
     print(f"{'shape':18s} {'cnt':>3s} {'GFLOP':>8s} | {'fwd ms':>8s} {'TF/s':>6s} {'frac':>5s} | {'dgrad ms':>8s} {'TF/s':>6s} | "
@@ -125,6 +137,7 @@ def main():
               f"{100 * count * t_w / max(tot['wgrad'], 1e-9):.1f}%")
     print(f"sum over one forward: fwd {tot['fwd']:.1f} ms, dgrad {tot['dgrad']:.1f} ms, wgrad {tot['wgrad']:.1f} ms")
     print(f"pointwise rows, count-weighted ({a.math}{'/' + a.x6_split if a.math == 'bf16x6' else ''}): fwd {pw['fwd']:.2f} ms, dgrad {pw['dgrad']:.2f} ms, wgrad {pw['wgrad']:.2f} ms")
+    print(f"winograd rows, count-weighted ({a.math}{'/x6-winograd' if a.x6_winograd else ''}): fwd {wn['fwd']:.2f} ms, dgrad {wn['dgrad']:.2f} ms, wgrad {wn['wgrad']:.2f} ms")
 
 
 if __name__ == "__main__":
