@@ -7,8 +7,10 @@ activations travel NHWC; tensors handed to / returned from the module are NCHW-s
 memory (torch's channels_last format), so neighbouring torch ops see ordinary 4-D tensors.
 Channel counts that are not multiples of 32 (the 3-channel image, the 19-class head) are zero-padded.
 """
+import ctypes
 import os
 import sys
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -232,18 +234,6 @@ def _tile_table(n, hi, wi, d, tile, device):
     return tab
 
 
-def winograd_stats_plan(n, hi, wi, cin_padded, k, r, s, stride, padding, dilation, ho, wo):
-    """(floats, records) of the statistics buffer a forward DigaConv2d on the fp32 Winograd path with 4x4 / 6x6 tiles fills for the
-    BatchNorm behind it (diga_conv2d_winograd_stats_floats / _records), or None when the layer is not on that path."""
-    if _layer_math(r, s, cin_padded) != 0 or not _winograd_ok(n, hi, wi, cin_padded, k, r, s, stride, (-padding[0], -padding[1]), tuple(dilation), ho, wo):
-        return None
-    tile = _wino_plan(hi, wi, dilation[0])[0]
-    if tile < 4 or k % 4 != 0:
-        return None
-    return (_lib.lib.diga_conv2d_winograd_stats_floats(n, hi, wi, k, dilation[0], tile),
-            _lib.lib.diga_conv2d_winograd_stats_records(n, hi, wi, k, dilation[0], tile))
-
-
 def _wino_ratio(hi, wi, d):
     return _wino_plan(hi, wi, d)[1]
 
@@ -265,16 +255,118 @@ def _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo):
     return ratio <= cfg.winograd_ratio and n * hi * wi * ratio * 9.0 / 256.0 < 32000
 
 
+class _Path(NamedTuple):
+    """Which kernel ONE convolution call runs on.  _plan (forward / backward-data) and _wgrad_plan (weight gradient) decide it, once
+    per call, from the call's geometry, the features it wants and the active configuration; everything else -- the launch, the
+    statistics buffer DigaConv2d allocates, infer_kernel, winograd_stats_plan, what a forward saves for its backward -- reads it."""
+    family: str                # "x6ls" (bf16x6, operands split by the loader waves) / "x6" (bf16x6 on triplets) / "twin" / "bf16x3" /
+    #                            "winograd" / "winograd_reflect" (reflection padding folded into the input transform) / "f32"
+    variant: str               # "" / "epi" (backward-data epilogue) / "opts" / "infer" / "keep" (Winograd forward that keeps V)
+    math: int                  # the layer's arithmetic (_layer_math): the `math` argument the library is given
+    arith: str                 # the arithmetic under which path_log counts the call
+    tile: int = 0              # Winograd: output-tile edge and the share of the direct convolution's multiplications (_wino_plan)
+    ratio: float = 1.0
+    x6w: bool = False          # Winograd: the Winograd-domain products run on bf16x6 (_wino_x6)
+    flops: bool = True         # counted in flop_log (all but the bf16x3 forward / backward-data kernels, the twin weight gradient, the stem's)
+
+
+def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, stats=None, epi=False, opts=None, infer=False,
+          shared=False, must_twin=False, x6_ok=True, keep=False):
+    """The _Path of a forward (tag = _TAG_FWD, doff = dilation) or backward-data (_TAG_BWD_DATA, doff = -dilation) call on an
+    [n,hi,wi,cin] input (cin padded) with tap offsets off0 + i * doff, or a RuntimeError where the library has no kernel for the
+    combination.  Pure: no tensor, no device; the switches are read from the active configuration now, nothing is remembered.
+    stats: None / "chunks" (equal-sized partial sums for the BatchNorm behind the conv) / "records" (the Winograd output transform's);
+    epi / infer: the call carries a backward-data / inference epilogue; opts: (reflect_pad, upsample_shift, activation) or None;
+    shared: a twin / triplet box comes with the input; must_twin: the input holds split-twin bytes; x6_ok=False keeps a pointwise
+    call off bf16x6 (the stem); keep: the caller wants the weight gradient, so a Winograd forward with Cout % 256 == 0 and
+    Cin % 128 == 0 keeps its transformed input for it (config.winograd_keep_v)."""
+    copt = opts is not None and any(opts)
+    if copt and (stats is not None or epi):
+        raise RuntimeError("DigaConv2d: folded padding / upsampling / activation cannot be combined with BN statistics or a backward epilogue")
+    math = _layer_math(r, s, cin, x6_ok and not copt)
+    if infer and (math != 0 or copt or stats is not None or epi or tag != _TAG_FWD or k % 4 != 0):
+        raise RuntimeError("DigaConv2d: no kernel with the inference epilogue for this call (exact-fp32 forward without statistics, "
+                           "Cout % 4 == 0; check infer_kernel / folds_eval_bn first)")
+    variant = "infer" if infer else "epi" if epi else "opts" if copt else ""
+    if math == 2:
+        # bf16x6: the weights as a pre-split image; the activations read as fp32 and split by the loader waves, or pre-split into
+        # three bf16 planes and copied global -> LDS by LDS-DMA (csrc/conv_bf16x6.h)
+        return _Path("x6ls", variant, 2, "bf16x6/ls") if _x6_loader() else _Path("x6", variant, 2, "bf16x6")
+    if math == 1 and _use_twin(cin, k, r * s, shared) and n * hi * wi * cin * 4 < (1 << 40):
+        # split-bf16 arithmetic without register staging: both operands pre-split, copied global -> LDS by LDS-DMA
+        return _Path("twin", variant, 1, "bf16x3", flops=False)
+    if must_twin:
+        raise RuntimeError("DigaConv2d: the input holds split-twin bytes but the twin kernel is not selected "
+                           "(conv math or config.conv_twin changed since the producer ran)")
+    if math == 1:
+        # split-bf16 arithmetic: the weights are split once per call (two bf16 arrays), the activations inside the kernel
+        return _Path("bf16x3", variant, 1, "bf16x3", flops=False)
+    if copt:
+        # reflection padding folded into the Winograd input transform (the translator's 3x3 ResBlock convs; round 5)
+        if (opts[0] and not opts[1] and not opts[2] and 0 < doff[0] < min(hi, wi)
+                and _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo)):
+            tile, ratio = _wino_plan(hi, wi, doff[0])
+            if tile >= 4:
+                return _Path("winograd_reflect", "opts", 0, "winograd", tile, ratio)
+    elif stats != "chunks" and _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo):
+        tile, ratio = _wino_plan(hi, wi, abs(doff[0]))
+        if stats is not None and (tile < 4 or epi or doff[0] < 0):
+            raise RuntimeError("DigaConv2d: Winograd statistics come with the forward output transform of 4x4 / 6x6 tiles")
+        if infer and tile < 4:
+            raise RuntimeError("DigaConv2d: the inference epilogue comes with Winograd tiles of 4x4 / 6x6 (winograd_max_tile = 2)")
+        x6w = not infer and _wino_x6()                 # (the inference epilogue stays exact fp32)
+        if keep and variant == "" and doff[0] > 0 and k % 256 == 0 and cin % 128 == 0 and config.active().winograd_keep_v:
+            variant = "keep"
+        return _Path("winograd", variant, 0, "winograd+bn" if infer else "winograd/x6" if x6w else "winograd", tile, ratio, x6w)
+    return _Path("f32", variant, 0, "f32+bn" if infer else "f32")
+
+
+def _wgrad_plan(n, hi, wi, cp, kp, r, s, stride, padding, dilation, ho, wo, x_twin=False, stem=False):
+    """_plan's sibling for the weight gradient of a layer with (padded) cp input and kp output channels.  x_twin: the forward left
+    the split twin of its input and the layer may use it (bf16x3); stem: the im2col GEMM of _StemConvFn, which stays off bf16x6."""
+    math = _layer_math(r, s, cp, not stem)
+    if math == 2:
+        return _Path("x6ls", "", 2, "bf16x6/ls") if _x6_loader() else _Path("x6", "", 2, "bf16x6")
+    if math == 1 and x_twin:
+        return _Path("twin", "", 1, "bf16x3", flops=False)
+    if (math == 0 and kp % 256 == 0 and cp % 128 == 0
+            and _winograd_ok(n, hi, wi, cp, kp, r, s, stride, (-padding[0], -padding[1]), dilation, ho, wo)):
+        tile, ratio = _wino_plan(hi, wi, dilation[0])
+        x6w = _wino_x6()                               # (read per call: a kept V is fp32 whichever arithmetic the forward ran)
+        return _Path("winograd", "", 0, "winograd/x6" if x6w else "winograd", tile, ratio, x6w)
+    return _Path("f32", "", math, "bf16x3" if math == 1 else "f32", flops=not stem)
+
+
+def _stats_plan(n, hi, wi, cin, k, r, s, stride, padding, dilation, ho, wo, opts=None, x6_ok=True):
+    """(form, _Path): the statistics a forward with emit_bn_stats hands the BatchNorm behind it, from the kernel the call will run on --
+    "chunks" of equal size, or (round 5) the "records" of unequal size that the Winograd output transform of 4x4 / 6x6 tiles leaves
+    (diga_bn_fwd_records); None: F(2x2)-only runs and config.winograd_stats = False keep the BatchNorm's own statistics pass."""
+    path = _plan(n, hi, wi, cin, k, r, s, stride, (-padding[0], -padding[1]), dilation, ho, wo, opts=opts, x6_ok=x6_ok)
+    if path.family != "winograd":
+        return "chunks", path
+    return ("records" if config.active().winograd_stats and path.tile >= 4 and k % 4 == 0 else None), path
+
+
+def winograd_stats_plan(n, hi, wi, cin_padded, k, r, s, stride, padding, dilation, ho, wo):
+    """(floats, records) of the statistics buffer a forward DigaConv2d on the fp32 Winograd path with 4x4 / 6x6 tiles fills for the
+    BatchNorm behind it (diga_conv2d_winograd_stats_floats / _records), or None when the layer is not on that path."""
+    path = _plan(n, hi, wi, cin_padded, k, r, s, stride, (-padding[0], -padding[1]), tuple(dilation), ho, wo)
+    if path.family != "winograd" or path.tile < 4 or k % 4 != 0:
+        return None
+    return (_lib.lib.diga_conv2d_winograd_stats_floats(n, hi, wi, k, dilation[0], path.tile),
+            _lib.lib.diga_conv2d_winograd_stats_records(n, hi, wi, k, dilation[0], path.tile))
+
+
 def infer_kernel(n, hi, wi, cin, k, r, s, stride, padding, dilation, ho, wo, pointwise_ok=True):
     """The forward kernel family with the inference epilogue (diga_infer_epilogue_t) a layer would run on under the active
     configuration -- "f32+bn" (direct / LDS-DMA / persistent GEMM) or "winograd+bn" (4x4 / 6x6 tiles) -- or None where there is none:
     a layer whose arithmetic is not exact fp32 (conv_math 1; pointwise layers in mode 2), Cout % 4 != 0, Winograd capped at 2x2 tiles.
     cin: the padded input channel count."""
-    if k % 4 != 0 or _layer_math(r, s, cin, pointwise_ok) != 0:
+    try:
+        return _plan(n, hi, wi, cin, k, r, s, stride, (-padding[0], -padding[1]), tuple(dilation), ho, wo, infer=True,
+                     x6_ok=pointwise_ok).arith
+    except RuntimeError:                               # (the planner's refusal of an inference epilogue IS the answer)
         return None
-    if _winograd_ok(n, hi, wi, cin, k, r, s, stride, (-padding[0], -padding[1]), tuple(dilation), ho, wo):
-        return "winograd+bn" if _wino_plan(hi, wi, dilation[0])[0] >= 4 else None
-    return "f32+bn"
 
 
 def _infer_epilogue(infer, out):
@@ -300,8 +392,95 @@ def _infer_epilogue(infer, out):
     return e, (ab, rn)
 
 
+def _make_split(src, ld, rows, ch, triplet):
+    """The pre-split copy of a [rows][ch] fp32 matrix with row pitch ld that the LDS-DMA kernels read: its split twin (bf16 hi / lo
+    planes, 4 bytes per element) or, for bf16x6, its three-plane triplet (6 bytes)."""
+    out = torch.empty(rows * ch * (6 if triplet else 4), dtype=torch.uint8, device=src.device)
+    _lib.call("diga_make_triplet" if triplet else "diga_make_twin", _lib.ptr(src), ld, _lib.ptr(out), rows, ch, _lib.stream())
+    return out
+
+
+# (family, variant) -> entry point.  The implicit-GEMM families share one argument layout (_conv_launch) up to: the leading operand
+# pointers (_operands), an input pitch (the two families that read fp32 activations through the ordinary loads), a bias slot (all
+# but `_epi`) and the one trailing pointer (statistics, or the variant's struct).  The Winograd entry points have their own layout
+# (_winograd_launch); with the products on bf16x6 one entry point serves every variant.
+_ENTRY = {
+    ("x6ls", ""): "diga_conv2d_nhwc_bf16x6_f32in", ("x6ls", "epi"): "diga_conv2d_nhwc_bf16x6_f32in_epi",
+    ("x6", ""): "diga_conv2d_nhwc_bf16x6", ("x6", "epi"): "diga_conv2d_nhwc_bf16x6_epi",
+    ("twin", ""): "diga_conv2d_nhwc_twin", ("twin", "epi"): "diga_conv2d_nhwc_twin_epi", ("twin", "opts"): "diga_conv2d_nhwc_twin_opts",
+    ("bf16x3", ""): "diga_conv2d_nhwc_bf16x3", ("bf16x3", "epi"): "diga_conv2d_nhwc_bf16x3_epi",
+    ("bf16x3", "opts"): "diga_conv2d_nhwc_bf16x3_opts",
+    ("f32", ""): "diga_conv2d_nhwc_f32", ("f32", "epi"): "diga_conv2d_nhwc_f32_epi", ("f32", "opts"): "diga_conv2d_nhwc_f32_opts",
+    ("f32", "infer"): "diga_conv2d_nhwc_f32_infer",
+    ("winograd", ""): "diga_conv2d_winograd_f32", ("winograd", "epi"): "diga_conv2d_winograd_f32_epi",
+    ("winograd", "infer"): "diga_conv2d_winograd_f32_infer", ("winograd", "keep"): "diga_conv2d_winograd_f32_keep",
+    ("winograd_reflect", "opts"): "diga_conv2d_winograd_f32_opts",
+}
+_WINOGRAD_X6 = "diga_conv2d_winograd_bf16x6"
+
+
+def _operands(path, x, w_krsc, twin_box):
+    """The operands of an implicit-GEMM call in the form its family reads -> (the leading arguments up to the weights, the tensors
+    behind them, the twin / triplet of x to hand back).  The weight image / split lives until the launch returns."""
+    n, hi, wi, cin = x.shape
+    k, r, s, _ = w_krsc.shape
+    if path.family == "x6ls":
+        # loader form: the activations are read as fp32 in place (contiguous or a channel slice) -- no triplet is built, returned or
+        # looked for in the box
+        split, ld = None, _nhwc_ld(x)
+        if ld is None:
+            x, ld = x.contiguous(), cin
+        act = [_lib.ptr(x), ld]
+    elif path.family in ("x6", "twin"):
+        split = twin_box[0] if twin_box is not None else None
+        if split is None:
+            split = _make_split(x if x.is_contiguous() else x.contiguous(), cin, n * hi * wi, cin, path.family == "x6")
+            if twin_box is not None:
+                twin_box[0] = split
+        act = [_lib.ptr(split)]
+    if path.family in ("x6ls", "x6", "twin"):
+        size, fill = ((_lib.lib.diga_split_bf16_image_bytes, "diga_split_bf16_image") if path.family == "twin" else
+                      (_lib.lib.diga_split_bf16x6_image_bytes, "diga_split_bf16x6_image"))
+        img = torch.empty(size(k, r * s, cin), dtype=torch.uint8, device=x.device)
+        _lib.call(fill, _lib.ptr(w_krsc), _lib.ptr(img), k, r * s, cin, _lib.stream())
+        return act + [_lib.ptr(img)], (x, split, img), split
+    if path.family == "bf16x3":
+        nel = w_krsc.numel()
+        w_hi = torch.empty(nel, dtype=torch.int16, device=w_krsc.device)
+        w_lo = torch.empty(nel, dtype=torch.int16, device=w_krsc.device)
+        _lib.call("diga_split_bf16", _lib.ptr(w_krsc), _lib.ptr(w_hi), _lib.ptr(w_lo), nel, _lib.stream())
+        return [_lib.ptr(x), _lib.ptr(w_hi), _lib.ptr(w_lo)], (w_hi, w_lo), None
+    return [_lib.ptr(x), _lib.ptr(w_krsc)], (), None
+
+
+def _winograd_launch(path, x, w_krsc, bias, out, d, flip, tag, stats, struct, keep_v):
+    """The Winograd entry points: workspace, tile table and (variant "keep") the kept transform, then one call.  d: |dilation|;
+    flip: 1 for backward-data; keep_v: a one-element list -- the transformed input stays alive for this layer's weight gradient."""
+    n, hi, wi, cin = x.shape
+    k, tile = out.shape[3], path.tile
+    size = _lib.lib.diga_conv2d_winograd_bf16x6_workspace_bytes if path.x6w else _lib.lib.diga_conv2d_winograd_workspace_bytes
+    ws = _lib.workspace(size(n, hi, wi, cin, k, d, tile), x.device, "winograd")
+    tab = _tile_table(n, hi, wi, d, tile, x.device)
+    variant, vk = path.variant, None
+    if variant == "keep":
+        vk = keep_v[0] = _alloc_keep_v(_lib.lib.diga_conv2d_winograd_v_floats(n, hi, wi, cin, d, tile), x.device)
+        if vk is None:                                 # policy or memory said recompute
+            variant = ""
+    lead = [_lib.ptr(x), _lib.ptr(w_krsc)] + ([] if variant == "epi" and not path.x6w else [_lib.ptr(bias)]) + [_lib.ptr(out)]
+    shape = (_lib.ptr(ws), ws.numel(), n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile)
+    if path.x6w:
+        # one entry point for the plain forward / backward-data, the forward with statistics, the forward that keeps V and
+        # backward-data with the epilogue
+        _lib.call(_WINOGRAD_X6, *lead, _lib.ptr(vk), *shape, flip, _lib.ptr(stats), struct, _lib.ptr(tab), tag, _lib.stream())
+        return
+    if variant == "keep":
+        lead.append(_lib.ptr(vk))
+    _lib.call(_ENTRY[(path.family, variant)], *lead, *shape, *((flip,) if variant in ("", "epi") else ()),
+              struct if struct is not None else _lib.ptr(stats), _lib.ptr(tab), tag, _lib.stream())
+
+
 def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin_box=None, must_twin=False, epi=None,
-                 opts=None, keep_v=None, wino_stats=False, x6_ok=True, infer=None):
+                 opts=None, keep_v=None, x6_ok=True, infer=None, path=None):
     """x [N,Hi,Wi,Cin] (contiguous or a channel slice of a contiguous tensor), w_krsc [K,R,S,Cin],
     out [N,Ho,Wo,K] (same rule).  twin_box: a one-element list shared by the convs that read the very same x.
     (In bf16x6 mode the box holds the three-plane triplet of x instead.)  x6_ok=False keeps a pointwise call off bf16x6 (the stem).
@@ -309,200 +488,93 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
     + ReLU) in the epilogue (diga_infer_epilogue_t); a layer without such a kernel (infer_kernel is None) raises.
     epi: a _lib.BwdEpilogue (backward-data only, bias-free): the `_epi` entry points finish the gradient in the epilogue.
     opts: (reflect_pad, upsample_shift, activation) = a diga_conv_options_t handed to the `_opts` entry points -- x is then the SOURCE tensor of the
-    (virtually) upsampled / mirrored input."""
-    import ctypes
-
-    copt = None
-    if opts is not None and any(opts):
-        if stats is not None or epi is not None:
-            raise RuntimeError("DigaConv2d: folded padding / upsampling / activation cannot be combined with BN statistics or a backward epilogue")
-        copt = _lib.ConvOptions(int(opts[0]), int(opts[1]), int(opts[2]))
+    (virtually) upsampled / mirrored input.  path: the call's _Path where the caller has planned it already (_Conv2dFn.forward: statistics
+    records and keep_v come with it).
+    Returns the twin / triplet of x the call read (built here or taken from the box), None on the other families."""
     n, hi, wi, cin = x.shape
     _, ho, wo, k = out.shape
     _, r, s, _ = w_krsc.shape
-    math = _layer_math(r, s, cin, x6_ok and copt is None)
-    inf = keep_inf = None
-    if infer is not None:
-        if math != 0 or copt is not None or stats is not None or epi is not None or tag != _TAG_FWD or k % 4 != 0:
-            raise RuntimeError("DigaConv2d: no kernel with the inference epilogue for this call (exact-fp32 forward without statistics, "
-                               "Cout % 4 == 0; check infer_kernel / folds_eval_bn first)")
-        inf, keep_inf = _infer_epilogue(infer, out)
-    if math == 2 and _x6_loader():
-        # bf16x6, loader form: the weights as a pre-split image, the activations read as fp32 (in place: contiguous or a channel
-        # slice) and split by the loader waves -- no triplet is built, returned or looked for in the box
-        ld = _nhwc_ld(x)
-        if ld is None:
-            x = x.contiguous()
-            ld = cin
-        img = torch.empty(_lib.lib.diga_split_bf16x6_image_bytes(k, 1, cin), dtype=torch.uint8, device=x.device)
-        _lib.call("diga_split_bf16x6_image", _lib.ptr(w_krsc), _lib.ptr(img), k, 1, cin, _lib.stream())
-        _log_path(tag, "bf16x6/ls")
-        _log_flops("conv_bwd_data" if tag == _TAG_BWD_DATA else "conv_fwd", 2.0 * n * ho * wo * k * cin, 2.0 * n * ho * wo * k * cin)
-        if epi is not None:
-            _lib.call("diga_conv2d_nhwc_bf16x6_f32in_epi", _lib.ptr(x), ld, _lib.ptr(img), _lib.ptr(out), n, hi, wi, cin, ho, wo, k,
-                      out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], ctypes.byref(epi), tag,
-                      _lib.stream())
-            return None
-        _lib.call("diga_conv2d_nhwc_bf16x6_f32in", _lib.ptr(x), ld, _lib.ptr(img), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin, ho,
-                  wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], _lib.ptr(stats), tag,
-                  _lib.stream())
-        return None
-    if math == 2:
-        # bf16x6: both operands pre-split into three bf16 planes, copied global -> LDS by LDS-DMA (csrc/conv_bf16x6.h)
-        trip = twin_box[0] if twin_box is not None else None
-        if trip is None:
-            xc = x if x.is_contiguous() else x.contiguous()
-            trip = torch.empty(n * hi * wi * cin * 6, dtype=torch.uint8, device=x.device)
-            _lib.call("diga_make_triplet", _lib.ptr(xc), cin, _lib.ptr(trip), n * hi * wi, cin, _lib.stream())
-            if twin_box is not None:
-                twin_box[0] = trip
-        img = torch.empty(_lib.lib.diga_split_bf16x6_image_bytes(k, 1, cin), dtype=torch.uint8, device=x.device)
-        _lib.call("diga_split_bf16x6_image", _lib.ptr(w_krsc), _lib.ptr(img), k, 1, cin, _lib.stream())
-        _log_path(tag, "bf16x6")
-        _log_flops("conv_bwd_data" if tag == _TAG_BWD_DATA else "conv_fwd", 2.0 * n * ho * wo * k * cin, 2.0 * n * ho * wo * k * cin)
-        if epi is not None:
-            _lib.call("diga_conv2d_nhwc_bf16x6_epi", _lib.ptr(trip), _lib.ptr(img), _lib.ptr(out), n, hi, wi, cin, ho, wo, k,
-                      out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], ctypes.byref(epi), tag,
-                      _lib.stream())
-            return trip
-        _lib.call("diga_conv2d_nhwc_bf16x6", _lib.ptr(trip), _lib.ptr(img), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin, ho, wo, k,
-                  out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], _lib.ptr(stats), tag,
-                  _lib.stream())
-        return trip
-    if (math == 1 and _use_twin(cin, k, r * s, twin_box is not None)
-            and n * hi * wi * cin * 4 < (1 << 40)):
-        # split-bf16 arithmetic without register staging: both operands pre-split, copied global -> LDS by LDS-DMA
-        twin = twin_box[0] if twin_box is not None else None
-        if twin is None:
-            xc = x if x.is_contiguous() else x.contiguous()
-            twin = torch.empty(n * hi * wi * cin * 4, dtype=torch.uint8, device=x.device)
-            _lib.call("diga_make_twin", _lib.ptr(xc), cin, _lib.ptr(twin), n * hi * wi, cin, _lib.stream())
-            if twin_box is not None:
-                twin_box[0] = twin
-        _log_path(tag, "bf16x3")
-        img = torch.empty(_lib.lib.diga_split_bf16_image_bytes(k, r * s, cin), dtype=torch.uint8, device=x.device)
-        _lib.call("diga_split_bf16_image", _lib.ptr(w_krsc), _lib.ptr(img), k, r * s, cin, _lib.stream())
-        if epi is not None:
-            _lib.call("diga_conv2d_nhwc_twin_epi", _lib.ptr(twin), _lib.ptr(img), _lib.ptr(out), n, hi, wi, cin, ho, wo, k,
-                      out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], ctypes.byref(epi), tag,
-                      _lib.stream())
-            return twin
-        if copt is not None:
-            _lib.call("diga_conv2d_nhwc_twin_opts", _lib.ptr(twin), _lib.ptr(img), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin, ho, wo, k,
-                      out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], ctypes.byref(copt), tag, _lib.stream())
-            return twin
-        _lib.call("diga_conv2d_nhwc_twin", _lib.ptr(twin), _lib.ptr(img), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin, ho, wo, k,
-                  out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], _lib.ptr(stats), tag,
-                  _lib.stream())
-        return twin
-    if must_twin:
-        raise RuntimeError("DigaConv2d: the input holds split-twin bytes but the twin kernel is not selected "
-                           "(conv math or config.conv_twin changed since the producer ran)")
-    if math == 1:
-        _log_path(tag, "bf16x3")
-        # split-bf16 arithmetic: the weights are split once here (two bf16 arrays), the activations inside the kernel
-        nel = w_krsc.numel()
-        w_hi = torch.empty(nel, dtype=torch.int16, device=w_krsc.device)
-        w_lo = torch.empty(nel, dtype=torch.int16, device=w_krsc.device)
-        _lib.call("diga_split_bf16", _lib.ptr(w_krsc), _lib.ptr(w_hi), _lib.ptr(w_lo), nel, _lib.stream())
-        if epi is not None:
-            _lib.call("diga_conv2d_nhwc_bf16x3_epi", _lib.ptr(x), _lib.ptr(w_hi), _lib.ptr(w_lo), _lib.ptr(out),
-                      n, hi, wi, cin, x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1],
-                      doff[0], doff[1], ctypes.byref(epi), tag, _lib.stream())
-            return None
-        if copt is not None:
-            _lib.call("diga_conv2d_nhwc_bf16x3_opts", _lib.ptr(x), _lib.ptr(w_hi), _lib.ptr(w_lo), _lib.ptr(bias), _lib.ptr(out),
-                      n, hi, wi, cin, x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1],
-                      doff[0], doff[1], ctypes.byref(copt), tag, _lib.stream())
-            return None
-        _lib.call("diga_conv2d_nhwc_bf16x3", _lib.ptr(x), _lib.ptr(w_hi), _lib.ptr(w_lo), _lib.ptr(bias), _lib.ptr(out),
-                  n, hi, wi, cin, x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1],
-                  doff[0], doff[1], _lib.ptr(stats), tag, _lib.stream())
-        return None
+    if path is None:
+        path = _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag, None if stats is None else "chunks", epi is not None,
+                     opts, infer is not None, twin_box is not None, must_twin, x6_ok)
+    struct = inf_held = None
+    if path.variant == "epi":
+        struct = ctypes.byref(epi)
+    elif path.variant == "opts":
+        struct = ctypes.byref(_lib.ConvOptions(int(opts[0]), int(opts[1]), int(opts[2])))
+    elif path.variant == "infer":
+        inf, inf_held = _infer_epilogue(infer, out)
+        struct = ctypes.byref(inf)
     direct = 2.0 * n * ho * wo * k * r * s * cin
-    name = "conv_bwd_data" if tag == _TAG_BWD_DATA else "conv_fwd"
-    if (math == 0 and copt is not None and copt.upsample_shift == 0 and copt.activation == 0 and copt.reflect_pad
-            and doff[0] > 0 and doff[0] < min(hi, wi) and _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo)
-            and _wino_plan(hi, wi, doff[0])[0] >= 4):
-        # reflection padding folded into the Winograd input transform (the translator's 3x3 ResBlock convs; round 5)
-        d = doff[0]
-        tile, ratio = _wino_plan(hi, wi, d)
-        _log_flops(name, direct, direct * ratio)
-        _log_path(tag, "winograd")
-        ws = _lib.workspace(_lib.lib.diga_conv2d_winograd_workspace_bytes(n, hi, wi, cin, k, d, tile), x.device, "winograd")
-        _lib.call("diga_conv2d_winograd_f32_opts", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                  n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile, ctypes.byref(copt), _lib.ptr(_tile_table(n, hi, wi, d, tile, x.device)),
-                  tag, _lib.stream())
+    _log_path(tag, path.arith)
+    if path.flops:
+        _log_flops("conv_bwd_data" if tag == _TAG_BWD_DATA else "conv_fwd", direct, direct * path.ratio)
+    if path.family in ("winograd", "winograd_reflect"):
+        _winograd_launch(path, x, w_krsc, bias, out, abs(doff[0]), 1 if doff[0] < 0 else 0, tag, stats, struct, keep_v)
         return None
-    if (math == 0 and copt is None and (stats is None or wino_stats)
-            and _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo)):
-        d = abs(doff[0])
-        tile, ratio = _wino_plan(hi, wi, d)
-        if stats is not None and (tile < 4 or epi is not None or doff[0] < 0):
-            raise RuntimeError("DigaConv2d: Winograd statistics come with the forward output transform of 4x4 / 6x6 tiles")
-        if inf is not None and tile < 4:
-            raise RuntimeError("DigaConv2d: the inference epilogue comes with Winograd tiles of 4x4 / 6x6 (winograd_max_tile = 2)")
-        _log_flops(name, direct, direct * ratio)
-        x6w = inf is None and _wino_x6()              # (the inference epilogue stays exact fp32)
-        _log_path(tag, "winograd+bn" if inf is not None else "winograd/x6" if x6w else "winograd")
-        if x6w:
-            nbytes = _lib.lib.diga_conv2d_winograd_bf16x6_workspace_bytes(n, hi, wi, cin, k, d, tile)
-        else:
-            nbytes = _lib.lib.diga_conv2d_winograd_workspace_bytes(n, hi, wi, cin, k, d, tile)
-        ws = _lib.workspace(nbytes, x.device, "winograd")
-        tab = _tile_table(n, hi, wi, d, tile, x.device)
-        if x6w:
-            # one entry point for the plain forward / backward-data, the forward with statistics, the forward that keeps V and
-            # backward-data with the epilogue
-            vk = None
-            if epi is None and keep_v is not None and doff[0] > 0:
-                vk = keep_v[0] = _alloc_keep_v(_lib.lib.diga_conv2d_winograd_v_floats(n, hi, wi, cin, d, tile), x.device)
-            _lib.call("diga_conv2d_winograd_bf16x6", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out),
-                      _lib.ptr(vk), _lib.ptr(ws), ws.numel(), n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile,
-                      1 if doff[0] < 0 else 0, _lib.ptr(stats), ctypes.byref(epi) if epi is not None else None,
-                      _lib.ptr(tab), tag, _lib.stream())
-            return None
-        if inf is not None:
-            _lib.call("diga_conv2d_winograd_f32_infer", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                      n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile, ctypes.byref(inf), _lib.ptr(tab), tag, _lib.stream())
-            return None
-        if epi is not None:
-            _lib.call("diga_conv2d_winograd_f32_epi", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                      n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile, 1 if doff[0] < 0 else 0, ctypes.byref(epi), _lib.ptr(tab), tag,
-                      _lib.stream())
-            return None
-        if keep_v is not None and doff[0] > 0:
-            # keep_v: a one-element list -- the transformed input stays alive for this layer's weight gradient
-            keep_v[0] = _alloc_keep_v(_lib.lib.diga_conv2d_winograd_v_floats(n, hi, wi, cin, d, tile), x.device)
-        if keep_v is not None and doff[0] > 0 and keep_v[0] is not None:
-            _lib.call("diga_conv2d_winograd_f32_keep", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(keep_v[0]),
-                      _lib.ptr(ws), ws.numel(), n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile, _lib.ptr(stats), _lib.ptr(tab), tag,
-                      _lib.stream())
-            return None
-        _lib.call("diga_conv2d_winograd_f32", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                  n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile, 1 if doff[0] < 0 else 0, _lib.ptr(stats), _lib.ptr(tab), tag,
-                  _lib.stream())
-        return None
-    _log_flops(name, direct, direct)
-    _log_path(tag, "f32+bn" if inf is not None else "f32")
-    if inf is not None:
-        _lib.call("diga_conv2d_nhwc_f32_infer", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin,
-                  x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1],
-                  ctypes.byref(inf), tag, _lib.stream())
-        return None
-    if epi is not None:
-        _lib.call("diga_conv2d_nhwc_f32_epi", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(out), n, hi, wi, cin,
-                  x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1],
-                  ctypes.byref(epi), tag, _lib.stream())
-        return None
-    if copt is not None:
-        _lib.call("diga_conv2d_nhwc_f32_opts", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin,
-                  x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1],
-                  ctypes.byref(copt), tag, _lib.stream())
-        return None
-    _lib.call("diga_conv2d_nhwc_f32", _lib.ptr(x), _lib.ptr(w_krsc), _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin,
-              x.stride(2), ho, wo, k, out.stride(2), r, s, stride[0], stride[1], off0[0], off0[1], doff[0], doff[1],
-              _lib.ptr(stats), tag, _lib.stream())
+    lead, held, split = _operands(path, x, w_krsc, twin_box)         # (`held`, `inf_held`: alive until the kernel is enqueued)
+    _lib.call(_ENTRY[(path.family, path.variant)], *lead, *(() if path.variant == "epi" else (_lib.ptr(bias),)), _lib.ptr(out),
+              n, hi, wi, cin, *((x.stride(2),) if path.family in ("bf16x3", "f32") else ()), ho, wo, k, out.stride(2), r, s,
+              stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], struct if struct is not None else _lib.ptr(stats), tag,
+              _lib.stream())
+    return split
+
+
+# weight gradient: family -> (entry point, its workspace query); Winograd by the arithmetic of its products
+_WGRAD = {
+    "x6ls": ("diga_conv2d_wgrad_bf16x6_f32in", _lib.lib.diga_conv2d_wgrad_bf16x6_workspace_bytes),
+    "x6": ("diga_conv2d_wgrad_bf16x6", _lib.lib.diga_conv2d_wgrad_bf16x6_workspace_bytes),
+    "twin": ("diga_conv2d_wgrad_twin", _lib.lib.diga_conv2d_wgrad_twin_workspace_bytes),
+    "f32": ("diga_conv2d_wgrad_nhwc_f32", _lib.lib.diga_conv2d_wgrad_workspace_bytes),
+}
+_WGRAD_WINOGRAD = {
+    False: ("diga_conv2d_wgrad_winograd_f32", _lib.lib.diga_conv2d_wgrad_winograd_workspace_bytes),
+    True: ("diga_conv2d_wgrad_winograd_bf16x6", _lib.lib.diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes),
+}
+
+
+def _wgrad_launch(path, gy, x, dwp, r, s, stride, padding, dilation, splits=None, wino_v=None):
+    """dwp [Kp,R,S,Cp] = the weight gradient of gy [N,Ho,Wo,Kp] and x [N,Hi,Wi,Cp] on the kernel `path` (_wgrad_plan) names.
+    splits: (twin / triplet of gy, of x) for the families that read those; wino_v: the forward's kept Winograd transform of x."""
+    n, hi, wi, cp = x.shape
+    _, ho, wo, kp = gy.shape
+    _log_path("wgrad", path.arith)
+    if path.flops:
+        direct = 2.0 * n * ho * wo * kp * r * s * cp
+        _log_flops("conv_bwd_weight", direct, direct * path.ratio)
+    if path.family == "winograd":
+        name, size = _WGRAD_WINOGRAD[path.x6w]
+        ws = _lib.workspace(size(n, hi, wi, cp, kp, dilation[0], path.tile, 1 if wino_v is not None else 0), x.device, "winograd_wgrad")
+        tab = _tile_table(n, hi, wi, dilation[0], path.tile, x.device)
+        _lib.call(name, _lib.ptr(gy), _lib.ptr(x), _lib.ptr(wino_v), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(), n, hi, wi, cp, x.stride(2),
+                  kp, gy.stride(2), dilation[0], path.tile, _lib.ptr(tab), _lib.stream())
+        return
+    name, size = _WGRAD[path.family]
+    ws = _lib.workspace(size(n, ho, wo, kp, cp, r, s), x.device, "wgrad")
+    f32 = path.family == "f32"                         # (reads pitched fp32 tensors and takes the layer's arithmetic)
+    if path.family == "x6ls":                          # fp32 dy and x as they are (a saved triplet of x, if any, is ignored)
+        lead = (_lib.ptr(gy), gy.stride(2), _lib.ptr(x), x.stride(2))
+    else:
+        lead = (_lib.ptr(gy), _lib.ptr(x)) if f32 else (_lib.ptr(splits[0]), _lib.ptr(splits[1]))
+    _lib.call(name, *lead, _lib.ptr(dwp), _lib.ptr(ws), ws.numel(), n, hi, wi, cp, *((x.stride(2),) if f32 else ()), ho, wo, kp,
+              *((gy.stride(2),) if f32 else ()), r, s, stride[0], stride[1], -padding[0], -padding[1], dilation[0], dilation[1],
+              *((path.math,) if f32 else ()), _lib.stream())
+
+
+class _Call(NamedTuple):
+    """What one call of the autograd functions below carries besides x, weight and bias."""
+    stride: tuple = (1, 1)
+    padding: tuple = (0, 0)
+    dilation: tuple = (1, 1)
+    stats: object = None       # the statistics buffer the kernel fills for the BatchNorm behind it; (buffer, "records"): Winograd records
+    uses: object = None        # [weight-gradient calls of the current backward pass], or INLINE_WGRAD
+    twin_box: object = None    # a one-element list shared by the convs that read the very same x
+    x_is_twin: bool = False    # x holds split-twin bytes
+    dy_is_twin: bool = False   # the output gradient will arrive as a split twin
+    bn_box: object = None      # the BatchNorm that produced x (norm._BnFn): its gradient is finished in this conv's backward-data epilogue
+    opts: object = None        # (reflect_pad, upsample_shift, activation)
+    chain: object = None       # the convs on one tensor that chain their input gradients
+    infer: object = None       # (ab, residual, relu): the inference epilogue
 
 
 class _StemConvFn(torch.autograd.Function):
@@ -510,8 +582,9 @@ class _StemConvFn(torch.autograd.Function):
     floats, then a 1x1 conv on the GEMM kernels.  No gradient wrt the input (it is the image)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, padding, dilation, stats=None, uses=None, twin_box=None, infer=None):
+    def forward(ctx, x, weight, bias, call):
         _lib.require_gpu(x, weight)
+        stride, padding = call.stride, call.padding
         xc = x.detach().float().contiguous()                      # NCHW
         n, c, h, w_ = xc.shape
         k, _, r, s = weight.shape
@@ -539,7 +612,7 @@ class _StemConvFn(torch.autograd.Function):
         w2 = _pad_last(weight.detach().permute(0, 2, 3, 1).reshape(k, 1, 1, kk).contiguous(), kp)
         out = torch.empty((n, ho, wo, k), dtype=torch.float32, device=x.device)
         b = None if bias is None else bias.detach().float().contiguous()
-        _conv_launch(xcol, w2, b, out, (1, 1), (0, 0), (1, 1), _TAG_FWD, stats, x6_ok=False, infer=infer)     # (bf16x6 mode: the stem stays exact fp32)
+        _conv_launch(xcol, w2, b, out, (1, 1), (0, 0), (1, 1), _TAG_FWD, call.stats, x6_ok=False, infer=call.infer)     # (bf16x6 mode: the stem stays exact fp32)
         ctx.save_for_backward(xcol)
         ctx.geom = (k, c, r, s, kk, kp, bias is not None, weight.stride())
         return out.permute(0, 3, 1, 2)
@@ -559,17 +632,13 @@ class _StemConvFn(torch.autograd.Function):
         dw = db = None
         if ctx.needs_input_grad[1]:
             dwp = torch.empty((kq, 1, 1, kp), dtype=torch.float32, device=xcol.device)
-            nbytes = _lib.lib.diga_conv2d_wgrad_workspace_bytes(n, ho, wo, kq, kp, 1, 1)
-            ws = _lib.workspace(nbytes, xcol.device, "wgrad")
-            lm = _layer_math(1, 1, kp, False)
-            _log_path("wgrad", "bf16x3" if lm == 1 else "f32")
-            _lib.call("diga_conv2d_wgrad_nhwc_f32", _lib.ptr(gyp), _lib.ptr(xcol), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(),
-                      n, ho, wo, kp, kp, ho, wo, kq, kq, 1, 1, 1, 1, 0, 0, 1, 1, lm, _lib.stream())
+            path = _wgrad_plan(n, ho, wo, kp, kq, 1, 1, (1, 1), (0, 0), (1, 1), ho, wo, stem=True)
+            _wgrad_launch(path, gyp, xcol, dwp, 1, 1, (1, 1), (0, 0), (1, 1))
             dw = torch.empty_strided((k, c, r, s), w_strides, dtype=torch.float32, device=xcol.device)
             dw.copy_(dwp[:k, 0, 0, :kk].reshape(k, r, s, c).permute(0, 3, 1, 2))
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(gy)
-        return None, dw, db, None, None, None, None, None, None, None
+        return None, dw, db, None
 
 
 def _set_mask(epi, box, xn, cp):
@@ -586,22 +655,37 @@ def _set_mask(epi, box, xn, cp):
 
 class _Conv2dFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, padding, dilation, stats=None, uses=None, twin_box=None, x_is_twin=False,
-                dy_is_twin=False, bn_box=None, opts=None, chain=None, infer=None):
+    def forward(ctx, x, weight, bias, call):
         # x: NCHW-shaped; weight: [K,C,R,S] (any dense layout); returns an NCHW-shaped channels_last tensor
         _lib.require_gpu(x, weight)
+        stride, padding, dilation, stats, uses, twin_box, x_is_twin, dy_is_twin, bn_box, opts, chain, infer = call
         if x_is_twin:          # the producer wrote the split twin instead of fp32 (same bytes per element): hand it on
             xt = x.detach().permute(0, 2, 3, 1)
             if not (xt.is_contiguous() and xt.dtype == torch.float32):
                 raise RuntimeError("DigaConv2d: a twin-only input must be a dense NHWC float32-shaped buffer")
             twin_box = [xt.reshape(-1).view(torch.uint8)]
+        if opts is not None and any(opts) and (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)):
+            raise RuntimeError("DigaConv2d: folded reflect padding / upsampling / tanh are inference-only (no backward)")
         xn = x.detach().permute(0, 2, 3, 1)
+        n, hi, wi, _ = xn.shape
         k, c, r, s = weight.shape
         cp = _pad_to(c)
+        up = int(opts[1]) if opts is not None else 0
+        ho = ((hi << up) + 2 * padding[0] - dilation[0] * (r - 1) - 1) // stride[0] + 1
+        wo = ((wi << up) + 2 * padding[1] - dilation[1] * (s - 1) - 1) // stride[1] + 1
+        wino_stats = isinstance(stats, tuple)         # (buffer, "records"): the Winograd output transform fills it (DigaConv2d.forward)
+        if wino_stats:
+            stats = stats[0]
+        # exact-fp32 Winograd layers whose weight gradient is wanted keep their transformed input (4x the input's bytes, HBM
+        # is 288 GB): the backward-weight pass then skips a bandwidth pass of 5x the input (config.winograd_keep_v = False: recompute)
+        path = _plan(n, hi, wi, cp, k, r, s, stride, (-padding[0], -padding[1]), dilation, ho, wo, _TAG_FWD,
+                     None if stats is None else "records" if wino_stats else "chunks", opts=opts, infer=infer is not None,
+                     shared=twin_box is not None, must_twin=bool(x_is_twin),
+                     keep=ctx.needs_input_grad[1])
         # bf16x6 with the split in the loader waves reads a channel slice of a wider NHWC buffer in place (and saves that view for the
         # weight gradient); every other path gets a dense copy
-        in_place = (cp == c and not x_is_twin and bn_box is None and chain is None and _x6_loader()
-                    and _layer_math(r, s, cp, opts is None or not any(opts)) == 2 and _nhwc_ld(xn) is not None)
+        in_place = (cp == c and not x_is_twin and bn_box is None and chain is None and path.family == "x6ls"
+                    and _nhwc_ld(xn) is not None)
         if not in_place and (not xn.is_contiguous() or xn.dtype != torch.float32):
             xn = xn.contiguous().float()
         xn = _pad_last(xn, cp)
@@ -609,34 +693,18 @@ class _Conv2dFn(torch.autograd.Function):
         if not w.is_contiguous():
             w = w.contiguous()
         w = _pad_last(w, cp)
-        n, hi, wi, _ = xn.shape
-        up = int(opts[1]) if opts is not None else 0
-        if opts is not None and any(opts) and (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)):
-            raise RuntimeError("DigaConv2d: folded reflect padding / upsampling / tanh are inference-only (no backward)")
-        ho = ((hi << up) + 2 * padding[0] - dilation[0] * (r - 1) - 1) // stride[0] + 1
-        wo = ((wi << up) + 2 * padding[1] - dilation[1] * (s - 1) - 1) // stride[1] + 1
         out = torch.empty((n, ho, wo, k), dtype=torch.float32, device=x.device)
         b = None if bias is None else bias.detach().float().contiguous()
-        # exact-fp32 Winograd layers whose weight gradient is wanted keep their transformed input (4x the input's bytes, HBM
-        # is 288 GB): the backward-weight pass then skips a bandwidth pass of 5x the input (config.winograd_keep_v = False: recompute)
-        keep_v = None
-        wino_stats = isinstance(stats, tuple)         # (buffer, "records"): the Winograd output transform fills it (DigaConv2d.forward)
-        if wino_stats:
-            stats = stats[0]
-        lm = _layer_math(r, s, cp, opts is None or not any(opts))
-        if (ctx.needs_input_grad[1] and lm == 0 and k % 256 == 0 and cp % 128 == 0 and (stats is None or wino_stats)
-                and (opts is None or not any(opts)) and config.active().winograd_keep_v
-                and _winograd_ok(n, hi, wi, cp, k, r, s, stride, (-padding[0], -padding[1]), dilation, ho, wo)):
-            keep_v = [None]
-        x_twin = _conv_launch(xn, w, b, out, stride, (-padding[0], -padding[1]), dilation, _TAG_FWD, stats, twin_box,
-                              must_twin=bool(x_is_twin), opts=opts, keep_v=keep_v, wino_stats=wino_stats, infer=infer)
+        keep_v = [None] if path.variant == "keep" else None
+        x_twin = _conv_launch(xn, w, b, out, stride, (-padding[0], -padding[1]), dilation, _TAG_FWD, stats, twin_box, opts=opts,
+                              keep_v=keep_v, infer=infer, path=path)
         ctx.wino_v = keep_v[0] if keep_v is not None else None
         ctx.max_tile = config.active().winograd_max_tile      # (the kept transform's layout is the forward's tile: checked in backward)
         ctx.save_for_backward(xn, w)
         # the split twin of the input serves the weight gradient too (multi-tap / shared-input layers, Cout >= 256)
-        ctx.x_twin = x_twin if (lm != 2 and ctx.needs_input_grad[1] and k >= 256 and k % 8 == 0 and cp == c) else None
+        ctx.x_twin = x_twin if (path.math != 2 and ctx.needs_input_grad[1] and k >= 256 and k % 8 == 0 and cp == c) else None
         # bf16x6: the three-plane triplet of the (padded) input serves the weight gradient of every eligible layer
-        ctx.x_trip = x_twin if (lm == 2 and ctx.needs_input_grad[1]) else None
+        ctx.x_trip = x_twin if (path.math == 2 and ctx.needs_input_grad[1]) else None
         ctx.dy_is_twin = bool(dy_is_twin)
         if dy_is_twin and ctx.x_twin is None and ctx.needs_input_grad[1]:
             raise RuntimeError("DigaConv2d: twin_grad=True on a layer whose weight gradient is not on the twin kernel")
@@ -696,9 +764,10 @@ class _Conv2dFn(torch.autograd.Function):
         x_twin = getattr(ctx, "x_twin", None)
         use_tw = x_twin is not None and ctx.needs_input_grad[1] and _lib.get_conv_math() == 1 and kp == k
         dy_box = [None] if use_tw else None            # the twin of dy: built once, read by backward-data and -weight
-        lm = _layer_math(r, s, cp)                     # this layer's arithmetic (bf16x6 mode: 2 for pointwise layers, else 0)
+        wpath = _wgrad_plan(n, hi, wi, cp, kp, r, s, stride, padding, dilation, ho, wo, x_twin=use_tw)
+        lm = wpath.math                                # this layer's arithmetic (bf16x6 mode: 2 for pointwise layers, else 0)
         use_x6 = lm == 2
-        x6_ls = use_x6 and _x6_loader()                # ... with the operands split by the loader waves: no triplets (read per call)
+        x6_ls = wpath.family == "x6ls"                 # ... with the operands split by the loader waves: no triplets (read per call)
         if use_x6:
             dy_box = [None]                            # the triplet of dy, shared the same way (stays empty in the loader form)
         if ctx.dy_is_twin:          # the BatchNorm after this conv wrote its dx as a twin (same bytes per element)
@@ -810,12 +879,16 @@ class _Conv2dFn(torch.autograd.Function):
             alias = kp == k and cp == c_true and dw.permute(0, 2, 3, 1).is_contiguous()
             dwp = dw.permute(0, 2, 3, 1) if alias else torch.empty((kp, r, s, cp), dtype=torch.float32, device=w.device)
 
-            dy_twin = None
-            if use_tw:
-                dy_twin = dy_box[0]
-                if dy_twin is None:                 # backward-data did not build it (no input gradient, strided, narrow)
-                    dy_twin = torch.empty(n * ho * wo * kp * 4, dtype=torch.uint8, device=w.device)
-                    _lib.call("diga_make_twin", _lib.ptr(gyp), kp, _lib.ptr(dy_twin), n * ho * wo, kp, st)
+            # the pre-split operands of the twin / triplet kernels: dy's is shared with backward-data, x's comes from the forward
+            splits = None
+            if use_tw or (use_x6 and not x6_ls):
+                dy_split, x_split = dy_box[0], x_twin if use_tw else x_trip
+                if dy_split is None:                # backward-data did not build it (no input gradient, strided, narrow)
+                    dy_split = _make_split(gyp, kp, n * ho * wo, kp, use_x6)
+                if x_split is None:                 # (bf16x6) the forward ran in another arithmetic and saved none
+                    x_split = _make_split(xn, xn.stride(2), n * hi * wi, cp, True)      # (xn may be a channel slice saved by the loader form)
+                splits = (dy_split, x_split)
+            ctx.x_trip = None
 
             wino_v = getattr(ctx, "wino_v", None)
             ctx.wino_v = None
@@ -824,73 +897,8 @@ class _Conv2dFn(torch.autograd.Function):
                                    f"({ctx.max_tile} -> {config.active().winograd_max_tile}): the kept input transform has the forward's "
                                    "layout (set_conv_math(..., exact=) belongs between steps, not inside one)")
 
-            def run_twin():
-                nbytes = _lib.lib.diga_conv2d_wgrad_twin_workspace_bytes(n, ho, wo, kp, cp, r, s)
-                ws = _lib.workspace(nbytes, w.device, "wgrad")
-                _lib.call("diga_conv2d_wgrad_twin", _lib.ptr(dy_twin), _lib.ptr(x_twin), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(),
-                          n, hi, wi, cp, ho, wo, kp, r, s, stride[0], stride[1], -padding[0], -padding[1], dilation[0],
-                          dilation[1], _lib.stream())
-                if not alias:
-                    dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
-
-            dy_trip = x_tr = None
-            if use_x6 and not x6_ls:
-                dy_trip, x_tr = dy_box[0], x_trip
-                if dy_trip is None:                 # backward-data did not build it (no input gradient wanted)
-                    dy_trip = torch.empty(n * ho * wo * kp * 6, dtype=torch.uint8, device=w.device)
-                    _lib.call("diga_make_triplet", _lib.ptr(gyp), kp, _lib.ptr(dy_trip), n * ho * wo, kp, st)
-                if x_tr is None:                    # the forward ran in another arithmetic and saved none
-                    x_tr = torch.empty(n * hi * wi * cp * 6, dtype=torch.uint8, device=w.device)
-                    _lib.call("diga_make_triplet", _lib.ptr(xn), xn.stride(2), _lib.ptr(x_tr), n * hi * wi, cp, st)     # (xn may be a channel slice saved by the loader form)
-            ctx.x_trip = None
-
-            def run_x6():
-                _log_path("wgrad", "bf16x6/ls" if x6_ls else "bf16x6")
-                _log_flops("conv_bwd_weight", 2.0 * n * ho * wo * kp * cp, 2.0 * n * ho * wo * kp * cp)
-                nbytes = _lib.lib.diga_conv2d_wgrad_bf16x6_workspace_bytes(n, ho, wo, kp, cp, 1, 1)
-                ws = _lib.workspace(nbytes, w.device, "wgrad")
-                if x6_ls:                           # fp32 dy and x as they are (a saved triplet of x, if any, is ignored)
-                    _lib.call("diga_conv2d_wgrad_bf16x6_f32in", _lib.ptr(gyp), gyp.stride(2), _lib.ptr(xn), xn.stride(2), _lib.ptr(dwp),
-                              _lib.ptr(ws), ws.numel(), n, hi, wi, cp, ho, wo, kp, 1, 1, stride[0], stride[1], -padding[0], -padding[1],
-                              dilation[0], dilation[1], _lib.stream())
-                    if not alias:
-                        dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
-                    return
-                _lib.call("diga_conv2d_wgrad_bf16x6", _lib.ptr(dy_trip), _lib.ptr(x_tr), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(),
-                          n, hi, wi, cp, ho, wo, kp, 1, 1, stride[0], stride[1], -padding[0], -padding[1], dilation[0],
-                          dilation[1], _lib.stream())
-                if not alias:
-                    dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
-
             def run():
-                if use_x6:
-                    return run_x6()
-                if use_tw:
-                    _log_path("wgrad", "bf16x3")
-                    return run_twin()
-                if (lm == 0 and kp % 256 == 0 and cp % 128 == 0 and gyp.stride(2) % 4 == 0
-                        and _winograd_ok(n, hi, wi, cp, kp, r, s, stride, (-padding[0], -padding[1]), dilation, ho, wo)):
-                    tile, ratio = _wino_plan(hi, wi, dilation[0])
-                    x6w = _wino_x6()                # (read per call: the kept V is fp32 whichever arithmetic the forward ran)
-                    sfx = "bf16x6" if x6w else "f32"
-                    _log_path("wgrad", "winograd/x6" if x6w else "winograd")
-                    _log_flops("conv_bwd_weight", 2.0 * n * ho * wo * kp * 9 * cp, 2.0 * n * ho * wo * kp * 9 * cp * ratio)
-                    nb = getattr(_lib.lib, "diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes" if x6w else "diga_conv2d_wgrad_winograd_workspace_bytes")(
-                        n, hi, wi, cp, kp, dilation[0], tile, 1 if wino_v is not None else 0)
-                    wsw = _lib.workspace(nb, w.device, "winograd_wgrad")
-                    tab = _tile_table(n, hi, wi, dilation[0], tile, w.device)
-                    _lib.call("diga_conv2d_wgrad_winograd_" + sfx, _lib.ptr(gyp), _lib.ptr(xn), _lib.ptr(wino_v), _lib.ptr(dwp), _lib.ptr(wsw),
-                              wsw.numel(), n, hi, wi, cp, xn.stride(2), kp, gyp.stride(2), dilation[0], tile, _lib.ptr(tab), _lib.stream())
-                    if not alias:
-                        dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
-                    return
-                _log_flops("conv_bwd_weight", 2.0 * n * ho * wo * kp * r * s * cp, 2.0 * n * ho * wo * kp * r * s * cp)
-                _log_path("wgrad", "bf16x3" if lm == 1 else "f32")
-                nbytes = _lib.lib.diga_conv2d_wgrad_workspace_bytes(n, ho, wo, kp, cp, r, s)
-                ws = _lib.workspace(nbytes, w.device, "wgrad")
-                _lib.call("diga_conv2d_wgrad_nhwc_f32", _lib.ptr(gyp), _lib.ptr(xn), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(),
-                          n, hi, wi, cp, xn.stride(2), ho, wo, kp, gyp.stride(2), r, s, stride[0], stride[1],
-                          -padding[0], -padding[1], dilation[0], dilation[1], lm, _lib.stream())
+                _wgrad_launch(wpath, gyp, xn, dwp, r, s, stride, padding, dilation, splits, wino_v)
                 if not alias:
                     dw.copy_(dwp[:k, :, :, :c_true].permute(0, 3, 1, 2))
 
@@ -907,11 +915,10 @@ class _Conv2dFn(torch.autograd.Function):
                 with torch.cuda.stream(side):
                     run()
                 dw.record_stream(side)          # (a returned gradient: never held, see _lib.release_to_side)
-                _lib.release_to_side(side, (gyp, xn) + (() if alias else (dwp,)) + ((dy_twin, x_twin) if use_tw else ()) + ((dy_trip, x_tr) if (use_x6 and not x6_ls) else ())
-                                     + ((wino_v,) if wino_v is not None else ()))
+                _lib.release_to_side(side, (gyp, xn) + (() if alias else (dwp,)) + (splits or ()) + ((wino_v,) if wino_v is not None else ()))
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(gy)
-        return dx, dw, db, None, None, None, None, None, None, None, None, None, None, None, None
+        return dx, dw, db, None
 
 
 class DigaConv2d(nn.Conv2d):
@@ -974,79 +981,60 @@ class DigaConv2d(nn.Conv2d):
         fn = _Conv2dFn
         if self._stem_path(x):
             fn = _StemConvFn           # image-like input: gather the few channels of all taps into the K dimension
+        stride, padding, dilation = tuple(self.stride), tuple(self.padding), tuple(self.dilation)
+        stats = wino_records = None
         if infer is not None:
             from diga_amd.model.norm import eval_coefficients
             if twin_grad or chain is not None or (opts is not None and any(opts)) or getattr(x, "_diga_is_twin", False):
                 raise RuntimeError("DigaConv2d: infer= is a plain forward (no twin gradient, chain, options or twin input)")
             bn, residual, relu = infer
-            inf = (eval_coefficients(bn), residual, bool(relu))
-            with torch.no_grad():
-                if fn is _StemConvFn:
-                    return fn.apply(x, self.weight, self.bias, tuple(self.stride), tuple(self.padding), tuple(self.dilation), None, None,
-                                    None, inf)
-                return fn.apply(x, self.weight, self.bias, tuple(self.stride), tuple(self.padding), tuple(self.dilation), None, None,
-                                None, False, False, None, None, None, inf)
-        stats = None
-        if self.emit_bn_stats and self.training and self.out_channels % 4 == 0:
-            n, _, h, w = x.shape
-            ho = (h + 2 * self.padding[0] - self.dilation[0] * (self.kernel_size[0] - 1) - 1) // self.stride[0] + 1
-            wo = (w + 2 * self.padding[1] - self.dilation[1] * (self.kernel_size[1] - 1) - 1) // self.stride[1] + 1
-        wino_records = None
-        if self.emit_bn_stats and self.training and self.out_channels % 4 == 0:
-            on_wino = (_layer_math(self.kernel_size[0], self.kernel_size[1], _pad_to(self.in_channels)) == 0 and fn is _Conv2dFn and (opts is None or not any(opts))
-                       and _winograd_ok(n, h, w, _pad_to(self.in_channels), self.out_channels, self.kernel_size[0], self.kernel_size[1],
-                                        self.stride, (-self.padding[0], -self.padding[1]), tuple(self.dilation), ho, wo))
-            if not on_wino:
-                stats = torch.empty(_lib.lib.diga_conv2d_stats_floats(n, ho, wo, self.out_channels), dtype=torch.float32,
-                                    device=x.device)
-            elif config.active().winograd_stats:
-                # round 5: the Winograd output transform (4x4 / 6x6 tiles) leaves the statistics as records of unequal size
-                # (diga_bn_fwd_records); F(2x2)-only runs keep the BatchNorm's own statistics pass
-                plan = winograd_stats_plan(n, h, w, _pad_to(self.in_channels), self.out_channels, self.kernel_size[0], self.kernel_size[1],
-                                           self.stride, self.padding, self.dilation, ho, wo)
-                if plan is not None:
-                    wino_records = int(plan[1])
-                    stats = (torch.empty(plan[0], dtype=torch.float32, device=x.device), "records")
-        uses = None
-        if torch.is_grad_enabled() and self.weight.requires_grad:
-            if self._bw_seen[0] > 0:          # a backward pass has consumed the previous graph(s)
-                self._bw_seen[0] = 0
-            uses = self._bw_seen              # [weight-gradient calls of the current backward pass]
-        twin_box = None
-        if self.share_twin:                   # several convs read this very tensor: the first one builds its split twin
-            twin_box = getattr(x, "_diga_twin_box", None)
-            if twin_box is None:
-                twin_box = x._diga_twin_box = [None]
-        x_is_twin = bool(getattr(x, "_diga_is_twin", False))
-        if x_is_twin and fn is not _Conv2dFn:
-            raise RuntimeError("DigaConv2d: twin-only input on the stem path")
-        bn_box = getattr(x, "_diga_bn_box", None)
-        if bn_box is not None and (self.share_twin or chain is not None or fn is not _Conv2dFn or not torch.is_grad_enabled()):
-            bn_box = None                     # several convs read this tensor (the chain carries the box) / no backward
-        if opts is not None and any(opts):
-            if fn is not _Conv2dFn or stats is not None:
-                raise RuntimeError("DigaConv2d: folded padding / upsampling / activation need the implicit-GEMM path without BN statistics")
-            y = fn.apply(x, self.weight, self.bias, tuple(self.stride), tuple(self.padding), tuple(self.dilation), None, uses,
-                         twin_box, False, False, None, tuple(int(v) for v in opts))
-        elif x_is_twin or twin_grad or bn_box is not None or chain is not None:
-            if fn is not _Conv2dFn or (self.bias is not None and twin_grad):
-                if chain is not None:
-                    chain["disabled"] = True
-                else:
-                    raise RuntimeError("DigaConv2d: twin gradient needs a bias-free conv on the implicit-GEMM path")
-            y = fn.apply(x, self.weight, self.bias, tuple(self.stride), tuple(self.padding), tuple(self.dilation), stats, uses,
-                         twin_box, x_is_twin, bool(twin_grad), bn_box, None, chain) if fn is _Conv2dFn else \
-                fn.apply(x, self.weight, self.bias, tuple(self.stride), tuple(self.padding), tuple(self.dilation), stats, uses, twin_box)
+            call = _Call(stride, padding, dilation, infer=(eval_coefficients(bn), residual, bool(relu)))
         else:
-            y = fn.apply(x, self.weight, self.bias, tuple(self.stride), tuple(self.padding), tuple(self.dilation), stats, uses,
-                         twin_box)
+            if self.emit_bn_stats and self.training and self.out_channels % 4 == 0:
+                n, _, h, w = x.shape
+                r, s = self.kernel_size
+                cp = _pad_to(self.in_channels)
+                ho = (h + 2 * padding[0] - dilation[0] * (r - 1) - 1) // stride[0] + 1
+                wo = (w + 2 * padding[1] - dilation[1] * (s - 1) - 1) // stride[1] + 1
+                form, path = _stats_plan(n, h, w, cp, self.out_channels, r, s, stride, padding, dilation, ho, wo, opts, fn is _Conv2dFn)
+                if form == "chunks":
+                    stats = torch.empty(_lib.lib.diga_conv2d_stats_floats(n, ho, wo, self.out_channels), dtype=torch.float32,
+                                        device=x.device)
+                elif form == "records":
+                    floats, wino_records = winograd_stats_plan(n, h, w, cp, self.out_channels, r, s, stride, padding, dilation, ho, wo)
+                    stats = (torch.empty(floats, dtype=torch.float32, device=x.device), "records")
+            uses = None
+            if torch.is_grad_enabled() and self.weight.requires_grad:
+                if self._bw_seen[0] > 0:          # a backward pass has consumed the previous graph(s)
+                    self._bw_seen[0] = 0
+                uses = self._bw_seen              # [weight-gradient calls of the current backward pass]
+            twin_box = None
+            if self.share_twin:                   # several convs read this very tensor: the first one builds its split twin
+                twin_box = getattr(x, "_diga_twin_box", None)
+                if twin_box is None:
+                    twin_box = x._diga_twin_box = [None]
+            x_is_twin = bool(getattr(x, "_diga_is_twin", False))
+            if x_is_twin and fn is not _Conv2dFn:
+                raise RuntimeError("DigaConv2d: twin-only input on the stem path")
+            bn_box = getattr(x, "_diga_bn_box", None)
+            if bn_box is not None and (self.share_twin or chain is not None or fn is not _Conv2dFn or not torch.is_grad_enabled()):
+                bn_box = None                     # several convs read this tensor (the chain carries the box) / no backward
+            if opts is not None and any(opts):
+                if fn is not _Conv2dFn or stats is not None:
+                    raise RuntimeError("DigaConv2d: folded padding / upsampling / activation need the implicit-GEMM path without BN statistics")
+                call = _Call(stride, padding, dilation, None, uses, twin_box, opts=tuple(int(v) for v in opts))
+            else:
+                if (x_is_twin or twin_grad or bn_box is not None or chain is not None) and (fn is not _Conv2dFn or (self.bias is not None and twin_grad)):
+                    if chain is None:
+                        raise RuntimeError("DigaConv2d: twin gradient needs a bias-free conv on the implicit-GEMM path")
+                    chain["disabled"] = True
+                call = _Call(stride, padding, dilation, stats, uses, twin_box, x_is_twin, bool(twin_grad), bn_box, None, chain)
+        with torch.set_grad_enabled(infer is None and torch.is_grad_enabled()):       # (infer=: nothing is differentiated)
+            y = fn.apply(x, self.weight, self.bias, call)
         if wino_records is not None:
             y._diga_bn_partials = (stats[0], ("records", wino_records))
         elif stats is not None:
-            chunk = _lib.lib.diga_conv2d_stats_chunk_rows(n, h, w, _pad_to(self.in_channels), ho, wo, self.out_channels,
-                                                          self.kernel_size[0], self.kernel_size[1], self.stride[0], self.stride[1],
-                                                          -self.padding[0], -self.padding[1],
-                                                          _layer_math(self.kernel_size[0], self.kernel_size[1], _pad_to(self.in_channels),
-                                                                      fn is _Conv2dFn))
+            chunk = _lib.lib.diga_conv2d_stats_chunk_rows(n, h, w, cp, ho, wo, self.out_channels, r, s, stride[0], stride[1],
+                                                          -padding[0], -padding[1], path.math)
             y._diga_bn_partials = (stats, chunk)     # picked up by the DigaBatchNorm2d that consumes y
         return y

@@ -30,16 +30,14 @@ _pkg = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 if os.path.dirname(_pkg) not in sys.path:
     sys.path.append(os.path.dirname(_pkg))
 from diga_amd import _lib  # noqa: E402
-from diga_amd.model.conv import INLINE_WGRAD, DigaConv2d, _Conv2dFn  # noqa: E402
+from diga_amd.model.conv import INLINE_WGRAD, DigaConv2d, _Call, _Conv2dFn  # noqa: E402
 from diga_amd.model.norm import DigaTrainableBatchNorm2d, _SmallLinearFn, nhwc  # noqa: E402
-
-_ONE, _ZERO = (1, 1), (0, 0)
 
 
 def _pointwise(x, w2d, bias=None):
     """1x1 convolution of an NCHW-shaped tensor with a [Cout, Cin] matrix (any autograd tensor) on the implicit-GEMM kernels."""
     # (INLINE_WGRAD: w2d may be a non-leaf -- its gradient is read by the next backward node, not by the optimizer after the join)
-    return _Conv2dFn.apply(x, w2d[:, :, None, None], bias, _ONE, _ZERO, _ONE, None, INLINE_WGRAD)
+    return _Conv2dFn.apply(x, w2d[:, :, None, None], bias, _Call(uses=INLINE_WGRAD))
 
 
 def _fold(wf, w):
