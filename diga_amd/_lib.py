@@ -82,6 +82,8 @@ SIGNATURES = {
     "diga_conv2d_wgrad_bf16x6": (INT, [P, P, P, P, SZ] + [I64] * 15 + [P]),
     "diga_conv2d_nhwc_bf16x6_f32in": (INT, [P, I64, P, P, P] + [I64] * 16 + [P, INT, P]),
     "diga_conv2d_nhwc_bf16x6_f32in_epi": (INT, [P, I64, P, P] + [I64] * 16 + [P, INT, P]),
+    "diga_infer_conv2d_nhwc_bf16x6": (INT, [P, P, P, P] + [I64] * 16 + [P, INT, P]),
+    "diga_infer_conv2d_nhwc_bf16x6_f32in": (INT, [P, I64, P, P, P] + [I64] * 16 + [P, INT, P]),
     "diga_conv2d_wgrad_bf16x6_f32in": (INT, [P, I64, P, I64, P, P, SZ] + [I64] * 15 + [P]),
     "diga_im2col_nchw": (INT, [P, P] + [I64] * 11 + [P]),
     "diga_norm_workspace_bytes": (SZ, [I64, I64, I64]),
@@ -116,6 +118,7 @@ SIGNATURES = {
     "diga_wgrad_batched_bf16x6_f32in": (INT, [P, P, P, P, SZ] + [I64] * 4 + [P]),
     "diga_conv2d_winograd_bf16x6_workspace_bytes": (SZ, [I64] * 7),
     "diga_conv2d_winograd_bf16x6": (INT, [P, P, P, P, P, P, SZ] + [I64] * 9 + [INT, P, P, P, INT, P]),
+    "diga_infer_conv2d_winograd_bf16x6": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P, INT, P]),
     "diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes": (SZ, [I64] * 7 + [INT]),
     "diga_conv2d_wgrad_winograd_bf16x6": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P]),
     "diga_conv2d_nhwc_bf16x3_epi": (INT, [P, P, P, P] + [I64] * 17 + [P, INT, P]),

@@ -62,6 +62,7 @@ class StepConfig:
     junction_chain: bool = True
     fold_downsample_bn: bool = True      # the downsample BatchNorm's apply pass inside the junction relu(bn3(c3) + skip) that alone reads it
     fold_eval_bn: bool = False           # eval-mode BatchNorm (+ skip, + ReLU) of the trunk inside the epilogue of the fp32 conv in front of it (bit-identical; offline passes)
+    fold_eval_bn_x6: bool = False        # ... and, under conv_math 2, inside the bf16x6 kernels as well: the pointwise layers' drain and, with x6_winograd, the Winograd output transform behind the bf16x6 products (means something only with fold_eval_bn)
     # ---- data parallelism (diga_amd/ddp.py)
     ddp_bucket_mb: int = 25
     ddp_grad_views: bool = True          # gradients live in the all-reduce buckets
@@ -103,6 +104,7 @@ class StepConfig:
         c.junction_chain = _flag("DIGA_JUNCTION_CHAIN", c.junction_chain)
         c.fold_downsample_bn = _flag("DIGA_FOLD_DOWNSAMPLE_BN", c.fold_downsample_bn)
         c.fold_eval_bn = _flag("DIGA_FOLD_EVAL_BN", c.fold_eval_bn)
+        c.fold_eval_bn_x6 = _flag("DIGA_FOLD_EVAL_BN_X6", c.fold_eval_bn_x6)
         c.ddp_bucket_mb = int(e("DIGA_DDP_BUCKET_MB", c.ddp_bucket_mb))
         c.ddp_grad_views = _flag("DIGA_DDP_GRAD_VIEWS", c.ddp_grad_views)
         c.ddp_overlap = _flag("DIGA_DDP_OVERLAP", c.ddp_overlap)
@@ -126,6 +128,8 @@ class StepConfig:
             raise ValueError(f"x6_winograd must be a bool, not {self.x6_winograd!r}")
         if not isinstance(self.fold_eval_bn, bool):
             raise ValueError(f"fold_eval_bn must be a bool, not {self.fold_eval_bn!r}")
+        if not isinstance(self.fold_eval_bn_x6, bool):
+            raise ValueError(f"fold_eval_bn_x6 must be a bool, not {self.fold_eval_bn_x6!r}")
         if self.winograd_max_tile not in (2, 4, 6):
             raise ValueError(f"winograd_max_tile must be 2, 4 or 6, not {self.winograd_max_tile!r}")
         return self

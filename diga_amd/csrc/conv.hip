@@ -121,7 +121,7 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 // what the BatchNorm after the conv needs -- per channel sum(y - s), sum((y - s)^2) and s = the tile's first row,
 // over the tile's valid rows -- in exactly the layout colstats_partial_kernel produces with 128-row chunks, so the
 // BN forward skips its own statistics pass over the conv output.
-template <int TM, int TN, bool EPI = false, int NTHR = 256, bool INF = false>
+template <int TM, int TN, bool EPI = false, int NTHR = 256, bool INF = false, int TAG = 0>
 __device__ __forceinline__ void drain_stage(const float* stage_in, const ConvArgs& a, int m0, int n0, int t, int tile_m,
                                             bool active = true);
 
@@ -225,7 +225,9 @@ __device__ __forceinline__ void epi_rows(const float* __restrict__ stage, const 
 // without the raw tensor ever reaching HBM.  Residual rows are taken eight at a time, all loads in flight before the first use,
 // with the running row pointers of epi_rows.  RES: a residual is given.  Entry points guarantee Cout % 4 == 0, lds % 4 == 0,
 // 16-byte aligned pointers.
-template <int TM, int TN, int NTHR, bool RES>
+// TAG: a second kernel family gets instantiations of its own (conv_fwd_x6_kernel passes 1) -- sharing one between families moved
+// the register allocation of conv_fwd_kernel<1, 32, false, true> (117 -> 118 VGPRs, two more loads); the code is the same.
+template <int TM, int TN, int NTHR, bool RES, int TAG = 0>
 __device__ __forceinline__ void infer_rows(const float* __restrict__ stage, const ConvArgs& a, int m0, int n, int cq, int rg,
                                            const float4 bv) {
     constexpr int BN = 64 * TN, LDS_LD = BN + 4, CQ = BN / 4, RG = NTHR / CQ, RPT = 128 / RG;
@@ -277,7 +279,7 @@ __device__ __forceinline__ void infer_rows(const float* __restrict__ stage, cons
 // EPI: the backward-data epilogue of diga_bwd_epilogue_t (its own instantiation of every kernel, so that the plain
 // kernels keep their register budget: inlined into the 256-register kernels the extra row buffers spilled).
 // INF: the inference epilogue of diga_infer_epilogue_t (infer_rows), likewise an instantiation of its own.
-template <int TM, int TN, bool EPI, int NTHR, bool INF>
+template <int TM, int TN, bool EPI, int NTHR, bool INF, int TAG>
 __device__ __forceinline__ void drain_stage(const float* stage_in, const ConvArgs& a, int m0, int n0, int t, int tile_m,
                                             bool active) {
     float* stage = const_cast<float*>(stage_in);
@@ -296,8 +298,8 @@ __device__ __forceinline__ void drain_stage(const float* stage_in, const ConvArg
         bv.w = n + 3 < a.Cout ? a.bias[n + 3] : 0.f;
     }
     if constexpr (INF) {
-        if (a.i_res != nullptr) infer_rows<TM, TN, NTHR, true>(stage, a, m0, n, cq, rg, bv);      // (uniform over the grid)
-        else infer_rows<TM, TN, NTHR, false>(stage, a, m0, n, cq, rg, bv);
+        if (a.i_res != nullptr) infer_rows<TM, TN, NTHR, true, TAG>(stage, a, m0, n, cq, rg, bv);      // (uniform over the grid)
+        else infer_rows<TM, TN, NTHR, false, TAG>(stage, a, m0, n, cq, rg, bv);
         return;
     }
     const float4 s0 = *reinterpret_cast<const float4*>(stage + cq * 4);       // tile row 0 (always a valid row)

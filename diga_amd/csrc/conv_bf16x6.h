@@ -145,8 +145,13 @@ __global__ __launch_bounds__(256) void split_image3_batched_kernel(const float* 
 // tiles each and row tile tile_m takes its weight image from batch tile_m / a.wb_tiles (a.wb_stride BYTES between the images; the
 // fp32 kernels use the two fields the same way, in floats).  Rows per batch are a multiple of 256, so no tile straddles two
 // batches; rows, slots, swizzle, ring, K-step order, MFMA waves and drain_stage are the un-batched kernel's -- so are a tile's bits.
-template <int TN, bool EPI = false, bool LS = false, bool WB = false>
+//
+// INF (the `_infer` entry points): the staged tile leaves through the inference epilogue of diga_infer_epilogue_t (drain_stage's INF
+// form, infer_rows; TAG = 1: this family's own instantiations of it) -- an instantiation of its own, so the others keep their registers.  Nothing before the drain reads it: the
+// accumulator that reaches the stage is the plain kernel's, bit for bit.
+template <int TN, bool EPI = false, bool LS = false, bool WB = false, bool INF = false>
 __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
+    static_assert(!(INF && (EPI || WB)), "the inference epilogue comes with the plain pointwise forward");
     constexpr int BM = 256, BN = 64 * TN, NT = 2 * TN, MT = 4;
     constexpr int A_PLANE = BM * 64, B_PLANE = BN * 64, STAGE = 3 * A_PLANE + 3 * B_PLANE;
     extern __shared__ __align__(16) unsigned char smem_b[];
@@ -329,7 +334,8 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
             for (int e = 0; e < 4; ++e)
                 stage[((wm & 1) * 64 + i * 16 + (lane >> 4) * 4 + e) * LDS_LD + wn * 32 * TN + j * 16 + (lane & 15)] = acc[i][j][e];
     __syncthreads();
-    drain_stage<2, TN, EPI>(stage, a, m0 + h * 128, n0, t, tile_m * 2 + h, m0 + h * 128 < a.M);
+    if constexpr (INF) drain_stage<2, TN, false, 256, true, 1>(stage, a, m0 + h * 128, n0, t, tile_m * 2 + h, m0 + h * 128 < a.M);
+    else drain_stage<2, TN, EPI>(stage, a, m0 + h * 128, n0, t, tile_m * 2 + h, m0 + h * 128 < a.M);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -601,11 +607,14 @@ extern "C" int diga_split_bf16x6_image(const float* w, void* img, int64_t K, int
     return launch_status("diga_split_bf16x6_image");
 }
 
-// in_ld < 0: `in_triplet` is a triplet image (the pass form); else it is the fp32 tensor with that row pitch (the loader form)
+// in_ld < 0: `in_triplet` is a triplet image (the pass form); else it is the fp32 tensor with that row pitch (the loader form).
+// inf: the inference epilogue (the `_infer` entry points; forward without statistics and without a backward epilogue), checked by
+// set_infer_epilogue -- the rules of diga_conv2d_nhwc_f32_infer -- before anything is launched.
 static int conv2d_bf16x6_impl(const void* in_triplet, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N, int64_t Hi,
                               int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
                               int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
-                              float* stats_partial, int prof_tag, void* stream, const diga_bwd_epilogue_t* epi) {
+                              float* stats_partial, int prof_tag, void* stream, const diga_bwd_epilogue_t* epi,
+                              const diga_infer_epilogue_t* inf = nullptr) {
     DIGA_REQUIRE(in_triplet && wgt_img && out, DIGA_EINVAL, "conv2d_bf16x6: null pointer");
     DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && Cout > 0, DIGA_EINVAL, "conv2d_bf16x6: bad shape");
     DIGA_REQUIRE(R == 1 && S == 1 && stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv2d_bf16x6: pointwise (1x1) convolutions only");
@@ -631,8 +640,12 @@ static int conv2d_bf16x6_impl(const void* in_triplet, int64_t in_ld, const void*
     a.tiles_n = (int)ceil_div(Cout, 64 * tn);
     set_options(a, nullptr);
     {
-        const int rc = set_bwd_epilogue(a, epi, "conv2d_bf16x6");
+        int rc = set_bwd_epilogue(a, epi, "conv2d_bf16x6");
         if (rc) return rc;
+        rc = set_infer_epilogue(a, inf, "conv2d_bf16x6_infer");
+        if (rc) return rc;
+        DIGA_REQUIRE(!inf || (!epi && prof_tag != DIGA_PROF_CONV_BWD_DATA), DIGA_EINVAL,
+                     "conv2d_bf16x6_infer: the inference epilogue comes with the forward (no backward epilogue)");
     }
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD, st,
@@ -640,6 +653,16 @@ static int conv2d_bf16x6_impl(const void* in_triplet, int64_t in_ld, const void*
     const size_t ring = (size_t)2 * (3 * 256 * 64 + 3 * 64 * tn * 64);
     const size_t stg = (size_t)2 * 128 * (64 * tn + 4) * sizeof(float);
     const size_t sh = ring > stg ? ring : stg;
+    if (inf != nullptr) {
+        if (f32in) {
+            if (tn == 2) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true, false, true>), 768, sh);
+            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, true, false, true>), 768, sh);
+            return launch_status("diga_infer_conv2d_nhwc_bf16x6_f32in");
+        }
+        if (tn == 2) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, false, false, true>), 768, sh);
+        else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, false, false, true>), 768, sh);
+        return launch_status("diga_infer_conv2d_nhwc_bf16x6");
+    }
     if (f32in) {
         if (tn == 2) {
             if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, true, true>), 768, sh);
@@ -696,6 +719,28 @@ extern "C" int diga_conv2d_nhwc_bf16x6_f32in_epi(const float* in, int64_t in_ld,
     DIGA_REQUIRE(in_ld >= 0, DIGA_EINVAL, "conv2d_bf16x6_f32in_epi: in_ld must be at least Cin and a multiple of 4");
     return conv2d_bf16x6_impl(in, in_ld, wgt_img, nullptr, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
                               off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi);
+}
+
+// The pointwise forward with the inference epilogue (include/diga_hip.h, diga_infer_epilogue_t): conv_fwd_x6_kernel<TN, ..., INF>.
+extern "C" int diga_infer_conv2d_nhwc_bf16x6(const void* in_triplet, const void* wgt_img, const float* bias, float* out, int64_t N,
+                                             int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
+                                             int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
+                                             int64_t off_dy, int64_t off_dx, const diga_infer_epilogue_t* infer, int prof_tag,
+                                             void* stream) {
+    DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_bf16x6_infer: null epilogue descriptor");
+    return conv2d_bf16x6_impl(in_triplet, -1, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
+                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, nullptr, infer);
+}
+
+extern "C" int diga_infer_conv2d_nhwc_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out,
+                                                   int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout,
+                                                   int64_t out_ld, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
+                                                   int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
+                                                   const diga_infer_epilogue_t* infer, int prof_tag, void* stream) {
+    DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_bf16x6_f32in_infer: null epilogue descriptor");
+    DIGA_REQUIRE(in_ld >= 0, DIGA_EINVAL, "conv2d_bf16x6_f32in_infer: in_ld must be at least Cin and a multiple of 4");
+    return conv2d_bf16x6_impl(in, in_ld, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
+                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, nullptr, infer);
 }
 
 namespace {

@@ -1123,9 +1123,9 @@ static int winograd_impl(const float* in, const float* wgt, const float* bias, f
                          void* stream, float* v_keep = nullptr, float* stats = nullptr,
                          const void* tile_table = nullptr, int reflect = 0, const diga_infer_epilogue_t* inf = nullptr,
                          bool x6 = false) {
-    // x6 (diga_conv2d_winograd_bf16x6): the products on the bf16x6 GEMM; tile table, transforms, v_keep, statistics and the backward
-    // epilogue as below.  Not with the inference epilogue or reflection padding (those stay exact fp32).
-    DIGA_REQUIRE(!x6 || (!inf && !reflect), DIGA_EINVAL, "conv2d_winograd_bf16x6: no inference epilogue / reflection padding");
+    // x6 (diga_conv2d_winograd_bf16x6 / _infer): the products on the bf16x6 GEMM; tile table, transforms, v_keep, statistics, the backward
+    // epilogue and the inference epilogue as below.  Not with reflection padding (that form stays exact fp32).
+    DIGA_REQUIRE(!x6 || !reflect, DIGA_EINVAL, "conv2d_winograd_bf16x6: no reflection padding");
     DIGA_REQUIRE(!inf || ((tile == 4 || tile == 6) && !flip && !epi && !stats && !reflect), DIGA_EINVAL,
                  "conv2d_winograd_infer: the inference epilogue comes with the plain forward of 4x4 / 6x6 tiles");
     DIGA_REQUIRE(!reflect || (tile != 2 && !flip && !epi && dilation < H && dilation < W), DIGA_EINVAL,
@@ -1388,6 +1388,22 @@ extern "C" int diga_conv2d_winograd_bf16x6(const float* in, const float* wgt, co
     }
     return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, flip, e, prof_tag,
                          stream, v_keep, stats_partial, tile_table, 0, nullptr, true);
+}
+
+// diga_conv2d_winograd_f32_infer with the products on the bf16x6 GEMM: the batched GEMM of diga_conv2d_winograd_bf16x6, then the
+// output transform with the inference epilogue (launch_output_infer_m)
+extern "C" int diga_infer_conv2d_winograd_bf16x6(const float* in, const float* wgt, const float* bias, float* out, void* workspace,
+                                                 size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld,
+                                                 int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile,
+                                                 const diga_infer_epilogue_t* infer, const void* tile_table, int prof_tag, void* stream) {
+    DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_winograd_bf16x6_infer: null epilogue descriptor");
+    DIGA_REQUIRE(infer->ab != nullptr && aligned16(infer->ab), DIGA_EINVAL,
+                 "conv2d_winograd_bf16x6_infer: the inference epilogue needs 16-byte aligned coefficients ab [2][Cout]");
+    DIGA_REQUIRE(!infer->residual || (aligned16(infer->residual) && infer->residual_ld >= Cout && infer->residual_ld % 4 == 0 &&
+                                      infer->residual != out),
+                 DIGA_EINVAL, "conv2d_winograd_bf16x6_infer: bad residual (16-byte aligned, residual_ld %% 4 == 0 and >= Cout, not the output)");
+    return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, 0, nullptr,
+                         prof_tag, stream, nullptr, nullptr, tile_table, 0, infer, true);
 }
 
 extern "C" size_t diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout,

@@ -16,7 +16,8 @@ from diga_amd import _lib, config
 
 def _fold_ctx(fold_bn):
     """fold_bn of the offline passes: None follows the active configuration (config.fold_eval_bn); True / False run the body with the
-    eval-mode BatchNorms of the trunk folded into the conv epilogues / as modules of their own (bit-identical results)."""
+    eval-mode BatchNorms of the trunk folded into the conv epilogues / as modules of their own (bit-identical results).  Which sites
+    fold under conv_math = 2 is config.fold_eval_bn_x6's business (read from the active configuration as it is)."""
     return contextlib.nullcontext() if fold_bn is None else config.override(fold_eval_bn=bool(fold_bn))
 
 

@@ -129,7 +129,8 @@ flop_log = None
 # a test or tool sets this to a dict to learn which kernels ran: (pass, arithmetic) -> launches, pass in "fwd" / "dgrad" / "wgrad",
 # arithmetic in "f32" / "bf16x3" / "bf16x6" / "bf16x6/ls" (bf16x6 with the operands split by the loader waves, config.x6_split = "loader") /
 # "winograd" / "winograd/x6" (the Winograd path with its products on bf16x6, config.x6_winograd); "f32+bn" / "winograd+bn": a forward with the eval-mode BatchNorm behind it
-# folded into its epilogue (config.fold_eval_bn)
+# folded into its epilogue (config.fold_eval_bn); "bf16x6+bn" / "bf16x6/ls+bn" / "winograd/x6+bn": the same on the bf16x6 kernels
+# (config.fold_eval_bn_x6)
 path_log = None
 
 
@@ -284,14 +285,16 @@ def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, sta
     if copt and (stats is not None or epi):
         raise RuntimeError("DigaConv2d: folded padding / upsampling / activation cannot be combined with BN statistics or a backward epilogue")
     math = _layer_math(r, s, cin, x6_ok and not copt)
-    if infer and (math != 0 or copt or stats is not None or epi or tag != _TAG_FWD or k % 4 != 0):
-        raise RuntimeError("DigaConv2d: no kernel with the inference epilogue for this call (exact-fp32 forward without statistics, "
-                           "Cout % 4 == 0; check infer_kernel / folds_eval_bn first)")
+    fold_x6 = infer and config.active().fold_eval_bn_x6        # the bf16x6 kernels' inference epilogue is a switch of its own
+    if infer and ((math != 0 and not (math == 2 and fold_x6)) or copt or stats is not None or epi or tag != _TAG_FWD or k % 4 != 0):
+        raise RuntimeError("DigaConv2d: no kernel with the inference epilogue for this call (exact-fp32 forward -- or, with "
+                           "config.fold_eval_bn_x6, bf16x6 -- without statistics, Cout % 4 == 0; check infer_kernel / folds_eval_bn first)")
     variant = "infer" if infer else "epi" if epi else "opts" if copt else ""
     if math == 2:
         # bf16x6: the weights as a pre-split image; the activations read as fp32 and split by the loader waves, or pre-split into
         # three bf16 planes and copied global -> LDS by LDS-DMA (csrc/conv_bf16x6.h)
-        return _Path("x6ls", variant, 2, "bf16x6/ls") if _x6_loader() else _Path("x6", variant, 2, "bf16x6")
+        bn = "+bn" if infer else ""
+        return _Path("x6ls", variant, 2, "bf16x6/ls" + bn) if _x6_loader() else _Path("x6", variant, 2, "bf16x6" + bn)
     if math == 1 and _use_twin(cin, k, r * s, shared) and n * hi * wi * cin * 4 < (1 << 40):
         # split-bf16 arithmetic without register staging: both operands pre-split, copied global -> LDS by LDS-DMA
         return _Path("twin", variant, 1, "bf16x3", flops=False)
@@ -314,10 +317,11 @@ def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, sta
             raise RuntimeError("DigaConv2d: Winograd statistics come with the forward output transform of 4x4 / 6x6 tiles")
         if infer and tile < 4:
             raise RuntimeError("DigaConv2d: the inference epilogue comes with Winograd tiles of 4x4 / 6x6 (winograd_max_tile = 2)")
-        x6w = not infer and _wino_x6()                 # (the inference epilogue stays exact fp32)
+        x6w = (not infer or fold_x6) and _wino_x6()    # (without config.fold_eval_bn_x6 the inference epilogue stays exact fp32)
         if keep and variant == "" and doff[0] > 0 and k % 256 == 0 and cin % 128 == 0 and config.active().winograd_keep_v:
             variant = "keep"
-        return _Path("winograd", variant, 0, "winograd+bn" if infer else "winograd/x6" if x6w else "winograd", tile, ratio, x6w)
+        arith = ("winograd/x6+bn" if x6w else "winograd+bn") if infer else "winograd/x6" if x6w else "winograd"
+        return _Path("winograd", variant, 0, arith, tile, ratio, x6w)
     return _Path("f32", variant, 0, "f32+bn" if infer else "f32")
 
 
@@ -359,9 +363,10 @@ def winograd_stats_plan(n, hi, wi, cin_padded, k, r, s, stride, padding, dilatio
 
 def infer_kernel(n, hi, wi, cin, k, r, s, stride, padding, dilation, ho, wo, pointwise_ok=True):
     """The forward kernel family with the inference epilogue (diga_infer_epilogue_t) a layer would run on under the active
-    configuration -- "f32+bn" (direct / LDS-DMA / persistent GEMM) or "winograd+bn" (4x4 / 6x6 tiles) -- or None where there is none:
-    a layer whose arithmetic is not exact fp32 (conv_math 1; pointwise layers in mode 2), Cout % 4 != 0, Winograd capped at 2x2 tiles.
-    cin: the padded input channel count."""
+    configuration -- "f32+bn" (direct / LDS-DMA / persistent GEMM) or "winograd+bn" (4x4 / 6x6 tiles); with config.fold_eval_bn_x6
+    under conv_math 2 also "bf16x6+bn" / "bf16x6/ls+bn" (pointwise layers, by config.x6_split) and "winograd/x6+bn" (config.x6_winograd)
+    -- or None where there is none: conv_math 1; pointwise layers in mode 2 without fold_eval_bn_x6; Cout % 4 != 0; Winograd capped at
+    2x2 tiles.  cin: the padded input channel count."""
     try:
         return _plan(n, hi, wi, cin, k, r, s, stride, (-padding[0], -padding[1]), tuple(dilation), ho, wo, infer=True,
                      x6_ok=pointwise_ok).arith
@@ -403,10 +408,11 @@ def _make_split(src, ld, rows, ch, triplet):
 # (family, variant) -> entry point.  The implicit-GEMM families share one argument layout (_conv_launch) up to: the leading operand
 # pointers (_operands), an input pitch (the two families that read fp32 activations through the ordinary loads), a bias slot (all
 # but `_epi`) and the one trailing pointer (statistics, or the variant's struct).  The Winograd entry points have their own layout
-# (_winograd_launch); with the products on bf16x6 one entry point serves every variant.
+# (_winograd_launch); with the products on bf16x6 one entry point serves every variant but "infer", which has its own.
 _ENTRY = {
     ("x6ls", ""): "diga_conv2d_nhwc_bf16x6_f32in", ("x6ls", "epi"): "diga_conv2d_nhwc_bf16x6_f32in_epi",
-    ("x6", ""): "diga_conv2d_nhwc_bf16x6", ("x6", "epi"): "diga_conv2d_nhwc_bf16x6_epi",
+    ("x6ls", "infer"): "diga_infer_conv2d_nhwc_bf16x6_f32in",
+    ("x6", ""): "diga_conv2d_nhwc_bf16x6", ("x6", "epi"): "diga_conv2d_nhwc_bf16x6_epi", ("x6", "infer"): "diga_infer_conv2d_nhwc_bf16x6",
     ("twin", ""): "diga_conv2d_nhwc_twin", ("twin", "epi"): "diga_conv2d_nhwc_twin_epi", ("twin", "opts"): "diga_conv2d_nhwc_twin_opts",
     ("bf16x3", ""): "diga_conv2d_nhwc_bf16x3", ("bf16x3", "epi"): "diga_conv2d_nhwc_bf16x3_epi",
     ("bf16x3", "opts"): "diga_conv2d_nhwc_bf16x3_opts",
@@ -417,6 +423,7 @@ _ENTRY = {
     ("winograd_reflect", "opts"): "diga_conv2d_winograd_f32_opts",
 }
 _WINOGRAD_X6 = "diga_conv2d_winograd_bf16x6"
+_WINOGRAD_X6_INFER = "diga_infer_conv2d_winograd_bf16x6"
 
 
 def _operands(path, x, w_krsc, twin_box):
@@ -468,6 +475,9 @@ def _winograd_launch(path, x, w_krsc, bias, out, d, flip, tag, stats, struct, ke
             variant = ""
     lead = [_lib.ptr(x), _lib.ptr(w_krsc)] + ([] if variant == "epi" and not path.x6w else [_lib.ptr(bias)]) + [_lib.ptr(out)]
     shape = (_lib.ptr(ws), ws.numel(), n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile)
+    if path.x6w and variant == "infer":
+        _lib.call(_WINOGRAD_X6_INFER, *lead, *shape, struct, _lib.ptr(tab), tag, _lib.stream())
+        return
     if path.x6w:
         # one entry point for the plain forward / backward-data, the forward with statistics, the forward that keeps V and
         # backward-data with the epilogue
@@ -947,8 +957,8 @@ class DigaConv2d(nn.Conv2d):
     def folds_eval_bn(self, x, bn, residual=None):
         """True when this conv on `x` may run as conv + eval-mode BatchNorm `bn` (+ residual, + ReLU) in ONE kernel
         (forward(..., infer=)): config.fold_eval_bn is on; nothing here is differentiated (grad mode off, or neither the input, the
-        residual nor this conv's parameters require grad); `bn` is in eval mode with running statistics; the layer's arithmetic is
-        exact fp32 on a kernel that has the inference epilogue (infer_kernel); Cout % 4 == 0; and neither module carries forward or
+        residual nor this conv's parameters require grad); `bn` is in eval mode with running statistics; the layer runs on a kernel
+        that has the inference epilogue (infer_kernel: exact fp32, or bf16x6 with config.fold_eval_bn_x6); Cout % 4 == 0; and neither module carries forward or
         forward-pre hooks (a hook would see a tensor that no longer exists).  Bit-identical to the two-module form either way."""
         if not config.active().fold_eval_bn:
             return False

@@ -4,6 +4,11 @@
 512 x 1024 half through diga_amd.evaluate.evaluate_two_scale.
 
     python tools/bench_eval.py [--pairs 3] [--images 10] [--warmup 2] [--height 1024] [--width 2048] [--families]
+                               [--math f32|bf16x3|bf16x6] [--x6-split pass|loader] [--x6-winograd] [--fold-x6]
+
+Without the last four the run is the active configuration's (its defaults come from the environment, as everywhere).  --math,
+--x6-split and --x6-winograd set the convolution arithmetic of BOTH forms; --fold-x6 (config.fold_eval_bn_x6) lets the fold reach the
+bf16x6 kernels under --math bf16x6, where without it only the stem and the 3x3 layers fold.
 
 After warm-up of both forms, `--pairs` times: `--images` calls with the fold off, then `--images` calls with it on, each group
 between two HIP events (the whole call: resize, both forward passes, the fused argmax / confusion kernel).  Prints ms per
@@ -19,6 +24,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from diga_amd import config  # noqa: E402
 from diga_amd import evaluate as ev  # noqa: E402
 from diga_amd.model import conv as dc  # noqa: E402
 from diga_amd.model import seg_model_noaux as sm  # noqa: E402
@@ -36,10 +42,32 @@ def main():
     ap.add_argument("--height", type=int, default=1024)
     ap.add_argument("--width", type=int, default=2048)
     ap.add_argument("--families", action="store_true", help="also time one layer per kernel family, folded against conv + BatchNorm")
+    ap.add_argument("--math", choices=["f32", "bf16x3", "bf16x6"], default=None, help="conv arithmetic of both forms (default: the active configuration's)")
+    ap.add_argument("--x6-split", choices=["pass", "loader"], default=None, help="bf16x6 operand form (config.x6_split)")
+    ap.add_argument("--x6-winograd", action="store_true", help="bf16x6 for the Winograd-domain GEMMs (config.x6_winograd)")
+    ap.add_argument("--fold-x6", action="store_true", help="the fold inside the bf16x6 kernels as well (config.fold_eval_bn_x6)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_eval.py measures on the GPU; none is visible")
+    fields = {}
+    if a.math is not None:
+        fields["conv_math"] = {"f32": 0, "bf16x3": 1, "bf16x6": 2}[a.math]
+    if a.x6_split is not None:
+        fields["x6_split"] = a.x6_split
+    if a.x6_winograd:
+        fields["x6_winograd"] = True
+    if a.fold_x6:
+        fields["fold_eval_bn_x6"] = True
+    with config.override(**fields):
+        run(a)
+
+
+def run(a):
     dev = "cuda"
+    cfg = config.active()
+    math = ("fp32", "bf16x3", "bf16x6")[cfg.conv_math]
+    if cfg.conv_math == 2:
+        math += f" ({cfg.x6_split}{', x6_winograd' if cfg.x6_winograd else ''}{', fold_eval_bn_x6' if cfg.fold_eval_bn_x6 else ''})"
     m = SegModel(arch=sm.RESNET101)
     m.load_state_dict(detweights.state_dict(od.RESNET101))
     m = m.to(dev).eval()
@@ -64,7 +92,7 @@ def main():
         logs[fold], dc.path_log = dc.path_log, None
         peaks[fold] = (torch.cuda.max_memory_allocated() - base) / 2 ** 30
     same = torch.equal(preds[False], preds[True])
-    print(f"geometry 1 x 3 x {a.height} x {a.width} + half, ResNet-101, eval, fp32; predictions identical fold on/off: {same}")
+    print(f"geometry 1 x 3 x {a.height} x {a.width} + half, ResNet-101, eval, {math}; predictions identical fold on/off: {same}")
     for fold in (False, True):
         fwd = {f"{k[1]}": v for k, v in sorted(logs[fold].items()) if k[0] == "fwd"}
         print(f"fold {'on ' if fold else 'off'}: conv launches per validation image {fwd} (sum {sum(fwd.values())}); "
@@ -105,15 +133,26 @@ FAMILIES = [
     ("128 x 64 tiles, 3x3         (l1.conv2 64->64)   ", 64, 64, 3, 1, (257, 513), False),
     ("Winograd output transform   (l3.conv2 256, d 2) ", 256, 256, 3, 2, (129, 257), False),
 ]
+# with config.fold_eval_bn_x6 under conv_math 2: one pointwise layer per column-tile width (TN) of conv_fwd_x6_kernel, each in both
+# operand forms (x6_split)
+X6_FAMILIES = [
+    ("bf16x6 TN 1                 (l1.conv1 256->64)  ", 256, 64, 1, 1, (257, 513), False),
+    ("bf16x6 TN 2                 (l3.conv1 1024->256)", 1024, 256, 1, 1, (129, 257), False),
+    ("bf16x6 TN 2 + residual      (l3.conv3 256->1024)", 256, 1024, 1, 1, (129, 257), True),
+]
 
 
 def families(a, dev):
     """conv + diga_bn_fwd(eval) against the one folded launch, per kernel family: what decides a family's eligibility."""
-    from diga_amd import config
     from diga_amd.model import norm as dn
     g = torch.Generator().manual_seed(4321)
     print("per kernel family, ms per layer call (two-module form / folded), warm, same tensors:")
-    for name, cin, cout, k, d, (h, w), with_res in FAMILIES:
+    cases = [(f, {}) for f in FAMILIES]
+    if config.active().conv_math == 2:
+        print("  (conv_math 2: the pointwise rows run on bf16x6 in the active operand form; their labels name the fp32 kernels of mode 0)")
+    if config.active().conv_math == 2 and config.active().fold_eval_bn_x6:
+        cases += [((f"{f[0][:-1]} {split:6s}",) + f[1:], {"x6_split": split}) for f in X6_FAMILIES for split in ("pass", "loader")]
+    for (name, cin, cout, k, d, (h, w), with_res), extra in cases:
         conv = dc.DigaConv2d(cin, cout, k, padding=d * (k // 2), dilation=d, bias=False).to(dev)
         bn = dn.DigaBatchNorm2d(cout).to(dev).eval()
         for p in bn.parameters():
@@ -125,7 +164,7 @@ def families(a, dev):
         res = torch.randn((1, cout, h, w), generator=g).to(dev).contiguous(memory_format=torch.channels_last) if with_res else None
 
         def run(fold):
-            with torch.no_grad(), config.override(fold_eval_bn=fold):
+            with torch.no_grad(), config.override(fold_eval_bn=fold, **extra):
                 if fold:
                     assert conv.folds_eval_bn(x, bn, residual=res)
                     return conv(x, infer=(bn, res, True))
