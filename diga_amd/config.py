@@ -45,6 +45,7 @@ class StepConfig:
     conv_math: int = 0                   # 0 exact fp32 (matrix cores, Winograd for stride-1 3x3), 1 split bf16 (three bf16 MFMAs per product), 2 bf16x6 (pointwise layers on three bf16 planes, fp32-equivalent; the rest as 0)
     x6_split: str = "pass"               # bf16x6 operands: "pass" split by an elementwise pass into triplet buffers, "loader" split by the GEMMs' loader waves straight from the fp32 tensors (bit-identical; no triplet buffers, channel slices not copied)
     x6_winograd: bool = False            # conv_math 2 only: the Winograd-domain GEMMs of the stride-1 3x3 layers on bf16x6 as well (loader form, whatever x6_split says; the transforms stay fp32)
+    x6_taps: bool = False                # conv_math 2 only: every multi-tap convolution that would run on the direct fp32 kernels (Cin % 32 == 0, no folded options), and the stem's im2col GEMM, on bf16x6 as well (loader form, whatever x6_split says)
     winograd: bool = True
     winograd_ratio: float = 0.62
     winograd_default_max_tile: int = 6
@@ -89,6 +90,7 @@ class StepConfig:
         c.conv_math = {"bf16x3": 1, "1": 1, "bf16x6": 2, "2": 2}.get(e("DIGA_CONV_MATH", ""), 0)
         c.x6_split = e("DIGA_X6_SPLIT", c.x6_split)
         c.x6_winograd = _flag("DIGA_X6_WINOGRAD", c.x6_winograd)
+        c.x6_taps = _flag("DIGA_X6_TAPS", c.x6_taps)
         c.winograd = _flag("DIGA_CONV_WINOGRAD", c.winograd)
         c.winograd_ratio = float(e("DIGA_CONV_WINOGRAD_RATIO", c.winograd_ratio))
         c.winograd_default_max_tile = c.winograd_max_tile = int(e("DIGA_CONV_WINOGRAD_TILE", c.winograd_default_max_tile))
@@ -126,6 +128,8 @@ class StepConfig:
             raise ValueError(f"x6_split must be 'pass' or 'loader', not {self.x6_split!r}")
         if not isinstance(self.x6_winograd, bool):
             raise ValueError(f"x6_winograd must be a bool, not {self.x6_winograd!r}")
+        if not isinstance(self.x6_taps, bool):
+            raise ValueError(f"x6_taps must be a bool, not {self.x6_taps!r}")
         if not isinstance(self.fold_eval_bn, bool):
             raise ValueError(f"fold_eval_bn must be a bool, not {self.fold_eval_bn!r}")
         if not isinstance(self.fold_eval_bn_x6, bool):

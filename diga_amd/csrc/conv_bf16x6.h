@@ -149,9 +149,20 @@ __global__ __launch_bounds__(256) void split_image3_batched_kernel(const float* 
 // INF (the `_infer` entry points): the staged tile leaves through the inference epilogue of diga_infer_epilogue_t (drain_stage's INF
 // form, infer_rows; TAG = 1: this family's own instantiations of it) -- an instantiation of its own, so the others keep their registers.  Nothing before the drain reads it: the
 // accumulator that reaches the stage is the plain kernel's, bit for bit.
-template <int TN, bool EPI = false, bool LS = false, bool WB = false, bool INF = false>
+//
+// TAPS (the `diga_conv_taps_*` entry points; LS only): a convolution with R * S <= 64 taps at offsets (oy0 + r * ody, ox0 + q * odx),
+// any sign (backward-data negates them), any stride.  The K-steps are (live taps) x Cin / 32, tap-major -- the order of
+// split_image3_kernel's image (ks = tap * cchunks + cc), so an R x S layer runs the K-step sequence of the pointwise kernel on the
+// tap-major im2col rows [M][RS * Cin] of its input: same weight image bytes, same LDS bytes, same bits.  Taps that lie outside the
+// image for every row of the block's tile (live_taps: uniform over the block) are stepped over in the weight image: they would add
+// exact zeros.  The loader lanes keep rows, k-slot, swizzle, LDS slot and the issue / vmcnt(0) / split3x4 / ds_write_b128 /
+// lgkmcnt(0) / barrier schedule; per row they keep the image's first pixel and (y0, x0) = (ho * sy + oy0, wo * sx + ox0), per tap they
+// derive (y0 + r * ody, x0 + q * odx) and the pointer -- null outside the image: no load is issued, the planes written are zero.  The
+// MFMA waves learn the new K-step count and nothing else; drain_stage, the fold accumulator and the ring are untouched.
+template <int TN, bool EPI = false, bool LS = false, bool WB = false, bool INF = false, bool TAPS = false>
 __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
     static_assert(!(INF && (EPI || WB)), "the inference epilogue comes with the plain pointwise forward");
+    static_assert(!TAPS || (LS && !WB), "the tap walk lives in the loader-split form");
     constexpr int BM = 256, BN = 64 * TN, NT = 2 * TN, MT = 4;
     constexpr int A_PLANE = BM * 64, B_PLANE = BN * 64, STAGE = 3 * A_PLANE + 3 * B_PLANE;
     extern __shared__ __align__(16) unsigned char smem_b[];
@@ -160,9 +171,101 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
     const int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_n = wg % a.tiles_n, tile_m = wg / a.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const int ksteps = a.Cin / 32;
+    int ksteps_all = a.Cin / 32;
+    uint64_t live = 0;
+    if constexpr (TAPS) {
+        live = live_taps(a, m0, BM);                             // (never empty)
+        ksteps_all *= __builtin_popcountll(live);
+    }
+    const int ksteps = ksteps_all;
 
-    if constexpr (LS) {
+    if constexpr (TAPS) {
+      if (loader) {
+        const int lw = wv - 8;                                   // 0..3: A rows lw*64 + 16 j + (lane >> 2)
+        const int lrow = lane >> 2;
+        const int kslot = (lane & 3) ^ lds_swz(lrow);
+        const int HoWo = a.Ho * a.Wo, cchunks = a.Cin / 32;
+        int pix0[4], y0[4], x0[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int m = min(m0 + lw * 64 + 16 * j + lrow, a.M - 1);
+            const int img = m / HoWo, rem = m - img * HoWo;
+            const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
+            pix0[j] = img * a.Hi * a.Wi;
+            y0[j] = ho * a.sy + a.oy0;
+            x0[j] = wo * a.sx + a.ox0;
+        }
+        const float* pa[4];
+        uint64_t todo = live;
+        int l_tap = 0, l_cc = 0, issued = 0;
+        auto next_tap = [&]() {                                  // -> l_tap = the next live tap, pa = its pixels
+            l_tap = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int r = l_tap / a.S, q = l_tap - r * a.S;
+            const int dy = r * a.ody, dx = q * a.odx;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int iy = y0[j] + dy, ix = x0[j] + dx;
+                const bool ok = (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
+                pa[j] = ok ? a.in + ((int64_t)pix0[j] + (int64_t)iy * a.Wi + ix) * a.in_ld + kslot * 8 : nullptr;
+            }
+        };
+        const unsigned char* bimg = a.wgt_img + (int64_t)tile_n * ((int64_t)a.R * a.S * cchunks) * (3 * B_PLANE) + (lw * 3 * TN) * 1024 + lane * 16;
+        float4 v[4][2];
+        auto issue = [&](int buf) {                              // global loads of the next K-step into registers + its weight DMA
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (pa[j] != nullptr) {
+                    v[j][0] = *reinterpret_cast<const float4*>(pa[j] + l_cc * 32);
+                    v[j][1] = *reinterpret_cast<const float4*>(pa[j] + l_cc * 32 + 4);
+                }
+            }
+            const unsigned char* bsrc = bimg + (int64_t)(l_tap * cchunks + l_cc) * (3 * B_PLANE);
+            unsigned char* bdst = smem_b + buf * STAGE + 3 * A_PLANE + (lw * 3 * TN) * 1024;
+#pragma unroll
+            for (int c = 0; c < 3 * TN; ++c) DIGA_LDS_DMA16(bsrc + c * 1024, bdst + c * 1024);
+        };
+        auto write = [&](int buf) {                              // split + three ds_write_b128 per row, wait for them, step on
+            unsigned char* stage = smem_b + buf * STAGE;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // a pixel outside the image: zero planes
+                if (pa[j] != nullptr) {
+                    uint2 a0, a1, a2, b0, b1, b2;
+                    split3x4(v[j][0], a0, a1, a2);
+                    split3x4(v[j][1], b0, b1, b2);
+                    q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
+                    q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
+                    q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
+                }
+                unsigned char* dst = stage + (lw * 64 + 16 * j) * 64 + lane * 16;
+                *reinterpret_cast<uint4*>(dst) = q0;
+                *reinterpret_cast<uint4*>(dst + A_PLANE) = q1;
+                *reinterpret_cast<uint4*>(dst + 2 * A_PLANE) = q2;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            ++issued;
+            if (++l_cc == cchunks) {                             // (pa changes only here, behind the writes that read it)
+                l_cc = 0;
+                if (issued < ksteps) next_tap();
+            }
+        };
+        next_tap();
+        issue(0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        write(0);
+        __builtin_amdgcn_s_barrier();                            // stage 0 has landed
+        for (int ks = 0; ks < ksteps; ++ks) {
+            if (ks + 1 < ksteps) {                               // (its stage was read by step ks - 1: behind the last barrier)
+                issue((ks + 1) & 1);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                write((ks + 1) & 1);
+            }
+            __builtin_amdgcn_s_barrier();
+        }
+        return;
+      }
+    } else if constexpr (LS) {
       if (loader) {
         const int lw = wv - 8;                                   // 0..3: A rows lw*64 + 16 j + (lane >> 2)
         const int lrow = lane >> 2;
@@ -614,10 +717,23 @@ static int conv2d_bf16x6_impl(const void* in_triplet, int64_t in_ld, const void*
                               int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
                               int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
                               float* stats_partial, int prof_tag, void* stream, const diga_bwd_epilogue_t* epi,
-                              const diga_infer_epilogue_t* inf = nullptr) {
+                              const diga_infer_epilogue_t* inf = nullptr, bool taps = false) {
     DIGA_REQUIRE(in_triplet && wgt_img && out, DIGA_EINVAL, "conv2d_bf16x6: null pointer");
     DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && Cout > 0, DIGA_EINVAL, "conv2d_bf16x6: bad shape");
-    DIGA_REQUIRE(R == 1 && S == 1 && stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv2d_bf16x6: pointwise (1x1) convolutions only");
+    if (taps) {
+        // the `diga_conv_taps_*` entry points (loader form only): up to 64 taps (live_taps' mask), every coordinate the loader
+        // derives -- (Ho - 1) * stride + offset + (R - 1) * step -- within 32 bits
+        DIGA_REQUIRE(in_ld >= 0, DIGA_EINVAL, "conv_taps_bf16x6: in_ld must be at least Cin and a multiple of 4");
+        DIGA_REQUIRE(R >= 1 && S >= 1 && R <= 64 && S <= 64 && R * S <= 64, DIGA_EINVAL, "conv_taps_bf16x6: 1 <= R * S <= 64 taps");
+        DIGA_REQUIRE(stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv_taps_bf16x6: strides must be positive");
+        const int64_t lim = 1ll << 30;
+        DIGA_REQUIRE(stride_y < lim && stride_x < lim && off_y0 > -lim && off_y0 < lim && off_x0 > -lim && off_x0 < lim && off_dy > -lim &&
+                     off_dy < lim && off_dx > -lim && off_dx < lim && Ho * stride_y < lim && Wo * stride_x < lim &&
+                     (off_dy < 0 ? -off_dy : off_dy) * R < lim && (off_dx < 0 ? -off_dx : off_dx) * S < lim,
+                     DIGA_EINVAL, "conv_taps_bf16x6: strides / offsets beyond 32-bit pixel coordinates");
+    } else {
+        DIGA_REQUIRE(R == 1 && S == 1 && stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv2d_bf16x6: pointwise (1x1) convolutions only");
+    }
     DIGA_REQUIRE(Cin > 0 && Cin % 32 == 0 && out_ld >= Cout, DIGA_EINVAL, "conv2d_bf16x6: Cin must be a multiple of 32");
     const bool f32in = in_ld >= 0;
     DIGA_REQUIRE(!f32in || (in_ld >= Cin && in_ld % 4 == 0 && in_ld < (1ll << 31)), DIGA_EINVAL,
@@ -631,13 +747,14 @@ static int conv2d_bf16x6_impl(const void* in_triplet, int64_t in_ld, const void*
     a.wgt_img = reinterpret_cast<const unsigned char*>(wgt_img); a.bias = bias; a.out = out; a.stats = stats_partial;
     a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.in_ld = f32in ? (int)in_ld : (int)Cin;
     a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.out_ld = (int)out_ld;
-    a.R = 1; a.S = 1; a.sy = (int)stride_y; a.sx = (int)stride_x;
+    a.R = (int)R; a.S = (int)S; a.sy = (int)stride_y; a.sx = (int)stride_x;
     a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
     a.M = (int)(N * Ho * Wo);
     a.tiles_m = (int)ceil_div(a.M, 256);
     a.all_inside = 0;
     const int tn = Cout > 64 ? 2 : 1;                 // (= image_bn(Cout) / 64: the weight image's tile)
     a.tiles_n = (int)ceil_div(Cout, 64 * tn);
+    DIGA_REQUIRE(!taps || (int64_t)a.tiles_m * a.tiles_n < (1ll << 31), DIGA_EINVAL, "conv_taps_bf16x6: too many tiles for one launch");
     set_options(a, nullptr);
     {
         int rc = set_bwd_epilogue(a, epi, "conv2d_bf16x6");
@@ -649,10 +766,25 @@ static int conv2d_bf16x6_impl(const void* in_triplet, int64_t in_ld, const void*
     }
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD, st,
-                   2.0 * (double)a.M * (double)Cout * (double)Cin);
+                   2.0 * (double)a.M * (double)Cout * (double)(R * S) * (double)Cin);
     const size_t ring = (size_t)2 * (3 * 256 * 64 + 3 * 64 * tn * 64);
     const size_t stg = (size_t)2 * 128 * (64 * tn + 4) * sizeof(float);
     const size_t sh = ring > stg ? ring : stg;
+    if (taps) {
+        if (inf != nullptr) {
+            if (tn == 2) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true, false, true, true>), 768, sh);
+            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, true, false, true, true>), 768, sh);
+            return launch_status("diga_infer_conv_taps_bf16x6_f32in");
+        }
+        if (tn == 2) {
+            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, true, true, false, false, true>), 768, sh);
+            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true, false, false, true>), 768, sh);
+        } else {
+            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, true, true, false, false, true>), 768, sh);
+            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, true, false, false, true>), 768, sh);
+        }
+        return launch_status("diga_conv_taps_bf16x6_f32in");
+    }
     if (inf != nullptr) {
         if (f32in) {
             if (tn == 2) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true, false, true>), 768, sh);
@@ -743,6 +875,36 @@ extern "C" int diga_infer_conv2d_nhwc_bf16x6_f32in(const float* in, int64_t in_l
                               off_x0, off_dy, off_dx, nullptr, prof_tag, stream, nullptr, infer);
 }
 
+// Multi-tap convolutions on the loader form (conv_fwd_x6_kernel<..., TAPS>): the argument lists of the pointwise `_f32in` entry
+// points with 1 <= R * S <= 64; R = S = 1 gives the pointwise kernel's bits.
+extern "C" int diga_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N,
+                                           int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
+                                           int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
+                                           int64_t off_dy, int64_t off_dx, float* stats_partial, int prof_tag, void* stream) {
+    return conv2d_bf16x6_impl(in, in_ld, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
+                              off_x0, off_dy, off_dx, stats_partial, prof_tag, stream, nullptr, nullptr, true);
+}
+
+extern "C" int diga_conv_taps_bf16x6_f32in_epi(const float* in, int64_t in_ld, const void* wgt_img, float* out, int64_t N, int64_t Hi,
+                                               int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R,
+                                               int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
+                                               int64_t off_dy, int64_t off_dx, const diga_bwd_epilogue_t* epi, int prof_tag,
+                                               void* stream) {
+    DIGA_REQUIRE(epi != nullptr, DIGA_EINVAL, "conv_taps_bf16x6_f32in_epi: null epilogue descriptor");
+    return conv2d_bf16x6_impl(in, in_ld, wgt_img, nullptr, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
+                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi, nullptr, true);
+}
+
+extern "C" int diga_infer_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out,
+                                                 int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout,
+                                                 int64_t out_ld, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
+                                                 int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
+                                                 const diga_infer_epilogue_t* infer, int prof_tag, void* stream) {
+    DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "infer_conv_taps_bf16x6_f32in: null epilogue descriptor");
+    return conv2d_bf16x6_impl(in, in_ld, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
+                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, nullptr, infer, true);
+}
+
 namespace {
 // 256 x 128 tiles at one block per CU: about two rounds of 256 blocks, at least 8 K-steps (256 pixels) per block.  Short pixel
 // ranges are also what keeps the weight gradient's error at the exact-fp32 kernels' level: the running sum of a range is
@@ -765,6 +927,15 @@ WgradPlan plan_wgrad_x6(int64_t M, int64_t Cout, int64_t Cin, int64_t RS = 1) {
     p.splits = (int)ceil_div(ksteps, p.steps_per_split);
     return p;
 }
+// shape rules of the multi-tap weight gradient (shared by the entry point's checks and its workspace query)
+bool taps_wgrad_shape_ok(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R, int64_t S) {
+    const int64_t lim = 1ll << 31;
+    if (N <= 0 || Ho <= 0 || Wo <= 0 || R < 1 || S < 1 || R > 64 || S > 64 || R * S > 64 || Cin <= 0 || Cin % 32 != 0 || Cin >= lim ||
+        Cout <= 0 || Cout % 8 != 0 || Cout >= lim || N >= lim || Ho >= lim || Wo >= lim || N * Ho >= lim || N * Ho * Wo >= lim)
+        return false;
+    const WgradPlan p = plan_wgrad_x6(N * Ho * Wo, Cout, Cin, R * S);
+    return ceil_div(Cout, 256) * ceil_div(Cin, 128) * R * S * p.splits < (1ll << 31);
+}
 }  // namespace
 
 extern "C" size_t diga_conv2d_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin,
@@ -777,18 +948,30 @@ extern "C" size_t diga_conv2d_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho
 static int conv2d_wgrad_bf16x6_impl(const void* dy_triplet, int64_t dy_ld, const void* x_triplet, int64_t x_ld, float* dw,
                                     void* workspace, size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin,
                                     int64_t Ho, int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
-                                    int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
+                                    int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream,
+                                    bool taps = false) {
     const bool f32in = dy_ld >= 0;
     DIGA_REQUIRE(dy_triplet && x_triplet && dw && workspace, DIGA_EINVAL, "conv2d_wgrad_bf16x6: null pointer");
     DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: bad shape");
-    DIGA_REQUIRE(R == 1 && S == 1 && stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: pointwise (1x1) convolutions only");
+    if (taps) {
+        // diga_conv_taps_wgrad_bf16x6_f32in: one block group per tap from the pixel table of all taps (conv_wgrad_x6_kernel<true>)
+        DIGA_REQUIRE(f32in && taps_wgrad_shape_ok(N, Ho, Wo, Cout, Cin, R, S) && stride_y > 0 && stride_x > 0, DIGA_EINVAL,
+                     "conv_taps_wgrad_bf16x6: 1 <= R * S <= 64, Cin %% 32, Cout %% 8, positive strides and a block count below 2^31 required");
+        const int64_t lim = 1ll << 30;
+        DIGA_REQUIRE(stride_y < lim && stride_x < lim && off_y0 > -lim && off_y0 < lim && off_x0 > -lim && off_x0 < lim && off_dy > -lim &&
+                     off_dy < lim && off_dx > -lim && off_dx < lim && Ho * stride_y < lim && Wo * stride_x < lim &&
+                     (off_dy < 0 ? -off_dy : off_dy) * R < lim && (off_dx < 0 ? -off_dx : off_dx) * S < lim,
+                     DIGA_EINVAL, "conv_taps_wgrad_bf16x6: strides / offsets beyond 32-bit pixel coordinates");
+    } else {
+        DIGA_REQUIRE(R == 1 && S == 1 && stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: pointwise (1x1) convolutions only");
+    }
     DIGA_REQUIRE(Cin > 0 && Cin % 8 == 0 && Cout > 0 && Cout % 8 == 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: channel counts must be multiples of 8");
     DIGA_REQUIRE(!f32in || (dy_ld >= Cout && dy_ld % 4 == 0 && x_ld >= Cin && x_ld % 4 == 0 && dy_ld < (1ll << 31) && x_ld < (1ll << 31)),
                  DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count and multiples of 4");
     DIGA_REQUIRE(aligned16(dy_triplet) && aligned16(x_triplet) && aligned16(dw) && aligned16(workspace), DIGA_EALIGN, "conv2d_wgrad_bf16x6: alignment");
     DIGA_REQUIRE(N * Hi * Wi < (1ll << 31) && N * Ho * Wo < (1ll << 31), DIGA_EINVAL, "conv2d_wgrad_bf16x6: too many pixels");
-    const int64_t RS = 1, M = N * Ho * Wo, M_pad = wgrad_mpad(M);
-    const WgradPlan p = plan_wgrad_x6(M, Cout, Cin);
+    const int64_t RS = taps ? R * S : 1, M = N * Ho * Wo, M_pad = wgrad_mpad(M);
+    const WgradPlan p = plan_wgrad_x6(M, Cout, Cin, RS);
     const size_t slab_bytes = wgrad_slab_bytes(p, Cout, Cin, RS);
     DIGA_REQUIRE(workspace_bytes >= slab_bytes + (size_t)RS * M_pad * sizeof(int) + 64, DIGA_EWORKSPACE, "conv2d_wgrad_bf16x6: workspace too small");
     WgradArgs a;
@@ -796,17 +979,17 @@ static int conv2d_wgrad_bf16x6_impl(const void* dy_triplet, int64_t dy_ld, const
     a.slab = p.splits > 1 ? (float*)workspace : dw;
     a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.x_ld = f32in ? (int)x_ld : (int)Cin;
     a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.dy_ld = f32in ? (int)dy_ld : (int)Cout;
-    a.R = 1; a.S = 1; a.sy = (int)stride_y; a.sx = (int)stride_x;
+    a.R = taps ? (int)R : 1; a.S = taps ? (int)S : 1; a.sy = (int)stride_y; a.sx = (int)stride_x;
     a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
     a.M = (int)M; a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.splits = p.splits; a.steps_per_split = p.steps_per_split;
     a.M_pad = (int)M_pad;
     hipStream_t st = (hipStream_t)stream;
-    ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)M * (double)Cout * (double)Cin);
+    ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)M * (double)Cout * (double)RS * (double)Cin);
     // (output pixel) -> input pixel table, -1 outside the image: in bounds for any stride / offset
     int* tab = reinterpret_cast<int*>(static_cast<char*>(workspace) + slab_bytes);
     float* zeros = reinterpret_cast<float*>(tab + RS * M_pad);
     hipLaunchKernelGGL(wgrad_pixtab_kernel, dim3((unsigned)ceil_div(M_pad, 256), (unsigned)RS), dim3(256), 0, st, tab, zeros, (int)M,
-                       (int)M_pad, (int)Ho, (int)Wo, (int)Hi, (int)Wi, 1, (int)stride_y, (int)stride_x, (int)off_y0, (int)off_x0,
+                       (int)M_pad, (int)Ho, (int)Wo, (int)Hi, (int)Wi, a.S, (int)stride_y, (int)stride_x, (int)off_y0, (int)off_x0,
                        (int)off_dy, (int)off_dx);
     a.ptab = tab;
     a.zeros = zeros;
@@ -824,7 +1007,7 @@ static int conv2d_wgrad_bf16x6_impl(const void* dy_triplet, int64_t dy_ld, const
         hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)workspace, dw, n4,
                            p.splits);
     }
-    return launch_status(f32in ? "diga_conv2d_wgrad_bf16x6_f32in" : "diga_conv2d_wgrad_bf16x6");
+    return launch_status(taps ? "diga_conv_taps_wgrad_bf16x6_f32in" : f32in ? "diga_conv2d_wgrad_bf16x6_f32in" : "diga_conv2d_wgrad_bf16x6");
 }
 
 extern "C" int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_triplet, float* dw, void* workspace,
@@ -842,6 +1025,24 @@ extern "C" int diga_conv2d_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, co
     DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
     return conv2d_wgrad_bf16x6_impl(dy, dy_ld, x, x_ld, dw, workspace, workspace_bytes, N, Hi, Wi, Cin, Ho, Wo, Cout, R, S, stride_y,
                                     stride_x, off_y0, off_x0, off_dy, off_dx, stream);
+}
+
+// The weight gradient of a multi-tap convolution on the loader form: diga_conv2d_wgrad_bf16x6_f32in's arguments with
+// 1 <= R * S <= 64, dw [Cout][R][S][Cin]; the split-K plan counts the taps (plan_wgrad_x6(M, Cout, Cin, R * S)).
+extern "C" size_t diga_conv_taps_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R,
+                                                              int64_t S) {
+    if (!taps_wgrad_shape_ok(N, Ho, Wo, Cout, Cin, R, S)) return 0;
+    const int64_t M = N * Ho * Wo, RS = R * S;
+    return wgrad_slab_bytes(plan_wgrad_x6(M, Cout, Cin, RS), Cout, Cin, RS) + (size_t)RS * wgrad_mpad(M) * sizeof(int) + 64;
+}
+
+extern "C" int diga_conv_taps_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
+                                                 size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
+                                                 int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
+                                                 int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
+    DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv_taps_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
+    return conv2d_wgrad_bf16x6_impl(dy, dy_ld, x, x_ld, dw, workspace, workspace_bytes, N, Hi, Wi, Cin, Ho, Wo, Cout, R, S, stride_y,
+                                    stride_x, off_y0, off_x0, off_dy, off_dx, stream, true);
 }
 
 // ---- the Winograd-domain GEMMs on bf16x6 (winograd.hip: diga_conv2d_winograd_bf16x6 / diga_conv2d_wgrad_winograd_bf16x6)

@@ -69,8 +69,23 @@ def _use_x6(cin, r, s):
     PADDED input channel count is a multiple of 32 -- any stride, any output channel count (the kernels clamp ragged channel tiles,
     the backward passes see channel counts padded to 32), with or without bias, BatchNorm statistics or a backward-data epilogue.
     Not eligible: multi-tap layers (Winograd / direct fp32), the stem's im2col GEMM (its backward has its own path) and calls with a
-    folded input map / activation (`opts`) -- the callers pass those as pointwise_ok=False to _layer_math."""
+    folded input map / activation (`opts`) -- the callers pass those as pointwise_ok=False to _layer_math.  (config.x6_taps, _x6_taps
+    below, is the opt-in that sends the multi-tap calls left on the direct fp32 kernels, and the stem, to bf16x6 too.)"""
     return r == 1 and s == 1 and cin % 32 == 0
+
+
+def _x6_taps():
+    """True when config.x6_taps is in force (conv_math = 2; both read per call): a multi-tap call that _plan / _wgrad_plan would leave
+    on the direct fp32 kernels runs on the multi-tap bf16x6 kernels instead (family "x6rs", the `diga_conv_taps_*` entry points), and
+    the stem's im2col GEMM on the pointwise ones ("x6ls") -- the loader form whatever x6_split says: fp32 tensors read in place, no
+    triplets.  Winograd keeps every call it takes."""
+    return _lib.get_conv_math() == 2 and config.active().x6_taps
+
+
+def _taps_ok(cin, r, s, copt):
+    """Eligibility of a call for the "x6rs" family: more than one tap (at most 64: the live-tap mask), padded Cin % 32 == 0, no folded
+    input map / activation."""
+    return 1 < r * s <= 64 and cin % 32 == 0 and not copt
 
 
 def _x6_loader():
@@ -130,7 +145,7 @@ flop_log = None
 # arithmetic in "f32" / "bf16x3" / "bf16x6" / "bf16x6/ls" (bf16x6 with the operands split by the loader waves, config.x6_split = "loader") /
 # "winograd" / "winograd/x6" (the Winograd path with its products on bf16x6, config.x6_winograd); "f32+bn" / "winograd+bn": a forward with the eval-mode BatchNorm behind it
 # folded into its epilogue (config.fold_eval_bn); "bf16x6+bn" / "bf16x6/ls+bn" / "winograd/x6+bn": the same on the bf16x6 kernels
-# (config.fold_eval_bn_x6)
+# (config.fold_eval_bn_x6); "bf16x6/taps" / "bf16x6/taps+bn": a multi-tap call on the bf16x6 kernels (config.x6_taps)
 path_log = None
 
 
@@ -260,7 +275,7 @@ class _Path(NamedTuple):
     """Which kernel ONE convolution call runs on.  _plan (forward / backward-data) and _wgrad_plan (weight gradient) decide it, once
     per call, from the call's geometry, the features it wants and the active configuration; everything else -- the launch, the
     statistics buffer DigaConv2d allocates, infer_kernel, winograd_stats_plan, what a forward saves for its backward -- reads it."""
-    family: str                # "x6ls" (bf16x6, operands split by the loader waves) / "x6" (bf16x6 on triplets) / "twin" / "bf16x3" /
+    family: str                # "x6ls" (bf16x6, operands split by the loader waves) / "x6" (bf16x6 on triplets) / "x6rs" (multi-tap bf16x6) / "twin" / "bf16x3" /
     #                            "winograd" / "winograd_reflect" (reflection padding folded into the input transform) / "f32"
     variant: str               # "" / "epi" (backward-data epilogue) / "opts" / "infer" / "keep" (Winograd forward that keeps V)
     math: int                  # the layer's arithmetic (_layer_math): the `math` argument the library is given
@@ -284,7 +299,8 @@ def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, sta
     copt = opts is not None and any(opts)
     if copt and (stats is not None or epi):
         raise RuntimeError("DigaConv2d: folded padding / upsampling / activation cannot be combined with BN statistics or a backward epilogue")
-    math = _layer_math(r, s, cin, x6_ok and not copt)
+    stem_x6 = not x6_ok and _x6_taps()                         # the stem's im2col GEMM: on bf16x6 only under config.x6_taps
+    math = _layer_math(r, s, cin, (x6_ok or stem_x6) and not copt)
     fold_x6 = infer and config.active().fold_eval_bn_x6        # the bf16x6 kernels' inference epilogue is a switch of its own
     if infer and ((math != 0 and not (math == 2 and fold_x6)) or copt or stats is not None or epi or tag != _TAG_FWD or k % 4 != 0):
         raise RuntimeError("DigaConv2d: no kernel with the inference epilogue for this call (exact-fp32 forward -- or, with "
@@ -294,7 +310,7 @@ def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, sta
         # bf16x6: the weights as a pre-split image; the activations read as fp32 and split by the loader waves, or pre-split into
         # three bf16 planes and copied global -> LDS by LDS-DMA (csrc/conv_bf16x6.h)
         bn = "+bn" if infer else ""
-        return _Path("x6ls", variant, 2, "bf16x6/ls" + bn) if _x6_loader() else _Path("x6", variant, 2, "bf16x6" + bn)
+        return _Path("x6ls", variant, 2, "bf16x6/ls" + bn) if (_x6_loader() or stem_x6) else _Path("x6", variant, 2, "bf16x6" + bn)
     if math == 1 and _use_twin(cin, k, r * s, shared) and n * hi * wi * cin * 4 < (1 << 40):
         # split-bf16 arithmetic without register staging: both operands pre-split, copied global -> LDS by LDS-DMA
         return _Path("twin", variant, 1, "bf16x3", flops=False)
@@ -322,15 +338,23 @@ def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, sta
             variant = "keep"
         arith = ("winograd/x6+bn" if x6w else "winograd+bn") if infer else "winograd/x6" if x6w else "winograd"
         return _Path("winograd", variant, 0, arith, tile, ratio, x6w)
+    if _x6_taps() and _taps_ok(cin, r, s, copt):
+        # what Winograd left of the multi-tap calls: bf16x6 with the tap walk in the loader waves (config.x6_taps)
+        if infer and not fold_x6:
+            raise RuntimeError("DigaConv2d: the multi-tap bf16x6 kernels' inference epilogue needs config.fold_eval_bn_x6 (check "
+                               "infer_kernel / folds_eval_bn first)")
+        return _Path("x6rs", variant, 2, "bf16x6/taps+bn" if infer else "bf16x6/taps")
     return _Path("f32", variant, 0, "f32+bn" if infer else "f32")
 
 
 def _wgrad_plan(n, hi, wi, cp, kp, r, s, stride, padding, dilation, ho, wo, x_twin=False, stem=False):
     """_plan's sibling for the weight gradient of a layer with (padded) cp input and kp output channels.  x_twin: the forward left
-    the split twin of its input and the layer may use it (bf16x3); stem: the im2col GEMM of _StemConvFn, which stays off bf16x6."""
-    math = _layer_math(r, s, cp, not stem)
+    the split twin of its input and the layer may use it (bf16x3); stem: the im2col GEMM of _StemConvFn, which stays off bf16x6
+    unless config.x6_taps is on."""
+    stem_x6 = stem and _x6_taps()
+    math = _layer_math(r, s, cp, not stem or stem_x6)
     if math == 2:
-        return _Path("x6ls", "", 2, "bf16x6/ls") if _x6_loader() else _Path("x6", "", 2, "bf16x6")
+        return _Path("x6ls", "", 2, "bf16x6/ls") if (_x6_loader() or stem_x6) else _Path("x6", "", 2, "bf16x6")
     if math == 1 and x_twin:
         return _Path("twin", "", 1, "bf16x3", flops=False)
     if (math == 0 and kp % 256 == 0 and cp % 128 == 0
@@ -338,6 +362,8 @@ def _wgrad_plan(n, hi, wi, cp, kp, r, s, stride, padding, dilation, ho, wo, x_tw
         tile, ratio = _wino_plan(hi, wi, dilation[0])
         x6w = _wino_x6()                               # (read per call: a kept V is fp32 whichever arithmetic the forward ran)
         return _Path("winograd", "", 0, "winograd/x6" if x6w else "winograd", tile, ratio, x6w)
+    if math == 0 and _x6_taps() and _taps_ok(cp, r, s, False):
+        return _Path("x6rs", "", 2, "bf16x6/taps")
     return _Path("f32", "", math, "bf16x3" if math == 1 else "f32", flops=not stem)
 
 
@@ -364,7 +390,8 @@ def winograd_stats_plan(n, hi, wi, cin_padded, k, r, s, stride, padding, dilatio
 def infer_kernel(n, hi, wi, cin, k, r, s, stride, padding, dilation, ho, wo, pointwise_ok=True):
     """The forward kernel family with the inference epilogue (diga_infer_epilogue_t) a layer would run on under the active
     configuration -- "f32+bn" (direct / LDS-DMA / persistent GEMM) or "winograd+bn" (4x4 / 6x6 tiles); with config.fold_eval_bn_x6
-    under conv_math 2 also "bf16x6+bn" / "bf16x6/ls+bn" (pointwise layers, by config.x6_split) and "winograd/x6+bn" (config.x6_winograd)
+    under conv_math 2 also "bf16x6+bn" / "bf16x6/ls+bn" (pointwise layers, by config.x6_split), "winograd/x6+bn" (config.x6_winograd)
+    and "bf16x6/taps+bn" (config.x6_taps: the multi-tap calls off Winograd; the stem then answers "bf16x6/ls+bn")
     -- or None where there is none: conv_math 1; pointwise layers in mode 2 without fold_eval_bn_x6; Cout % 4 != 0; Winograd capped at
     2x2 tiles.  cin: the padded input channel count."""
     try:
@@ -412,6 +439,8 @@ def _make_split(src, ld, rows, ch, triplet):
 _ENTRY = {
     ("x6ls", ""): "diga_conv2d_nhwc_bf16x6_f32in", ("x6ls", "epi"): "diga_conv2d_nhwc_bf16x6_f32in_epi",
     ("x6ls", "infer"): "diga_infer_conv2d_nhwc_bf16x6_f32in",
+    ("x6rs", ""): "diga_conv_taps_bf16x6_f32in", ("x6rs", "epi"): "diga_conv_taps_bf16x6_f32in_epi",
+    ("x6rs", "infer"): "diga_infer_conv_taps_bf16x6_f32in",
     ("x6", ""): "diga_conv2d_nhwc_bf16x6", ("x6", "epi"): "diga_conv2d_nhwc_bf16x6_epi", ("x6", "infer"): "diga_infer_conv2d_nhwc_bf16x6",
     ("twin", ""): "diga_conv2d_nhwc_twin", ("twin", "epi"): "diga_conv2d_nhwc_twin_epi", ("twin", "opts"): "diga_conv2d_nhwc_twin_opts",
     ("bf16x3", ""): "diga_conv2d_nhwc_bf16x3", ("bf16x3", "epi"): "diga_conv2d_nhwc_bf16x3_epi",
@@ -431,7 +460,7 @@ def _operands(path, x, w_krsc, twin_box):
     behind them, the twin / triplet of x to hand back).  The weight image / split lives until the launch returns."""
     n, hi, wi, cin = x.shape
     k, r, s, _ = w_krsc.shape
-    if path.family == "x6ls":
+    if path.family in ("x6ls", "x6rs"):
         # loader form: the activations are read as fp32 in place (contiguous or a channel slice) -- no triplet is built, returned or
         # looked for in the box
         split, ld = None, _nhwc_ld(x)
@@ -445,7 +474,7 @@ def _operands(path, x, w_krsc, twin_box):
             if twin_box is not None:
                 twin_box[0] = split
         act = [_lib.ptr(split)]
-    if path.family in ("x6ls", "x6", "twin"):
+    if path.family in ("x6ls", "x6rs", "x6", "twin"):
         size, fill = ((_lib.lib.diga_split_bf16_image_bytes, "diga_split_bf16_image") if path.family == "twin" else
                       (_lib.lib.diga_split_bf16x6_image_bytes, "diga_split_bf16x6_image"))
         img = torch.empty(size(k, r * s, cin), dtype=torch.uint8, device=x.device)
@@ -533,6 +562,7 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
 # weight gradient: family -> (entry point, its workspace query); Winograd by the arithmetic of its products
 _WGRAD = {
     "x6ls": ("diga_conv2d_wgrad_bf16x6_f32in", _lib.lib.diga_conv2d_wgrad_bf16x6_workspace_bytes),
+    "x6rs": ("diga_conv_taps_wgrad_bf16x6_f32in", _lib.lib.diga_conv_taps_wgrad_bf16x6_workspace_bytes),
     "x6": ("diga_conv2d_wgrad_bf16x6", _lib.lib.diga_conv2d_wgrad_bf16x6_workspace_bytes),
     "twin": ("diga_conv2d_wgrad_twin", _lib.lib.diga_conv2d_wgrad_twin_workspace_bytes),
     "f32": ("diga_conv2d_wgrad_nhwc_f32", _lib.lib.diga_conv2d_wgrad_workspace_bytes),
@@ -562,7 +592,7 @@ def _wgrad_launch(path, gy, x, dwp, r, s, stride, padding, dilation, splits=None
     name, size = _WGRAD[path.family]
     ws = _lib.workspace(size(n, ho, wo, kp, cp, r, s), x.device, "wgrad")
     f32 = path.family == "f32"                         # (reads pitched fp32 tensors and takes the layer's arithmetic)
-    if path.family == "x6ls":                          # fp32 dy and x as they are (a saved triplet of x, if any, is ignored)
+    if path.family in ("x6ls", "x6rs"):                # fp32 dy and x as they are (a saved triplet of x, if any, is ignored)
         lead = (_lib.ptr(gy), gy.stride(2), _lib.ptr(x), x.stride(2))
     else:
         lead = (_lib.ptr(gy), _lib.ptr(x)) if f32 else (_lib.ptr(splits[0]), _lib.ptr(splits[1]))
@@ -622,7 +652,7 @@ class _StemConvFn(torch.autograd.Function):
         w2 = _pad_last(weight.detach().permute(0, 2, 3, 1).reshape(k, 1, 1, kk).contiguous(), kp)
         out = torch.empty((n, ho, wo, k), dtype=torch.float32, device=x.device)
         b = None if bias is None else bias.detach().float().contiguous()
-        _conv_launch(xcol, w2, b, out, (1, 1), (0, 0), (1, 1), _TAG_FWD, call.stats, x6_ok=False, infer=call.infer)     # (bf16x6 mode: the stem stays exact fp32)
+        _conv_launch(xcol, w2, b, out, (1, 1), (0, 0), (1, 1), _TAG_FWD, call.stats, x6_ok=False, infer=call.infer)     # (bf16x6 mode: the stem stays exact fp32 unless config.x6_taps)
         ctx.save_for_backward(xcol)
         ctx.geom = (k, c, r, s, kk, kp, bias is not None, weight.stride())
         return out.permute(0, 3, 1, 2)
@@ -775,10 +805,13 @@ class _Conv2dFn(torch.autograd.Function):
         use_tw = x_twin is not None and ctx.needs_input_grad[1] and _lib.get_conv_math() == 1 and kp == k
         dy_box = [None] if use_tw else None            # the twin of dy: built once, read by backward-data and -weight
         wpath = _wgrad_plan(n, hi, wi, cp, kp, r, s, stride, padding, dilation, ho, wo, x_twin=use_tw)
-        lm = wpath.math                                # this layer's arithmetic (bf16x6 mode: 2 for pointwise layers, else 0)
-        use_x6 = lm == 2
-        x6_ls = wpath.family == "x6ls"                 # ... with the operands split by the loader waves: no triplets (read per call)
-        if use_x6:
+        # The two passes decide their arithmetic separately: a layer may have a Winograd backward-data (0) and a multi-tap bf16x6
+        # weight gradient (2; config.x6_taps).  dm: what the backward-data call's planner (_plan, in _conv_launch) will be given --
+        # 2 for the pointwise layers of bf16x6 mode, whose dy triplet (pass form) the two passes share.
+        dm = _layer_math(r, s, kp)
+        use_x6 = wpath.math == 2                       # the weight gradient runs on bf16x6 ...
+        x6_ls = wpath.family in ("x6ls", "x6rs")       # ... with the operands split by the loader waves: no triplets (read per call)
+        if use_x6 or dm == 2:
             dy_box = [None]                            # the triplet of dy, shared the same way (stays empty in the loader form)
         if ctx.dy_is_twin:          # the BatchNorm after this conv wrote its dx as a twin (same bytes per element)
             if not (kp == k and _lib.get_conv_math() == 1 and cp > 64 and (use_tw or not ctx.needs_input_grad[1])):
@@ -798,7 +831,7 @@ class _Conv2dFn(torch.autograd.Function):
                 # rows per partial-sum record of the backward-data epilogue this call will run (the Winograd form writes one
                 # record per tile group: any divisor of the row count the finaliser is told works, 128 as before)
                 epi_chunk = _lib.lib.diga_conv2d_epi_chunk_rows(n, ho, wo, kp, hi, wi, cp, r, s, 1, 1, padding[0], padding[1],
-                                                                  lm)
+                                                                  dm)
                 chain = ctx.chain if (ctx.chain is not None and not ctx.chain.get("disabled")) else None
                 last_of_chain = False
                 if chain is not None:
@@ -848,13 +881,13 @@ class _Conv2dFn(torch.autograd.Function):
                     epi.mean, epi.invstd, epi.partials = _lib.ptr(box["mean"]), _lib.ptr(box["invstd"]), _lib.ptr(part)
                     box["premasked"] = (dxn.data_ptr(), part, dxn, add, dxn._version, epi_chunk)
                 _conv_launch(gyp, wt, None, dxn, (1, 1), (padding[0], padding[1]), (-dilation[0], -dilation[1]),
-                             _TAG_BWD_DATA, None, dy_box if (((use_tw or ctx.dy_is_twin) and cp > 64) or use_x6) else None,
+                             _TAG_BWD_DATA, None, dy_box if (((use_tw or ctx.dy_is_twin) and cp > 64) or dm == 2) else None,
                              must_twin=ctx.dy_is_twin, epi=epi)
             else:
                 if (r, s) != (1, 1) or padding != (0, 0):
                     raise NotImplementedError("backward-data of strided convs is only needed (and built) for 1x1")
                 dense = torch.empty((n, ho, wo, cp), dtype=torch.float32, device=w.device)
-                _conv_launch(gyp, wt, None, dense, (1, 1), (0, 0), (1, 1), _TAG_BWD_DATA, twin_box=dy_box if use_x6 else None)
+                _conv_launch(gyp, wt, None, dense, (1, 1), (0, 0), (1, 1), _TAG_BWD_DATA, twin_box=dy_box if dm == 2 else None)
                 dxn = torch.zeros((n, hi, wi, cp), dtype=torch.float32, device=w.device)
                 dxn[:, ::stride[0], ::stride[1]] = dense
             dx = dxn[..., :c_true].permute(0, 3, 1, 2)

@@ -541,6 +541,36 @@ int diga_infer_conv2d_nhwc_bf16x6_f32in(const float* in, int64_t in_ld, const vo
                                         int64_t off_dy, int64_t off_dx, const diga_infer_epilogue_t* infer, int prof_tag,
                                         void* stream);
 
+/* bf16x6 for convolutions with more than one tap (opt-in: StepConfig.x6_taps under conv_math = 2), loader form only: `in` / `dy` / `x`
+ * are the fp32 tensors, the weights the tap-major image of diga_split_bf16x6_image(w [Cout][R*S][Cin], ..., Cout, R * S, Cin).  The
+ * argument lists are those of the pointwise `_f32in` entry points above; the taps sit at (off_y0 + r * off_dy, off_x0 + s * off_dx),
+ * either sign (backward-data passes the negated offsets and the transposed weights), any stride; a tap outside the image reads zeros.
+ * The K loop walks the taps in the image's order and steps over those that lie outside the image for a block's whole row tile, so the
+ * result is, bit for bit, diga_conv2d_nhwc_bf16x6_f32in on the tap-major im2col rows [M][R*S*Cin]; R = S = 1 gives the pointwise
+ * kernel's bits.  Checked before any launch: non-null 16-byte aligned pointers, Cin % 32 == 0, in_ld / out_ld, 1 <= R * S <= 64,
+ * positive strides, pixel counts and pixel coordinates below 2^31, the epilogue descriptors' rules (DIGA_EINVAL / DIGA_EALIGN).
+ * (Not named diga_conv2d_*: see diga_infer_conv2d_nhwc_bf16x6.) */
+int diga_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N, int64_t Hi,
+                                int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
+                                int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
+                                float* stats_partial, int prof_tag, void* stream);
+int diga_conv_taps_bf16x6_f32in_epi(const float* in, int64_t in_ld, const void* wgt_img, float* out, int64_t N, int64_t Hi, int64_t Wi,
+                                    int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
+                                    int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
+                                    const diga_bwd_epilogue_t* epi, int prof_tag, void* stream);
+int diga_infer_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N,
+                                      int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
+                                      int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
+                                      int64_t off_dy, int64_t off_dx, const diga_infer_epilogue_t* infer, int prof_tag, void* stream);
+/* ... and their weight gradient dw [Cout][R][S][Cin]: diga_conv2d_wgrad_bf16x6_f32in's arguments with 1 <= R * S <= 64, Cin % 32 == 0
+ * and Cout % 8 == 0; one block group per tap, split-K by the bf16x6 plan with the taps counted among the tiles.  The workspace query
+ * returns 0 for a shape the entry point rejects (DIGA_EINVAL); a workspace smaller than it asks for: DIGA_EWORKSPACE. */
+size_t diga_conv_taps_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R, int64_t S);
+int diga_conv_taps_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
+                                      size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo,
+                                      int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0,
+                                      int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream);
+
 /* bf16x6 for the Winograd-domain GEMMs of the stride-1 3x3 layers (opt-in: StepConfig.x6_winograd under conv_math = 2).  The
  * Winograd transforms stay fp32; the (tile + 2)^2 products per layer run on the loader-split bf16x6 kernels in ONE batched launch.
  *

@@ -3,7 +3,7 @@
 geometries of ResNet-101 DeepLabV2 at the C2 size (16 images of 768x768 -> 193x193 / 97x97 maps).
 
     python tools/bench_conv.py [--images 16] [--reps 5] [--math f32|bf16x3|bf16x6] [--x6-split pass|loader] [--pointwise-only]
-                                 [--x6-winograd] [--winograd-only]
+                                 [--x6-winograd] [--winograd-only] [--x6-taps] [--no-winograd] [--winograd-max-tile 2|4|6] [--taps-only]
 Prints one line per (shape, pass): ms, TFLOP/s, fraction of the 157.3 TFLOP/s fp32 MFMA peak, and the
 share of a training step's conv time that shape accounts for (count x time).
 --math bf16x6: the pointwise layers run on bf16x6, the rest on the exact-fp32 paths; the operand split passes are part of the
@@ -12,6 +12,10 @@ figures (forward: inside the timed call; backward: the elementwise launches -- t
 images remain.
 --x6-winograd (with --math bf16x6): the Winograd-domain GEMMs of the stride-1 3x3 layers on bf16x6 too (config.x6_winograd); the batched
 weight-image split is inside the timed calls.  --winograd-only: time the rows that take the Winograd path only.
+--x6-taps (with --math bf16x6): the multi-tap calls Winograd does not take, and the stem's im2col GEMM, on bf16x6 too (config.x6_taps);
+the weight-image split of the backward (booked as elementwise) is added to dgrad as for the pointwise rows.  --no-winograd sets
+config.winograd = False for the run (every 3x3 row on the direct kernels -- or, with --x6-taps, on the multi-tap bf16x6 kernels);
+--winograd-max-tile 2 is the F(2x2,3x3) cap of the "exact" setting.  --taps-only: time the rows with more than one tap only.
 """
 import argparse
 import os
@@ -22,6 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from diga_amd import _lib, config  # noqa: E402
+from diga_amd.model import conv as dc  # noqa: E402
 from diga_amd.model.conv import DigaConv2d  # noqa: E402
 
 PEAK = 157.3          # fp32 MFMA peak; the split-bf16 mode is priced against 2500 / 3 = 833.3, bf16x6 against 2500 / 6 (see --math)
@@ -64,19 +69,29 @@ def main():
     ap.add_argument("--x6-split", default="pass", choices=["pass", "loader"], help="bf16x6 operand form (config.x6_split)")
     ap.add_argument("--x6-winograd", action="store_true", help="bf16x6 for the Winograd-domain GEMMs as well (config.x6_winograd)")
     ap.add_argument("--winograd-only", action="store_true", help="time the stride-1 3x3 rows of >= 128 channels only (what --x6-winograd changes)")
+    ap.add_argument("--x6-taps", action="store_true", help="bf16x6 for the multi-tap calls off Winograd and the stem as well (config.x6_taps)")
+    ap.add_argument("--no-winograd", action="store_true", help="config.winograd = False for the run")
+    ap.add_argument("--winograd-max-tile", type=int, default=None, choices=[2, 4, 6], help="config.winograd_max_tile for the run")
+    ap.add_argument("--taps-only", action="store_true", help="time the rows with more than one tap only (what --x6-taps can change)")
     a = ap.parse_args()
     _lib.set_conv_math(a.math)
     config.active().x6_split = a.x6_split
     config.active().x6_winograd = a.x6_winograd
+    config.active().x6_taps = a.x6_taps
+    if a.no_winograd:
+        config.active().winograd = False
+    if a.winograd_max_tile is not None:
+        config.active().winograd_max_tile = a.winograd_max_tile
     global PEAK
     PEAK = {"bf16x3": 2500.0 / 3.0, "bf16x6": 2500.0 / 6.0}.get(a.math, 157.3)
     dev = "cuda"
     rows, tot = [], {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}
     pw = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the pointwise (1x1) rows alone
     wn = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the rows on the Winograd path (aspp.d24 stays direct: its ratio)
+    tp = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the rows with more than one tap
     for name, count, cin, cout, k, stride, dil, hw in SHAPES:
         wino_row = k == 3 and stride == 1 and cin >= 128 and cout >= 128 and name != "aspp.d24"
-        if (a.only and a.only not in name) or (a.pointwise_only and k != 1) or (a.winograd_only and not wino_row):
+        if (a.only and a.only not in name) or (a.pointwise_only and k != 1) or (a.winograd_only and not wino_row) or (a.taps_only and k == 1):
             continue
         pad = dil * (k - 1) // 2
         m = DigaConv2d(cin, cout, k, stride=stride, padding=pad, dilation=dil, bias=False).to(dev)
@@ -96,6 +111,7 @@ def main():
 
         # isolate the two backward kernels through the event profiler inside the library
         _lib.call("diga_prof_reset")
+        dc.path_log = {}
         for _ in range(a.reps):
             m.weight.grad = None
             if need_dx:
@@ -110,7 +126,9 @@ def main():
         nw, tw = _lib.prof_query("conv_bwd_weight")
         t_d = td / nd if nd else 0.0
         t_w = tw / nw if nw else 0.0
-        if a.math == "bf16x6" and k == 1:
+        on_taps = any(arith.startswith("bf16x6") for (p, arith) in dc.path_log if p in ("dgrad", "wgrad"))
+        dc.path_log = None
+        if a.math == "bf16x6" and (k == 1 or (a.x6_taps and on_taps)):
             # the split passes of the backward (triplet of dy, the weight image; booked as elementwise) belong to the layer's time
             ne, te = _lib.prof_query("elementwise")
             t_d += te / a.reps
@@ -122,6 +140,10 @@ def main():
             pw["fwd"] += count * t_f
             pw["dgrad"] += count * t_d
             pw["wgrad"] += count * t_w
+        if k > 1:
+            tp["fwd"] += count * t_f
+            tp["dgrad"] += count * t_d
+            tp["wgrad"] += count * t_w
         if wino_row:
             wn["fwd"] += count * t_f
             wn["dgrad"] += count * t_d
@@ -138,6 +160,8 @@ def main():
     print(f"sum over one forward: fwd {tot['fwd']:.1f} ms, dgrad {tot['dgrad']:.1f} ms, wgrad {tot['wgrad']:.1f} ms")
     print(f"pointwise rows, count-weighted ({a.math}{'/' + a.x6_split if a.math == 'bf16x6' else ''}): fwd {pw['fwd']:.2f} ms, dgrad {pw['dgrad']:.2f} ms, wgrad {pw['wgrad']:.2f} ms")
     print(f"winograd rows, count-weighted ({a.math}{'/x6-winograd' if a.x6_winograd else ''}): fwd {wn['fwd']:.2f} ms, dgrad {wn['dgrad']:.2f} ms, wgrad {wn['wgrad']:.2f} ms")
+    setting = a.math + ("/x6-taps" if a.x6_taps else "") + ("/no-winograd" if a.no_winograd else "") + (f"/tile{a.winograd_max_tile}" if a.winograd_max_tile else "")
+    print(f"multi-tap rows, count-weighted ({setting}): fwd {tp['fwd']:.2f} ms, dgrad {tp['dgrad']:.2f} ms, wgrad {tp['wgrad']:.2f} ms")
 
 
 if __name__ == "__main__":

@@ -4,10 +4,10 @@
 512 x 1024 half through diga_amd.evaluate.evaluate_two_scale.
 
     python tools/bench_eval.py [--pairs 3] [--images 10] [--warmup 2] [--height 1024] [--width 2048] [--families]
-                               [--math f32|bf16x3|bf16x6] [--x6-split pass|loader] [--x6-winograd] [--fold-x6]
+                               [--math f32|bf16x3|bf16x6] [--x6-split pass|loader] [--x6-winograd] [--x6-taps] [--fold-x6]
 
-Without the last four the run is the active configuration's (its defaults come from the environment, as everywhere).  --math,
---x6-split and --x6-winograd set the convolution arithmetic of BOTH forms; --fold-x6 (config.fold_eval_bn_x6) lets the fold reach the
+Without the last five the run is the active configuration's (its defaults come from the environment, as everywhere).  --math,
+--x6-split, --x6-winograd and --x6-taps set the convolution arithmetic of BOTH forms; --fold-x6 (config.fold_eval_bn_x6) lets the fold reach the
 bf16x6 kernels under --math bf16x6, where without it only the stem and the 3x3 layers fold.
 
 After warm-up of both forms, `--pairs` times: `--images` calls with the fold off, then `--images` calls with it on, each group
@@ -45,6 +45,7 @@ def main():
     ap.add_argument("--math", choices=["f32", "bf16x3", "bf16x6"], default=None, help="conv arithmetic of both forms (default: the active configuration's)")
     ap.add_argument("--x6-split", choices=["pass", "loader"], default=None, help="bf16x6 operand form (config.x6_split)")
     ap.add_argument("--x6-winograd", action="store_true", help="bf16x6 for the Winograd-domain GEMMs (config.x6_winograd)")
+    ap.add_argument("--x6-taps", action="store_true", help="bf16x6 for the multi-tap calls off Winograd and the stem (config.x6_taps)")
     ap.add_argument("--fold-x6", action="store_true", help="the fold inside the bf16x6 kernels as well (config.fold_eval_bn_x6)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -56,6 +57,8 @@ def main():
         fields["x6_split"] = a.x6_split
     if a.x6_winograd:
         fields["x6_winograd"] = True
+    if a.x6_taps:
+        fields["x6_taps"] = True
     if a.fold_x6:
         fields["fold_eval_bn_x6"] = True
     with config.override(**fields):
@@ -67,7 +70,7 @@ def run(a):
     cfg = config.active()
     math = ("fp32", "bf16x3", "bf16x6")[cfg.conv_math]
     if cfg.conv_math == 2:
-        math += f" ({cfg.x6_split}{', x6_winograd' if cfg.x6_winograd else ''}{', fold_eval_bn_x6' if cfg.fold_eval_bn_x6 else ''})"
+        math += f" ({cfg.x6_split}{', x6_winograd' if cfg.x6_winograd else ''}{', x6_taps' if cfg.x6_taps else ''}{', fold_eval_bn_x6' if cfg.fold_eval_bn_x6 else ''})"
     m = SegModel(arch=sm.RESNET101)
     m.load_state_dict(detweights.state_dict(od.RESNET101))
     m = m.to(dev).eval()
