@@ -30,6 +30,7 @@
 #include <atomic>
 
 #include "common.h"
+#include "conv_call.h"
 
 namespace diga {
 
@@ -2491,13 +2492,6 @@ static int check_conv_common(const char* who, int64_t Cin, int64_t in_ld, int64_
     return DIGA_OK;
 }
 
-// input-map / activation options of a forward convolution (include/diga_hip.h, diga_conv_options_t); nullptr = none
-static void set_options(ConvArgs& a, const diga_conv_options_t* o) {
-    a.pad_reflect = o ? o->reflect_pad : 0;
-    a.up_shift = o ? o->upsample_shift : 0;
-    a.act = o ? o->activation : 0;
-}
-
 static int check_options(const diga_conv_options_t* o, const char* who) {
     if (o == nullptr) return DIGA_OK;
     DIGA_REQUIRE(o->reflect_pad >= 0 && o->reflect_pad <= 1 && o->upsample_shift >= 0 && o->upsample_shift <= 2 && o->activation >= 0 &&
@@ -2505,49 +2499,52 @@ static int check_options(const diga_conv_options_t* o, const char* who) {
     return DIGA_OK;
 }
 
-// fills the backward-epilogue fields of ConvArgs from the public descriptor (nullptr = plain convolution)
-static int set_bwd_epilogue(ConvArgs& a, const diga_bwd_epilogue_t* e, const char* who) {
-    a.e_add = a.e_masky = a.e_x = a.e_relu_ab = a.e_mean = a.e_invstd = nullptr;
-    a.e_partials = nullptr;
-    a.e_maskbits = nullptr;
-    a.e_add_ld = a.e_masky_ld = a.e_x_ld = a.e_maskbits_ld = 0;
-    if (e == nullptr) return DIGA_OK;
-    DIGA_REQUIRE(e->addend || e->mask_y || e->mask_bits || e->x, DIGA_EINVAL, "%s: empty epilogue descriptor", who);
-    DIGA_REQUIRE(a.Cout % 4 == 0 && a.out_ld % 4 == 0 && aligned16(a.out) && a.bias == nullptr && a.stats == nullptr, DIGA_EINVAL,
-                 "%s: a backward epilogue needs Cout %% 4 == 0, out_ld %% 4 == 0, a 16-byte aligned output, no bias, no forward statistics", who);
-    DIGA_REQUIRE(!e->addend || (aligned16(e->addend) && e->addend_ld >= a.Cout && e->addend_ld % 4 == 0), DIGA_EINVAL, "%s: bad addend", who);
-    DIGA_REQUIRE(!e->mask_y || (aligned16(e->mask_y) && e->mask_ld >= a.Cout && e->mask_ld % 4 == 0), DIGA_EINVAL, "%s: bad mask_y", who);
-    DIGA_REQUIRE(!e->x || (aligned16(e->x) && e->x_ld >= a.Cout && e->x_ld % 4 == 0), DIGA_EINVAL, "%s: bad x", who);
-    DIGA_REQUIRE((e->mask_y != nullptr) + (e->relu_ab != nullptr) + (e->mask_bits != nullptr) <= 1, DIGA_EINVAL,
-                 "%s: give one of mask_y, mask_bits, relu_ab", who);
-    DIGA_REQUIRE(!e->mask_bits || e->mask_bits_ld * 8 >= a.Cout, DIGA_EINVAL, "%s: bad mask_bits", who);
-    DIGA_REQUIRE(!e->relu_ab || (e->x && aligned16(e->relu_ab)), DIGA_EINVAL, "%s: relu_ab needs x", who);
-    DIGA_REQUIRE(!e->partials || (e->x && e->mean && e->invstd && aligned16(e->mean) && aligned16(e->invstd)), DIGA_EINVAL,
-                 "%s: partials need x, mean and invstd", who);
-    a.e_add = e->addend; a.e_add_ld = (int)e->addend_ld;
-    a.e_masky = e->mask_y; a.e_masky_ld = (int)e->mask_ld;
-    a.e_maskbits = e->mask_bits; a.e_maskbits_ld = (int)e->mask_bits_ld;
-    a.e_x = e->x; a.e_x_ld = (int)e->x_ld;
-    a.e_relu_ab = e->relu_ab; a.e_mean = e->mean; a.e_invstd = e->invstd; a.e_partials = e->partials;
+// The one place a ConvCall becomes the kernels' ConvArgs: the casts, M, the options and both epilogues (checked here, in
+// this order; `who` / `who_infer` prefix the messages), everything else at its default.  The tile counts and all_inside are
+// the family's to set, next to its kernel choice.
+static int fill_conv_args(ConvArgs& a, const ConvCall& c, const char* who, const char* who_infer) {
+    a = ConvArgs{};
+    a.in = static_cast<const float*>(c.in); a.wgt = c.wgt; a.wgt_hi = c.wgt_hi; a.wgt_lo = c.wgt_lo;
+    a.wgt_img = static_cast<const unsigned char*>(c.wgt_img); a.bias = c.bias; a.out = c.out; a.stats = c.stats;
+    a.N = (int)c.N; a.Hi = (int)c.Hi; a.Wi = (int)c.Wi; a.Cin = (int)c.Cin; a.in_ld = (int)(c.in_ld >= 0 ? c.in_ld : c.Cin);
+    a.Ho = (int)c.Ho; a.Wo = (int)c.Wo; a.Cout = (int)c.Cout; a.out_ld = (int)c.out_ld;
+    a.R = (int)c.R; a.S = (int)c.S; a.sy = (int)c.stride_y; a.sx = (int)c.stride_x;
+    a.oy0 = (int)c.off_y0; a.ox0 = (int)c.off_x0; a.ody = (int)c.off_dy; a.odx = (int)c.off_dx;
+    a.M = (int)(c.N * c.Ho * c.Wo);
+    int rc = check_options(c.opts, who);
+    if (rc) return rc;
+    if (const diga_conv_options_t* o = c.opts) {
+        a.pad_reflect = o->reflect_pad; a.up_shift = o->upsample_shift; a.act = o->activation;
+    }
+    const bool out4 = c.Cout % 4 == 0 && c.out_ld % 4 == 0 && aligned16(c.out) && c.stats == nullptr;
+    rc = check_bwd_epilogue(c.epi, c.Cout, who, out4 && c.bias == nullptr);
+    if (rc) return rc;
+    if (const diga_bwd_epilogue_t* e = c.epi) {
+        a.e_add = e->addend; a.e_add_ld = (int)e->addend_ld;
+        a.e_masky = e->mask_y; a.e_masky_ld = (int)e->mask_ld;
+        a.e_maskbits = e->mask_bits; a.e_maskbits_ld = (int)e->mask_bits_ld;
+        a.e_x = e->x; a.e_x_ld = (int)e->x_ld;
+        a.e_relu_ab = e->relu_ab; a.e_mean = e->mean; a.e_invstd = e->invstd; a.e_partials = e->partials;
+    }
+    rc = check_infer_epilogue(c.infer, c.Cout, c.out, who_infer, out4 && (c.bias == nullptr || aligned16(c.bias)));
+    if (rc) return rc;
+    if (const diga_infer_epilogue_t* e = c.infer) {
+        a.i_ab = e->ab;
+        a.i_res = e->residual;
+        a.i_res_ld = e->residual ? (int)e->residual_ld : 0;
+        a.i_relu = e->relu ? 1 : 0;
+    }
     return DIGA_OK;
 }
 
-// fills the inference-epilogue fields of ConvArgs from the public descriptor (nullptr = plain convolution)
-static int set_infer_epilogue(ConvArgs& a, const diga_infer_epilogue_t* e, const char* who) {
-    a.i_ab = a.i_res = nullptr;
-    a.i_res_ld = a.i_relu = 0;
-    if (e == nullptr) return DIGA_OK;
-    DIGA_REQUIRE(e->ab != nullptr && aligned16(e->ab), DIGA_EINVAL, "%s: the inference epilogue needs 16-byte aligned coefficients ab [2][Cout]", who);
-    DIGA_REQUIRE(a.Cout % 4 == 0 && a.out_ld % 4 == 0 && aligned16(a.out) && (a.bias == nullptr || aligned16(a.bias)) && a.stats == nullptr,
-                 DIGA_EINVAL, "%s: the inference epilogue needs Cout %% 4 == 0, out_ld %% 4 == 0, 16-byte aligned pointers, no statistics", who);
-    DIGA_REQUIRE(!e->residual || (aligned16(e->residual) && e->residual_ld >= a.Cout && e->residual_ld % 4 == 0 && e->residual != a.out),
-                 DIGA_EINVAL, "%s: bad residual (16-byte aligned, residual_ld %% 4 == 0 and >= Cout, not the output)", who);
-    a.i_ab = e->ab;
-    a.i_res = e->residual;
-    a.i_res_ld = e->residual ? (int)e->residual_ld : 0;
-    a.i_relu = e->relu ? 1 : 0;
-    return DIGA_OK;
+// Opts `kernel` into `sh` bytes of dynamic LDS and launches it: every launch of the convolution families goes through here.
+template <class Args>
+static void launch_k(void (*kernel)(Args), unsigned grid, unsigned threads, size_t sh, hipStream_t st, const Args& a) {
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), sh, st, a);
 }
+using ConvKernel = void (*)(ConvArgs);
+using WgradKernel = void (*)(WgradArgs);
 
 // ---------------------------------------------------------------------------------------------
 // Plain fp32 GEMM out [M x Cout] = A [M x K] * W^T (W [Cout][K], one panel per `wb_tiles` 256-row tiles) as a PERSISTENT
@@ -2876,36 +2873,15 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
 
 // the instantiation follows the pointers: statistics / bias arithmetic only where there is a buffer for it
 static void launch_gemm_persistent(const GemmArgs& g, hipStream_t st) {
-    const size_t sh = 3 * (256 + 128) * 128;
-#define DIGA_GEMM_P(STATS_, BIAS_)                                                                                                    \
-    do {                                                                                                                              \
-        (void)hipFuncSetAttribute((const void*)gemm_f32_persistent_kernel<STATS_, BIAS_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)sh);                                                                                           \
-        hipLaunchKernelGGL((gemm_f32_persistent_kernel<STATS_, BIAS_>), dim3(256), dim3(768), sh, st, g);                              \
-    } while (0)
-#define DIGA_GEMM_PI(BIAS_, INF_)                                                                                                     \
-    do {                                                                                                                              \
-        (void)hipFuncSetAttribute((const void*)gemm_f32_persistent_kernel<false, BIAS_, INF_>,                                        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);                                               \
-        hipLaunchKernelGGL((gemm_f32_persistent_kernel<false, BIAS_, INF_>), dim3(256), dim3(768), sh, st, g);                         \
-    } while (0)
-    if (g.i_ab != nullptr) {                          // the inference epilogue (no statistics: checked by the entry point)
-        if (g.i_res != nullptr) {
-            if (g.bias != nullptr) DIGA_GEMM_PI(true, 2);
-            else DIGA_GEMM_PI(false, 2);
-        } else {
-            if (g.bias != nullptr) DIGA_GEMM_PI(true, 1);
-            else DIGA_GEMM_PI(false, 1);
-        }
-    } else if (g.stats != nullptr) {
-        if (g.bias != nullptr) DIGA_GEMM_P(true, true);
-        else DIGA_GEMM_P(true, false);
-    } else {
-        if (g.bias != nullptr) DIGA_GEMM_P(false, true);
-        else DIGA_GEMM_P(false, false);
-    }
-#undef DIGA_GEMM_P
-#undef DIGA_GEMM_PI
+    // [plain | statistics | inference epilogue | inference epilogue + residual][bias]  (no statistics with an inference epilogue:
+    // checked by the entry point)
+    static void (*const kGemm[4][2])(GemmArgs) = {
+        {gemm_f32_persistent_kernel<false, false>, gemm_f32_persistent_kernel<false, true>},
+        {gemm_f32_persistent_kernel<true, false>, gemm_f32_persistent_kernel<true, true>},
+        {gemm_f32_persistent_kernel<false, false, 1>, gemm_f32_persistent_kernel<false, true, 1>},
+        {gemm_f32_persistent_kernel<false, false, 2>, gemm_f32_persistent_kernel<false, true, 2>}};
+    const int v = g.i_ab != nullptr ? (g.i_res != nullptr ? 3 : 2) : g.stats != nullptr ? 1 : 0;
+    launch_k(kGemm[v][g.bias != nullptr], 256, 768, 3 * (256 + 128) * 128, st, g);
 }
 
 // `batches` independent products out_b [rows x Cout] = A_b [rows x K] * W_b^T (W_b [Cout][K]) in one launch of
@@ -2919,16 +2895,13 @@ int gemm_batched_f32_dma(const float* A, int64_t rows_per_batch, int batches, in
                  "gemm_batched_f32_dma: rows %% 256, K %% 32, Cout %% 4 required");
     const int64_t M = rows_per_batch * batches;
     DIGA_REQUIRE(M / 256 < 32768 && M < (1ll << 31), DIGA_EINVAL, "gemm_batched_f32_dma: too many rows");
+    ConvCall c;                                            // the stacked rows as an M / 256 x 256 image under a 1x1 convolution
+    c.in = A; c.in_ld = K; c.wgt = W; c.out = out; c.out_ld = Cout;
+    c.N = 1; c.Hi = c.Ho = M / 256; c.Wi = c.Wo = 256; c.Cin = K; c.Cout = Cout;
+    c.R = c.S = c.stride_y = c.stride_x = c.off_dy = c.off_dx = 1;
     ConvArgs a;
-    a.in = A; a.wgt = W; a.wgt_hi = nullptr; a.wgt_lo = nullptr; a.wgt_img = nullptr; a.bias = nullptr; a.out = out; a.stats = nullptr;
-    a.N = 1; a.Hi = (int)(M / 256); a.Wi = 256; a.Cin = (int)K; a.in_ld = (int)K;
-    a.Ho = a.Hi; a.Wo = 256; a.Cout = (int)Cout; a.out_ld = (int)Cout;
-    a.R = 1; a.S = 1; a.sy = 1; a.sx = 1; a.oy0 = 0; a.ox0 = 0; a.ody = 1; a.odx = 1;
-    a.M = (int)M; a.tiles_m = (int)ceil_div(M, 128); a.tiles_n = (int)ceil_div(Cout, 128); a.all_inside = 1;
-    a.pad_reflect = 0; a.up_shift = 0; a.act = 0;
-    a.e_add = a.e_masky = a.e_x = a.e_relu_ab = a.e_mean = a.e_invstd = nullptr;
-    a.e_partials = nullptr; a.e_maskbits = nullptr;
-    a.e_add_ld = a.e_masky_ld = a.e_x_ld = a.e_maskbits_ld = 0;
+    (void)fill_conv_args(a, c, "gemm_batched_f32_dma", "gemm_batched_f32_dma");
+    a.tiles_m = (int)ceil_div(M, 128); a.tiles_n = (int)ceil_div(Cout, 128); a.all_inside = 1;
     a.wb_tiles = (int)(rows_per_batch / 256);
     a.wb_stride = Cout * K;
     const unsigned grid = (unsigned)((M / 256) * a.tiles_n);
@@ -2942,118 +2915,84 @@ int gemm_batched_f32_dma(const float* A, int64_t rows_per_batch, int batches, in
         launch_gemm_persistent(g, st);
         return DIGA_OK;
     }
-    (void)hipFuncSetAttribute((const void*)conv_fwd_dma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    hipLaunchKernelGGL(conv_fwd_dma_kernel<false>, dim3(grid), dim3(768), sh, st, a);
+    launch_k<ConvArgs>(conv_fwd_dma_kernel<false>, grid, 768, sh, st, a);
     return DIGA_OK;
 }
 
 // A stride-1 pointwise convolution in fp32 with enough tiles for two rounds goes to gemm_f32_persistent_kernel (shape rule
 // only: the statistics buffer's chunk size must be known to the caller, diga_conv2d_stats_chunk_rows).
-bool pointwise_persistent_ok(int64_t M, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t R,
-                             int64_t S, int64_t sy, int64_t sx, int64_t oy0, int64_t ox0) {
-    return R == 1 && S == 1 && sy == 1 && sx == 1 && oy0 == 0 && ox0 == 0 && Hi == Ho && Wi == Wo && Cin % 32 == 0 &&
-           Cout % 128 == 0 && ceil_div(M, 256) * (Cout / 128) >= 512;
+bool pointwise_persistent_ok(const ConvGeometry& g) {
+    return g.R == 1 && g.S == 1 && g.stride_y == 1 && g.stride_x == 1 && g.off_y0 == 0 && g.off_x0 == 0 && g.Hi == g.Ho && g.Wi == g.Wo &&
+           g.Cin % 32 == 0 && g.Cout % 128 == 0 && ceil_div(g.N * g.Ho * g.Wo, 256) * (g.Cout / 128) >= 512;
 }
 
 }  // namespace diga
 
 using namespace diga;
 
-static int conv2d_f32_impl(const float* in, const float* wgt, const float* bias, float* out, int64_t N,
-                                    int64_t Hi, int64_t Wi, int64_t Cin, int64_t in_ld, int64_t Ho, int64_t Wo,
-                                    int64_t Cout, int64_t out_ld, int64_t R, int64_t S, int64_t stride_y,
-                                    int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
-                                    float* stats_partial, int prof_tag, void* stream, const diga_bwd_epilogue_t* epi,
-                                    const diga_conv_options_t* opts = nullptr, const diga_infer_epilogue_t* inf = nullptr) {
-    DIGA_REQUIRE(in && wgt && out, DIGA_EINVAL, "conv2d: null pointer");
-    DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && Cout > 0 && R > 0 && S > 0, DIGA_EINVAL, "conv2d: bad shape");
-    int rc = check_conv_common("conv2d", Cin, in_ld, out_ld, Cout, in, wgt, out);
+// ProfScope tag and FLOP figure of a forward / backward-data convolution (priced as the direct convolution)
+static int conv_prof_tag(const ConvCall& c) { return c.prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD; }
+static double conv_flops(const ConvCall& c) {
+    return 2.0 * (double)(int)(c.N * c.Ho * c.Wo) * (double)c.Cout * (double)(c.R * c.S) * (double)c.Cin;
+}
+
+static int conv2d_f32(const ConvCall& c) {
+    const float* in = static_cast<const float*>(c.in);
+    DIGA_REQUIRE(in && c.wgt && c.out, DIGA_EINVAL, "conv2d: null pointer");
+    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0 && c.Cout > 0 && c.R > 0 && c.S > 0, DIGA_EINVAL, "conv2d: bad shape");
+    int rc = check_conv_common("conv2d", c.Cin, c.in_ld, c.out_ld, c.Cout, in, c.wgt, c.out);
     if (rc) return rc;
-    DIGA_REQUIRE(N * Hi * Wi < (1ll << 31) && N * Ho * Wo < (1ll << 31), DIGA_EINVAL, "conv2d: too many pixels for 32-bit tile indices");
+    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv2d: too many pixels for 32-bit tile indices");
     ConvArgs a;
-    a.in = in; a.wgt = wgt; a.wgt_hi = nullptr; a.wgt_lo = nullptr; a.bias = bias; a.out = out; a.stats = stats_partial;
-    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.in_ld = (int)in_ld;
-    a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.out_ld = (int)out_ld;
-    a.R = (int)R; a.S = (int)S; a.sy = (int)stride_y; a.sx = (int)stride_x;
-    a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
-    a.M = (int)(N * Ho * Wo);
-    a.all_inside = 0;
+    rc = fill_conv_args(a, c, "conv2d", "conv2d_infer");
+    if (rc) return rc;
     a.tiles_m = (int)ceil_div(a.M, 128);
-    rc = check_options(opts, "conv2d");
-    if (rc) return rc;
-    set_options(a, opts);
-    rc = set_bwd_epilogue(a, epi, "conv2d");
-    if (rc) return rc;
-    rc = set_infer_epilogue(a, inf, "conv2d_infer");
-    if (rc) return rc;
-    DIGA_REQUIRE(!inf || (!epi && !opts && (int64_t)a.M * (inf->residual ? inf->residual_ld : 0) < (1ll << 32)), DIGA_EINVAL,
+    DIGA_REQUIRE(!c.infer || (!c.epi && !c.opts && (int64_t)a.M * (c.infer->residual ? c.infer->residual_ld : 0) < (1ll << 32)), DIGA_EINVAL,
                  "conv2d_infer: not combinable with a backward epilogue / options; residual beyond 2^32 elements");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof(prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD, st,
-                   2.0 * (double)a.M * (double)Cout * (double)(R * S) * (double)Cin);
-#define DIGA_LAUNCH_K(KERNEL_, THREADS_, SH_)                                                                          \
-    do {                                                                                                               \
-        (void)hipFuncSetAttribute((const void*)KERNEL_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SH_));        \
-        hipLaunchKernelGGL(KERNEL_, dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(THREADS_), (SH_), st, a);             \
-    } while (0)
-#define DIGA_FWD_LAUNCH(TN_, BK_)                                                                                      \
-    do {                                                                                                               \
-        const size_t sh = (size_t)(2 * 128 * (BK_ + 4) + 2 * 64 * TN_ * (BK_ + 4)) * sizeof(float);                     \
-        if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_kernel<TN_, 32, true>), 256, sh);                                   \
-        else if (inf != nullptr) DIGA_LAUNCH_K((conv_fwd_kernel<TN_, 32, false, true>), 256, sh);                       \
-        else DIGA_LAUNCH_K((conv_fwd_kernel<TN_, BK_, false>), 256, sh);                                                \
-    } while (0)
+    hipStream_t st = (hipStream_t)c.stream;
+    ProfScope prof(conv_prof_tag(c), st, conv_flops(c));
+    const ConvVariant v = conv_variant(c.epi, c.infer);
     // 256 x 128 tiles, LDS-DMA operands (conv_fwd_dma_kernel): one block per CU, so nothing overlaps a tile's epilogue --
     // measured on the C2 shapes (tools/bench_conv.py, same box) it wins 5-12 % (22 % with dead taps) from K >= 256 into
     // >= 256 channels and loses 5-10 % on the 128-channel / K = 64 layers, which stay on the 128 x 128 kernel at two
     // blocks per CU.
-    if (pointwise_persistent_ok(N * Ho * Wo, Hi, Wi, Cin, Ho, Wo, Cout, R, S, stride_y, stride_x, off_y0, off_x0) &&
-        epi == nullptr && !(opts && (opts->reflect_pad || opts->upsample_shift || opts->activation))) {
+    if (pointwise_persistent_ok(c) && c.epi == nullptr && !(a.pad_reflect || a.up_shift || a.act)) {
         // 1x1, stride 1: the persistent GEMM (statistics per 64-row chunk: diga_conv2d_stats_chunk_rows)
-        DIGA_REQUIRE((int64_t)a.M * out_ld < (1ll << 32), DIGA_EINVAL, "conv2d_nhwc_f32: output beyond 2^32 elements (the pointwise kernel "
+        DIGA_REQUIRE((int64_t)a.M * c.out_ld < (1ll << 32), DIGA_EINVAL, "conv2d_nhwc_f32: output beyond 2^32 elements (the pointwise kernel "
                      "addresses it with 32-bit element offsets)");
         GemmArgs g;
-        g.A = in; g.W = wgt; g.out = out; g.M = a.M; g.K = (int)Cin; g.Cout = (int)Cout;
-        g.tiles_m = (int)ceil_div(a.M, 256); g.tiles_n = (int)(Cout / 128); g.wb_tiles = 0; g.wb_stride = 0;
-        g.a_ld = in_ld; g.out_ld = out_ld; g.bias = bias; g.stats = stats_partial; g.rows_valid = a.M;
+        g.A = in; g.W = c.wgt; g.out = c.out; g.M = a.M; g.K = a.Cin; g.Cout = a.Cout;
+        g.tiles_m = (int)ceil_div(a.M, 256); g.tiles_n = a.Cout / 128; g.wb_tiles = 0; g.wb_stride = 0;
+        g.a_ld = c.in_ld; g.out_ld = c.out_ld; g.bias = c.bias; g.stats = c.stats; g.rows_valid = a.M;
         g.i_ab = a.i_ab; g.i_res = a.i_res; g.i_res_ld = a.i_res_ld; g.i_relu = a.i_relu;
         launch_gemm_persistent(g, st);
         return launch_status("diga_conv2d_nhwc_f32");
     }
-    if (a.M >= 256 && Cout >= 256 && R * S * Cin >= 256) {
+    if (a.M >= 256 && c.Cout >= 256 && c.R * c.S * c.Cin >= 256) {
         // (the BatchNorm partials keep their 128-row chunks)
-        a.tiles_n = (int)ceil_div(Cout, 128);
-        const unsigned grid = (unsigned)(ceil_div(a.M, 256) * a.tiles_n);
-        const size_t sh = 3 * (256 + 128) * 128;
-        if (epi != nullptr) {
-            (void)hipFuncSetAttribute((const void*)conv_fwd_dma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            hipLaunchKernelGGL(conv_fwd_dma_kernel<true>, dim3(grid), dim3(768), sh, st, a);
-        } else if (inf != nullptr) {
-            (void)hipFuncSetAttribute((const void*)conv_fwd_dma_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            hipLaunchKernelGGL((conv_fwd_dma_kernel<false, true>), dim3(grid), dim3(768), sh, st, a);
-        } else {
-            (void)hipFuncSetAttribute((const void*)conv_fwd_dma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            hipLaunchKernelGGL(conv_fwd_dma_kernel<false>, dim3(grid), dim3(768), sh, st, a);
-        }
-    } else if (Cout > 64) {
-        a.tiles_n = (int)ceil_div(Cout, 128);
-        DIGA_FWD_LAUNCH(2, 32);
+        static const ConvKernel kDma[3] = {conv_fwd_dma_kernel<false>, conv_fwd_dma_kernel<true>, conv_fwd_dma_kernel<false, true>};
+        a.tiles_n = (int)ceil_div(c.Cout, 128);
+        launch_k(kDma[v], (unsigned)(ceil_div(a.M, 256) * a.tiles_n), 768, 3 * (256 + 128) * 128, st, a);
     } else {
-        a.tiles_n = 1;
-        DIGA_FWD_LAUNCH(1, 32);
+        static const ConvKernel kDirect[2][3] = {                                       // [tn - 1][variant]
+            {conv_fwd_kernel<1, 32, false>, conv_fwd_kernel<1, 32, true>, conv_fwd_kernel<1, 32, false, true>},
+            {conv_fwd_kernel<2, 32, false>, conv_fwd_kernel<2, 32, true>, conv_fwd_kernel<2, 32, false, true>}};
+        const int tn = c.Cout > 64 ? 2 : 1;
+        a.tiles_n = (int)ceil_div(c.Cout, 64 * tn);
+        launch_k(kDirect[tn - 1][v], (unsigned)(a.tiles_m * a.tiles_n), 256, (size_t)(2 * 128 * (32 + 4) + 2 * 64 * tn * (32 + 4)) * sizeof(float), st, a);
     }
-#undef DIGA_FWD_LAUNCH
     return launch_status("diga_conv2d_nhwc_f32");
 }
-
 
 extern "C" int diga_conv2d_nhwc_f32(const float* in, const float* wgt, const float* bias, float* out, int64_t N,
                                     int64_t Hi, int64_t Wi, int64_t Cin, int64_t in_ld, int64_t Ho, int64_t Wo,
                                     int64_t Cout, int64_t out_ld, int64_t R, int64_t S, int64_t stride_y,
                                     int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
                                     float* stats_partial, int prof_tag, void* stream) {
-    return conv2d_f32_impl(in, wgt, bias, out, N, Hi, Wi, Cin, in_ld, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0, off_x0,
-                           off_dy, off_dx, stats_partial, prof_tag, stream, nullptr);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.stats = stats_partial; c.prof_tag = prof_tag;
+    return conv2d_f32(c);
 }
 
 extern "C" int diga_conv2d_nhwc_f32_infer(const float* in, const float* wgt, const float* bias, float* out, int64_t N,
@@ -3062,8 +3001,10 @@ extern "C" int diga_conv2d_nhwc_f32_infer(const float* in, const float* wgt, con
                                           int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
                                           const diga_infer_epilogue_t* infer, int prof_tag, void* stream) {
     DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_infer: null epilogue descriptor");
-    return conv2d_f32_impl(in, wgt, bias, out, N, Hi, Wi, Cin, in_ld, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0, off_x0,
-                           off_dy, off_dx, nullptr, prof_tag, stream, nullptr, nullptr, infer);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.infer = infer; c.prof_tag = prof_tag;
+    return conv2d_f32(c);
 }
 
 extern "C" int diga_conv2d_nhwc_f32_epi(const float* in, const float* wgt, float* out, int64_t N, int64_t Hi, int64_t Wi,
@@ -3072,8 +3013,10 @@ extern "C" int diga_conv2d_nhwc_f32_epi(const float* in, const float* wgt, float
                                         int64_t off_x0, int64_t off_dy, int64_t off_dx, const diga_bwd_epilogue_t* epi,
                                         int prof_tag, void* stream) {
     DIGA_REQUIRE(epi != nullptr, DIGA_EINVAL, "conv2d_epi: null epilogue descriptor");
-    return conv2d_f32_impl(in, wgt, nullptr, out, N, Hi, Wi, Cin, in_ld, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                           off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.out = out; c.out_ld = out_ld; c.epi = epi; c.prof_tag = prof_tag;
+    return conv2d_f32(c);
 }
 
 extern "C" int diga_split_bf16(const float* x, uint16_t* hi, uint16_t* lo, int64_t n, void* stream) {
@@ -3085,71 +3028,46 @@ extern "C" int diga_split_bf16(const float* x, uint16_t* hi, uint16_t* lo, int64
     return launch_status("diga_split_bf16");
 }
 
-static int conv2d_bf16x3_impl(const float* in, const uint16_t* wgt_hi, const uint16_t* wgt_lo, const float* bias,
-                                       float* out, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t in_ld,
-                                       int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
-                                       int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
-                                       int64_t off_dx, float* stats_partial, int prof_tag, void* stream,
-                                       const diga_bwd_epilogue_t* epi, const diga_conv_options_t* opts = nullptr) {
-    DIGA_REQUIRE(in && wgt_hi && wgt_lo && out, DIGA_EINVAL, "conv2d_bf16x3: null pointer");
-    DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && Cout > 0 && R > 0 && S > 0, DIGA_EINVAL, "conv2d_bf16x3: bad shape");
-    int rc = check_conv_common("conv2d_bf16x3", Cin, in_ld, out_ld, Cout, in, in, out);
+static int conv2d_bf16x3(const ConvCall& c) {
+    const float* in = static_cast<const float*>(c.in);
+    DIGA_REQUIRE(in && c.wgt_hi && c.wgt_lo && c.out, DIGA_EINVAL, "conv2d_bf16x3: null pointer");
+    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0 && c.Cout > 0 && c.R > 0 && c.S > 0, DIGA_EINVAL, "conv2d_bf16x3: bad shape");
+    int rc = check_conv_common("conv2d_bf16x3", c.Cin, c.in_ld, c.out_ld, c.Cout, in, in, c.out);
     if (rc) return rc;
-    DIGA_REQUIRE(((uintptr_t)wgt_hi & 7u) == 0 && ((uintptr_t)wgt_lo & 7u) == 0, DIGA_EALIGN, "conv2d_bf16x3: weight alignment");
-    DIGA_REQUIRE(N * Hi * Wi < (1ll << 31) && N * Ho * Wo < (1ll << 31), DIGA_EINVAL, "conv2d_bf16x3: too many pixels");
+    DIGA_REQUIRE(((uintptr_t)c.wgt_hi & 7u) == 0 && ((uintptr_t)c.wgt_lo & 7u) == 0, DIGA_EALIGN, "conv2d_bf16x3: weight alignment");
+    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv2d_bf16x3: too many pixels");
     ConvArgs a;
-    a.in = in; a.wgt = nullptr; a.wgt_hi = wgt_hi; a.wgt_lo = wgt_lo; a.wgt_img = nullptr; a.bias = bias; a.out = out; a.stats = stats_partial;
-    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.in_ld = (int)in_ld;
-    a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.out_ld = (int)out_ld;
-    a.R = (int)R; a.S = (int)S; a.sy = (int)stride_y; a.sx = (int)stride_x;
-    a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
-    a.M = (int)(N * Ho * Wo);
-    a.tiles_m = (int)ceil_div(a.M, 128);
-    {
-        const int64_t y_lo = off_y0 + std::min<int64_t>(0, (R - 1) * off_dy), y_hi = (Ho - 1) * stride_y + off_y0 + std::max<int64_t>(0, (R - 1) * off_dy);
-        const int64_t x_lo = off_x0 + std::min<int64_t>(0, (S - 1) * off_dx), x_hi = (Wo - 1) * stride_x + off_x0 + std::max<int64_t>(0, (S - 1) * off_dx);
-        a.all_inside = y_lo >= 0 && y_hi < Hi && x_lo >= 0 && x_hi < Wi;
+    rc = fill_conv_args(a, c, "conv2d_bf16x3", "conv2d_bf16x3");
+    if (rc) return rc;
+    if (!(a.pad_reflect || a.up_shift)) {
+        const int64_t y_lo = c.off_y0 + std::min<int64_t>(0, (c.R - 1) * c.off_dy), y_hi = (c.Ho - 1) * c.stride_y + c.off_y0 + std::max<int64_t>(0, (c.R - 1) * c.off_dy);
+        const int64_t x_lo = c.off_x0 + std::min<int64_t>(0, (c.S - 1) * c.off_dx), x_hi = (c.Wo - 1) * c.stride_x + c.off_x0 + std::max<int64_t>(0, (c.S - 1) * c.off_dx);
+        a.all_inside = y_lo >= 0 && y_hi < c.Hi && x_lo >= 0 && x_hi < c.Wi;
     }
-    rc = check_options(opts, "conv2d_bf16x3");
-    if (rc) return rc;
-    set_options(a, opts);
-    if (a.pad_reflect || a.up_shift) a.all_inside = 0;
-    rc = set_bwd_epilogue(a, epi, "conv2d_bf16x3");
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof(prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD, st,
-                   2.0 * (double)a.M * (double)Cout * (double)(R * S) * (double)Cin);
-    const int tn = Cout > 64 ? 2 : 1;
-    a.tiles_n = (int)ceil_div(Cout, 64 * tn);
+    hipStream_t st = (hipStream_t)c.stream;
+    ProfScope prof(conv_prof_tag(c), st, conv_flops(c));
+    const ConvVariant v = conv_variant(c.epi, nullptr);
+    const int tn = c.Cout > 64 ? 2 : 1;
+    a.tiles_n = (int)ceil_div(c.Cout, 64 * tn);
     // the wide kernel addresses the input and the weights with 32-bit element offsets
-    const bool fits32 = N * Hi * Wi * in_ld < (1ll << 31) && Cout * R * S * Cin < (1ll << 31);
+    const bool fits32 = c.N * c.Hi * c.Wi * c.in_ld < (1ll << 31) && c.Cout * c.R * c.S * c.Cin < (1ll << 31);
     DIGA_REQUIRE(fits32 || !(a.pad_reflect || a.up_shift), DIGA_EINVAL,
                  "conv2d_bf16x3: reflect padding / fused upsampling are implemented by the 256-row kernel only");
     if (fits32) {
+        static const ConvKernel kWide[2][2] = {{conv_fwd_x3w_kernel<1, false, false>, conv_fwd_x3w_kernel<1, false, true>},   // [tn - 1][variant]
+                                               {conv_fwd_x3w_kernel<2, false, false>, conv_fwd_x3w_kernel<2, false, true>}};
         a.tiles_m = (int)ceil_div(a.M, 256);
         const size_t loop = (size_t)2 * 256 * 64 + (size_t)2 * 64 * tn * 64, stage = (size_t)128 * (64 * tn + 4) * sizeof(float);
-        const size_t sh = loop > stage ? loop : stage;
+        ConvKernel k = kWide[tn - 1][v];
 #ifdef DIGA_PROBE_STAMP                                                         /* diagnostic build only (tools/diag/build_probe.sh) */
-        if (tn == 2 && a.stats != nullptr) {
-            (void)hipFuncSetAttribute((const void*)conv_fwd_x3w_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            hipLaunchKernelGGL((conv_fwd_x3w_kernel<2, true>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(256), sh, st, a);
-        } else
+        if (tn == 2 && a.stats != nullptr) k = conv_fwd_x3w_kernel<2, true>;
 #endif
-        if (tn == 2) {
-            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x3w_kernel<2, false, true>), 256, sh);
-            else DIGA_LAUNCH_K((conv_fwd_x3w_kernel<2, false, false>), 256, sh);
-        } else {
-            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x3w_kernel<1, false, true>), 256, sh);
-            else DIGA_LAUNCH_K((conv_fwd_x3w_kernel<1, false, false>), 256, sh);
-        }
-    } else if (tn == 2) {
-        const size_t sh = (size_t)2 * (2 * 128 * kRowB + 2 * 128 * kRowB);
-        if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x3p_kernel<2, true>), 256, sh);
-        else DIGA_LAUNCH_K((conv_fwd_x3p_kernel<2, false>), 256, sh);
+        launch_k(k, (unsigned)(a.tiles_m * a.tiles_n), 256, loop > stage ? loop : stage, st, a);
     } else {
-        const size_t sh = (size_t)2 * (2 * 128 * kRowB + 2 * 64 * kRowB);
-        if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x3p_kernel<1, true>), 256, sh);
-        else DIGA_LAUNCH_K((conv_fwd_x3p_kernel<1, false>), 256, sh);
+        static const ConvKernel kPixel[2][2] = {{conv_fwd_x3p_kernel<1, false>, conv_fwd_x3p_kernel<1, true>},               // [tn - 1][variant]
+                                                {conv_fwd_x3p_kernel<2, false>, conv_fwd_x3p_kernel<2, true>}};
+        a.tiles_m = (int)ceil_div(a.M, 128);
+        launch_k(kPixel[tn - 1][v], (unsigned)(a.tiles_m * a.tiles_n), 256, (size_t)2 * (2 * 128 * kRowB + 2 * 64 * tn * kRowB), st, a);
     }
     return launch_status("diga_conv2d_nhwc_bf16x3");
 }
@@ -3159,8 +3077,11 @@ extern "C" int diga_conv2d_nhwc_bf16x3(const float* in, const uint16_t* wgt_hi, 
                                        int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
                                        int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
                                        int64_t off_dx, float* stats_partial, int prof_tag, void* stream) {
-    return conv2d_bf16x3_impl(in, wgt_hi, wgt_lo, bias, out, N, Hi, Wi, Cin, in_ld, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x,
-                              off_y0, off_x0, off_dy, off_dx, stats_partial, prof_tag, stream, nullptr);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.wgt_hi = wgt_hi; c.wgt_lo = wgt_lo; c.bias = bias; c.out = out; c.out_ld = out_ld;
+    c.stats = stats_partial; c.prof_tag = prof_tag;
+    return conv2d_bf16x3(c);
 }
 
 extern "C" int diga_conv2d_nhwc_bf16x3_epi(const float* in, const uint16_t* wgt_hi, const uint16_t* wgt_lo, float* out, int64_t N,
@@ -3169,8 +3090,10 @@ extern "C" int diga_conv2d_nhwc_bf16x3_epi(const float* in, const uint16_t* wgt_
                                            int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
                                            const diga_bwd_epilogue_t* epi, int prof_tag, void* stream) {
     DIGA_REQUIRE(epi != nullptr, DIGA_EINVAL, "conv2d_bf16x3_epi: null epilogue descriptor");
-    return conv2d_bf16x3_impl(in, wgt_hi, wgt_lo, nullptr, out, N, Hi, Wi, Cin, in_ld, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x,
-                              off_y0, off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.wgt_hi = wgt_hi; c.wgt_lo = wgt_lo; c.out = out; c.out_ld = out_ld; c.epi = epi; c.prof_tag = prof_tag;
+    return conv2d_bf16x3(c);
 }
 
 // ---- "twin" path: activations and weights pre-split, staged by LDS-DMA (conv_fwd_x3t_kernel)
@@ -3205,57 +3128,31 @@ extern "C" int diga_split_bf16_image(const float* w, void* img, int64_t K, int64
     return launch_status("diga_split_bf16_image");
 }
 
-static int conv2d_twin_impl(const void* in_twin, const void* wgt_img, const float* bias, float* out, int64_t N,
-                                     int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
-                                     int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
-                                     int64_t off_dy, int64_t off_dx, float* stats_partial, int prof_tag, void* stream,
-                                     const diga_bwd_epilogue_t* epi, const diga_conv_options_t* opts = nullptr) {
-    DIGA_REQUIRE(in_twin && wgt_img && out, DIGA_EINVAL, "conv2d_twin: null pointer");
-    DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && Cout > 0 && R > 0 && S > 0, DIGA_EINVAL, "conv2d_twin: bad shape");
-    DIGA_REQUIRE(Cin > 0 && Cin % 32 == 0 && out_ld >= Cout, DIGA_EINVAL, "conv2d_twin: Cin must be a multiple of 32");
-    DIGA_REQUIRE(aligned16(in_twin) && aligned16(wgt_img) && ((uintptr_t)out & 3u) == 0, DIGA_EALIGN, "conv2d_twin: alignment");
-    DIGA_REQUIRE(N * Hi * Wi < (1ll << 31) && N * Ho * Wo < (1ll << 31), DIGA_EINVAL, "conv2d_twin: too many pixels");
+static int conv2d_twin(const ConvCall& c) {
+    DIGA_REQUIRE(c.in && c.wgt_img && c.out, DIGA_EINVAL, "conv2d_twin: null pointer");
+    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0 && c.Cout > 0 && c.R > 0 && c.S > 0, DIGA_EINVAL, "conv2d_twin: bad shape");
+    DIGA_REQUIRE(c.Cin > 0 && c.Cin % 32 == 0 && c.out_ld >= c.Cout, DIGA_EINVAL, "conv2d_twin: Cin must be a multiple of 32");
+    DIGA_REQUIRE(aligned16(c.in) && aligned16(c.wgt_img) && ((uintptr_t)c.out & 3u) == 0, DIGA_EALIGN, "conv2d_twin: alignment");
+    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv2d_twin: too many pixels");
     ConvArgs a;
-    a.in = reinterpret_cast<const float*>(in_twin); a.wgt = nullptr; a.wgt_hi = nullptr; a.wgt_lo = nullptr;
-    a.wgt_img = reinterpret_cast<const unsigned char*>(wgt_img); a.bias = bias; a.out = out; a.stats = stats_partial;
-    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.in_ld = (int)Cin;
-    a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.out_ld = (int)out_ld;
-    a.R = (int)R; a.S = (int)S; a.sy = (int)stride_y; a.sx = (int)stride_x;
-    a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
-    a.M = (int)(N * Ho * Wo);
+    const int rc = fill_conv_args(a, c, "conv2d_twin", "conv2d_twin");
+    if (rc) return rc;
+    const int tn = c.Cout > 64 ? 2 : 1;
     a.tiles_m = (int)ceil_div(a.M, 256);
-    a.all_inside = 0;
-    const int tn = Cout > 64 ? 2 : 1;
-    a.tiles_n = (int)ceil_div(Cout, 64 * tn);
-    {
-        int rc = check_options(opts, "conv2d_twin");
-        if (rc) return rc;
-        set_options(a, opts);
-        rc = set_bwd_epilogue(a, epi, "conv2d_twin");
-        if (rc) return rc;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof(prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD, st,
-                   2.0 * (double)a.M * (double)Cout * (double)(R * S) * (double)Cin);
-    const size_t sh = (size_t)3 * (2 * 256 * 64 + 2 * 64 * tn * 64);
+    a.tiles_n = (int)ceil_div(c.Cout, 64 * tn);
+    hipStream_t st = (hipStream_t)c.stream;
+    ProfScope prof(conv_prof_tag(c), st, conv_flops(c));
     // two MFMA waves per SIMD + dead-tap skipping (conv_fwd_x3t8_kernel).  Its predecessor with one MFMA wave per SIMD measured
     // 3-6 % slower on multi-tap layers (ASPP dilation 24: 17 %) and 3-12 % on pointwise layers (tools/experiments/).
-    DIGA_REQUIRE(R * S <= 64, DIGA_EINVAL, "conv2d_twin: at most 64 taps (the dead-tap mask is one 64-bit word)");
-    {
-        // K order: tap-major (the weight layout's order, bit-identical to the register-staged kernel).  Walking channel
-        // chunks outer / taps inner instead (to line up in time the re-reads of an input row that tiles running together
-        // make through different vertical taps) measured 8-14 % SLOWER on every shape, ASPP included: the loader's
-        // per-step tap switch costs more than the locality returns (commit 78ff4b5 has the switch).
-        const size_t stg = (size_t)2 * 128 * (64 * tn + 4) * sizeof(float);
-        const size_t sh8 = sh > stg ? sh : stg;
-        if (tn == 2) {
-            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x3t8_kernel<2, true>), 768, sh8);
-            else DIGA_LAUNCH_K((conv_fwd_x3t8_kernel<2, false>), 768, sh8);
-        } else {
-            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x3t8_kernel<1, true>), 768, sh8);
-            else DIGA_LAUNCH_K((conv_fwd_x3t8_kernel<1, false>), 768, sh8);
-        }
-    }
+    DIGA_REQUIRE(c.R * c.S <= 64, DIGA_EINVAL, "conv2d_twin: at most 64 taps (the dead-tap mask is one 64-bit word)");
+    // K order: tap-major (the weight layout's order, bit-identical to the register-staged kernel).  Walking channel
+    // chunks outer / taps inner instead (to line up in time the re-reads of an input row that tiles running together
+    // make through different vertical taps) measured 8-14 % SLOWER on every shape, ASPP included: the loader's
+    // per-step tap switch costs more than the locality returns (commit 78ff4b5 has the switch).
+    static const ConvKernel kTwin[2][2] = {{conv_fwd_x3t8_kernel<1, false>, conv_fwd_x3t8_kernel<1, true>},   // [tn - 1][variant]
+                                           {conv_fwd_x3t8_kernel<2, false>, conv_fwd_x3t8_kernel<2, true>}};
+    const size_t ring = (size_t)3 * (2 * 256 * 64 + 2 * 64 * tn * 64), stg = (size_t)2 * 128 * (64 * tn + 4) * sizeof(float);
+    launch_k(kTwin[tn - 1][conv_variant(c.epi, nullptr)], (unsigned)(a.tiles_m * a.tiles_n), 768, ring > stg ? ring : stg, st, a);
     return launch_status("diga_conv2d_nhwc_twin");
 }
 
@@ -3263,8 +3160,10 @@ extern "C" int diga_conv2d_nhwc_twin(const void* in_twin, const void* wgt_img, c
                                      int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
                                      int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
                                      int64_t off_dy, int64_t off_dx, float* stats_partial, int prof_tag, void* stream) {
-    return conv2d_twin_impl(in_twin, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0, off_x0,
-                            off_dy, off_dx, stats_partial, prof_tag, stream, nullptr);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in_twin; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld; c.stats = stats_partial; c.prof_tag = prof_tag;
+    return conv2d_twin(c);
 }
 
 extern "C" int diga_conv2d_nhwc_twin_epi(const void* in_twin, const void* wgt_img, float* out, int64_t N, int64_t Hi, int64_t Wi,
@@ -3272,8 +3171,10 @@ extern "C" int diga_conv2d_nhwc_twin_epi(const void* in_twin, const void* wgt_im
                                          int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
                                          int64_t off_dx, const diga_bwd_epilogue_t* epi, int prof_tag, void* stream) {
     DIGA_REQUIRE(epi != nullptr, DIGA_EINVAL, "conv2d_twin_epi: null epilogue descriptor");
-    return conv2d_twin_impl(in_twin, wgt_img, nullptr, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                            off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in_twin; c.wgt_img = wgt_img; c.out = out; c.out_ld = out_ld; c.epi = epi; c.prof_tag = prof_tag;
+    return conv2d_twin(c);
 }
 
 // The same three forward entry points with the translator's input map / output activation folded in (diga_conv_options_t):
@@ -3283,8 +3184,10 @@ extern "C" int diga_conv2d_nhwc_f32_opts(const float* in, const float* wgt, cons
                                          int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
                                          int64_t off_dy, int64_t off_dx, const diga_conv_options_t* opts, int prof_tag, void* stream) {
     DIGA_REQUIRE(opts != nullptr, DIGA_EINVAL, "conv2d_opts: null options");
-    return conv2d_f32_impl(in, wgt, bias, out, N, Hi, Wi, Cin, in_ld, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0, off_x0,
-                           off_dy, off_dx, nullptr, prof_tag, stream, nullptr, opts);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.opts = opts; c.prof_tag = prof_tag;
+    return conv2d_f32(c);
 }
 
 extern "C" int diga_conv2d_nhwc_bf16x3_opts(const float* in, const uint16_t* wgt_hi, const uint16_t* wgt_lo, const float* bias, float* out,
@@ -3293,8 +3196,11 @@ extern "C" int diga_conv2d_nhwc_bf16x3_opts(const float* in, const uint16_t* wgt
                                             int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
                                             const diga_conv_options_t* opts, int prof_tag, void* stream) {
     DIGA_REQUIRE(opts != nullptr, DIGA_EINVAL, "conv2d_bf16x3_opts: null options");
-    return conv2d_bf16x3_impl(in, wgt_hi, wgt_lo, bias, out, N, Hi, Wi, Cin, in_ld, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, nullptr, opts);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.wgt_hi = wgt_hi; c.wgt_lo = wgt_lo; c.bias = bias; c.out = out; c.out_ld = out_ld; c.opts = opts;
+    c.prof_tag = prof_tag;
+    return conv2d_bf16x3(c);
 }
 
 extern "C" int diga_conv2d_nhwc_twin_opts(const void* in_twin, const void* wgt_img, const float* bias, float* out, int64_t N, int64_t Hi,
@@ -3302,8 +3208,10 @@ extern "C" int diga_conv2d_nhwc_twin_opts(const void* in_twin, const void* wgt_i
                                           int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
                                           int64_t off_dx, const diga_conv_options_t* opts, int prof_tag, void* stream) {
     DIGA_REQUIRE(opts != nullptr, DIGA_EINVAL, "conv2d_twin_opts: null options");
-    return conv2d_twin_impl(in_twin, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0, off_x0,
-                            off_dy, off_dx, nullptr, prof_tag, stream, nullptr, opts);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in_twin; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld; c.opts = opts; c.prof_tag = prof_tag;
+    return conv2d_twin(c);
 }
 
 extern "C" size_t diga_conv2d_stats_floats(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout) {
@@ -3322,8 +3230,10 @@ extern "C" int diga_conv2d_epi_chunk_rows(int64_t N, int64_t Hi, int64_t Wi, int
 extern "C" int diga_conv2d_stats_chunk_rows(int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout,
                                             int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
                                             int math) {
-    return (math == DIGA_CONV_MATH_F32 && pointwise_persistent_ok(N * Ho * Wo, Hi, Wi, Cin, Ho, Wo, Cout, R, S, stride_y, stride_x, off_y0, off_x0))
-               ? 64 : 128;
+    ConvGeometry g;
+    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.Cout = Cout; g.R = R; g.S = S;
+    g.stride_y = stride_y; g.stride_x = stride_x; g.off_y0 = off_y0; g.off_x0 = off_x0;
+    return (math == DIGA_CONV_MATH_F32 && pointwise_persistent_ok(g)) ? 64 : 128;
 }
 
 
@@ -3383,6 +3293,49 @@ int64_t wgrad_mpad(int64_t M) { return ceil_div(M, kBK) * kBK + 2 * kBK; }
 size_t wgrad_slab_bytes(const WgradPlan& p, int64_t Cout, int64_t Cin, int64_t RS) {
     return p.splits > 1 ? (size_t)p.splits * Cout * RS * Cin * sizeof(float) : 0;
 }
+
+// The one place a WgradCall becomes the kernels' WgradArgs: the casts, M, the split-K plan and where the partial sums go.  The
+// pixel table (launch_pixtab) and the batched forms' tap strides are added by the families that have them.
+void fill_wgrad_args(WgradArgs& a, const WgradCall& c, const WgradPlan& p, int64_t M_pad) {
+    a = WgradArgs{};
+    a.dy = static_cast<const float*>(c.dy); a.x = static_cast<const float*>(c.x);
+    a.slab = p.splits > 1 ? static_cast<float*>(c.workspace) : c.dw;
+    a.N = (int)c.N; a.Hi = (int)c.Hi; a.Wi = (int)c.Wi; a.Cin = (int)c.Cin; a.x_ld = (int)(c.x_ld >= 0 ? c.x_ld : c.Cin);
+    a.Ho = (int)c.Ho; a.Wo = (int)c.Wo; a.Cout = (int)c.Cout; a.dy_ld = (int)(c.dy_ld >= 0 ? c.dy_ld : c.Cout);
+    a.R = (int)c.R; a.S = (int)c.S; a.sy = (int)c.stride_y; a.sx = (int)c.stride_x;
+    a.oy0 = (int)c.off_y0; a.ox0 = (int)c.off_x0; a.ody = (int)c.off_dy; a.odx = (int)c.off_dx;
+    a.M = (int)(c.N * c.Ho * c.Wo); a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.splits = p.splits; a.steps_per_split = p.steps_per_split;
+    a.M_pad = (int)M_pad;
+}
+unsigned wgrad_grid(const WgradArgs& a) { return (unsigned)((int64_t)a.tiles_m * a.tiles_n * a.R * a.S * a.splits); }
+// (tap, output pixel) -> input pixel table behind the split-K slabs of the workspace (-1 outside the image: in bounds for any
+// stride / offset), then 16 zero bytes
+void launch_pixtab(WgradArgs& a, const WgradCall& c, size_t slab_bytes, hipStream_t st) {
+    int* tab = reinterpret_cast<int*>(static_cast<char*>(c.workspace) + slab_bytes);
+    float* zeros = reinterpret_cast<float*>(tab + (int64_t)a.R * a.S * a.M_pad);
+    hipLaunchKernelGGL(wgrad_pixtab_kernel, dim3((unsigned)ceil_div(a.M_pad, 256), (unsigned)(a.R * a.S)), dim3(256), 0, st, tab, zeros,
+                       a.M, a.M_pad, a.Ho, a.Wo, a.Hi, a.Wi, a.S, a.sy, a.sx, a.oy0, a.ox0, a.ody, a.odx);
+    a.ptab = tab;
+    a.zeros = zeros;
+}
+// the split-K partial sums of `slab`, added in fixed order into dw [Cout][R * S][Cin]
+void launch_slab_reduce(const WgradArgs& a, const float* slab, float* dw, hipStream_t st) {
+    if (a.splits <= 1) return;
+    const int64_t n4 = (int64_t)a.Cout * a.R * a.S * a.Cin / 4;
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, slab, dw, n4, a.splits);
+}
+// `batches` independent products riding on the tap index (the Winograd-domain weight gradients): the rows as a 1 x rows image,
+// "tap" t reads Z + t * rows * Cout and V + t * rows * Cin
+void fill_wgrad_batched(WgradArgs& a, const float* Z, const float* V, float* dU, float* slab, int64_t rows, int batches, int64_t Cout,
+                        int64_t Cin, const WgradPlan& p) {
+    WgradCall c;
+    c.dy = Z; c.x = V; c.dw = dU; c.workspace = slab;
+    c.N = c.Hi = c.Ho = 1; c.Wi = c.Wo = rows; c.Cin = Cin; c.Cout = Cout;
+    c.R = 1; c.S = batches; c.stride_y = c.stride_x = c.off_dy = c.off_dx = 1;
+    fill_wgrad_args(a, c, p, rows);
+    a.dy_tap_stride = rows * Cout;
+    a.x_tap_stride = rows * Cin;
+}
 }  // namespace
 
 namespace diga {
@@ -3397,24 +3350,10 @@ int wgrad_batched_f32_dma(const float* Z, const float* V, float* dU, float* slab
                           int64_t Cin, hipStream_t st) {
     DIGA_REQUIRE(rows > 0 && rows % 32 == 0 && Cout % 256 == 0 && Cin % 128 == 0 && batches > 0 && rows < (1ll << 31), DIGA_EINVAL,
                  "wgrad_batched_f32_dma: rows %% 32, Cout %% 256, Cin %% 128 required");
-    const WgradPlan p = plan_wgrad_wide(rows, Cout, Cin, batches);
     WgradArgs a;
-    a.dy = Z; a.x = V; a.slab = p.splits > 1 ? slab : dU;
-    a.N = 1; a.Hi = 1; a.Wi = (int)rows; a.Cin = (int)Cin; a.x_ld = (int)Cin;
-    a.Ho = 1; a.Wo = (int)rows; a.Cout = (int)Cout; a.dy_ld = (int)Cout;
-    a.R = 1; a.S = batches; a.sy = 1; a.sx = 1; a.oy0 = 0; a.ox0 = 0; a.ody = 1; a.odx = 1;
-    a.M = (int)rows; a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.splits = p.splits; a.steps_per_split = p.steps_per_split;
-    a.ptab = nullptr; a.zeros = nullptr; a.M_pad = (int)rows;
-    a.dy_tap_stride = rows * Cout;
-    a.x_tap_stride = rows * Cin;
-    const unsigned grid = (unsigned)((int64_t)p.tiles_m * p.tiles_n * batches * p.splits);
-    const size_t shd = (size_t)3 * kBK * (256 + 128) * 4;
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shd);
-    hipLaunchKernelGGL(conv_wgrad_dma_kernel, dim3(grid), dim3(768), shd, st, a);
-    if (p.splits > 1) {
-        const int64_t n4 = Cout * batches * Cin / 4;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)slab, dU, n4, p.splits);
-    }
+    fill_wgrad_batched(a, Z, V, dU, slab, rows, batches, Cout, Cin, plan_wgrad_wide(rows, Cout, Cin, batches));
+    launch_k<WgradArgs>(conv_wgrad_dma_kernel, wgrad_grid(a), 768, (size_t)3 * kBK * (256 + 128) * 4, st, a);
+    launch_slab_reduce(a, slab, dU, st);
     return DIGA_OK;
 }
 
@@ -3456,80 +3395,29 @@ extern "C" int diga_conv2d_wgrad_nhwc_f32(const float* dy, const float* x, float
     const size_t need = slab_bytes + ((wide || f32_tab) ? (size_t)RS * M_pad * sizeof(int) + 64 : 0);
     DIGA_REQUIRE(workspace_bytes >= need && (need == 0 || (workspace && aligned16(workspace))), DIGA_EWORKSPACE,
                  "conv2d_wgrad: workspace too small (%zu < %zu)", workspace_bytes, need);
+    WgradCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.dw = dw; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
     WgradArgs a;
-    a.dy = dy; a.x = x; a.slab = p.splits > 1 ? (float*)workspace : dw;
-    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.x_ld = (int)x_ld;
-    a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.dy_ld = (int)dy_ld;
-    a.R = (int)R; a.S = (int)S; a.sy = (int)stride_y; a.sx = (int)stride_x;
-    a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
-    a.M = (int)M; a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.splits = p.splits; a.steps_per_split = p.steps_per_split;
-    a.ptab = nullptr; a.zeros = nullptr; a.M_pad = (int)M_pad;
+    fill_wgrad_args(a, c, p, M_pad);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)M * (double)Cout * (double)RS * (double)Cin);
-    const unsigned grid = (unsigned)((int64_t)p.tiles_m * p.tiles_n * RS * p.splits);
+    if (wide || f32_tab) launch_pixtab(a, c, slab_bytes, st);
     if (wide) {
-        int* tab = reinterpret_cast<int*>(static_cast<char*>(workspace) + slab_bytes);
-        float* zeros = reinterpret_cast<float*>(tab + RS * M_pad);
-        hipLaunchKernelGGL(wgrad_pixtab_kernel, dim3((unsigned)ceil_div(M_pad, 256), (unsigned)RS), dim3(256), 0, st, tab, zeros,
-                           (int)M, (int)M_pad, (int)Ho, (int)Wo, (int)Hi, (int)Wi, (int)S, (int)stride_y, (int)stride_x,
-                           (int)off_y0, (int)off_x0, (int)off_dy, (int)off_dx);
-        a.ptab = tab;
-        a.zeros = zeros;
-        const size_t shw = (size_t)2 * (256 + 64 * p.tn) * kRowB;
-        if (p.tn == 2) {
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_x3w_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shw);
-            hipLaunchKernelGGL((conv_wgrad_x3w_kernel<2>), dim3(grid), dim3(256), shw, st, a);
-        } else {
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_x3w_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shw);
-            hipLaunchKernelGGL((conv_wgrad_x3w_kernel<1>), dim3(grid), dim3(256), shw, st, a);
-        }
-    } else
-    {
-    if (f32_tab) {
-        int* tab = reinterpret_cast<int*>(static_cast<char*>(workspace) + slab_bytes);
-        float* zeros = reinterpret_cast<float*>(tab + RS * M_pad);
-        hipLaunchKernelGGL(wgrad_pixtab_kernel, dim3((unsigned)ceil_div(M_pad, 256), (unsigned)RS), dim3(256), 0, st, tab, zeros,
-                           (int)M, (int)M_pad, (int)Ho, (int)Wo, (int)Hi, (int)Wi, (int)S, (int)stride_y, (int)stride_x,
-                           (int)off_y0, (int)off_x0, (int)off_dy, (int)off_dx);
-        a.ptab = tab;
-    }
-    if (dma) {
-        const size_t shd = (size_t)3 * kBK * (256 + 128) * 4;
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shd);
-        hipLaunchKernelGGL(conv_wgrad_dma_kernel, dim3(grid), dim3(768), shd, st, a);
+        static const WgradKernel kWide[2] = {conv_wgrad_x3w_kernel<1>, conv_wgrad_x3w_kernel<2>};                  // [tn - 1]
+        launch_k(kWide[p.tn - 1], wgrad_grid(a), 256, (size_t)2 * (256 + 64 * p.tn) * kRowB, st, a);
+    } else if (dma) {
+        launch_k<WgradArgs>(conv_wgrad_dma_kernel, wgrad_grid(a), 768, (size_t)3 * kBK * (256 + 128) * 4, st, a);
+    } else if (x3) {
+        static const WgradKernel kX3[2][2] = {{conv_wgrad_x3_kernel<1, 1>, conv_wgrad_x3_kernel<1, 2>},             // [tm - 1][tn - 1]
+                                              {conv_wgrad_x3_kernel<2, 1>, conv_wgrad_x3_kernel<2, 2>}};
+        launch_k(kX3[p.tm - 1][p.tn - 1], wgrad_grid(a), 256, (size_t)2 * (2 * 64 * p.tm * kRowB + 2 * 64 * p.tn * kRowB), st, a);
     } else {
-    const size_t sh = (size_t)(4 * kBK * kLDW) * sizeof(float);
-#define DIGA_WGRAD_LAUNCH(TM_, TN_)                                                                                   \
-    do {                                                                                                               \
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_kernel<TM_, TN_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); \
-        hipLaunchKernelGGL((conv_wgrad_kernel<TM_, TN_>), dim3(grid), dim3(256), sh, st, a);                            \
-    } while (0)
-#define DIGA_WGRAD_X3_LAUNCH(TM_, TN_)                                                                                \
-    do {                                                                                                               \
-        const size_t shx = (size_t)2 * (2 * 64 * TM_ * kRowB + 2 * 64 * TN_ * kRowB);                                   \
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_x3_kernel<TM_, TN_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shx); \
-        hipLaunchKernelGGL((conv_wgrad_x3_kernel<TM_, TN_>), dim3(grid), dim3(256), shx, st, a);                        \
-    } while (0)
-    if (x3) {
-        if (p.tm == 2 && p.tn == 2) DIGA_WGRAD_X3_LAUNCH(2, 2);
-        else if (p.tm == 2) DIGA_WGRAD_X3_LAUNCH(2, 1);
-        else if (p.tn == 2) DIGA_WGRAD_X3_LAUNCH(1, 2);
-        else DIGA_WGRAD_X3_LAUNCH(1, 1);
-    } else {
-        if (p.tm == 2 && p.tn == 2) DIGA_WGRAD_LAUNCH(2, 2);
-        else if (p.tm == 2) DIGA_WGRAD_LAUNCH(2, 1);
-        else if (p.tn == 2) DIGA_WGRAD_LAUNCH(1, 2);
-        else DIGA_WGRAD_LAUNCH(1, 1);
+        static const WgradKernel kF32[2][2] = {{conv_wgrad_kernel<1, 1>, conv_wgrad_kernel<1, 2>},                  // [tm - 1][tn - 1]
+                                               {conv_wgrad_kernel<2, 1>, conv_wgrad_kernel<2, 2>}};
+        launch_k(kF32[p.tm - 1][p.tn - 1], wgrad_grid(a), 256, (size_t)(4 * kBK * kLDW) * sizeof(float), st, a);
     }
-#undef DIGA_WGRAD_X3_LAUNCH
-#undef DIGA_WGRAD_LAUNCH
-    }
-    }
-    if (p.splits > 1) {
-        const int64_t n4 = Cout * RS * Cin / 4;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)workspace, dw,
-                           n4, p.splits);
-    }
+    launch_slab_reduce(a, static_cast<const float*>(workspace), dw, st);
     return launch_status("diga_conv2d_wgrad_nhwc_f32");
 }
 
@@ -3557,33 +3445,16 @@ extern "C" int diga_conv2d_wgrad_twin(const void* dy_twin, const void* x_twin, f
     const WgradPlan p = plan_wgrad_twin(M, Cout, Cin, RS);
     const size_t slab_bytes = wgrad_slab_bytes(p, Cout, Cin, RS);
     DIGA_REQUIRE(workspace_bytes >= slab_bytes + (size_t)RS * M_pad * sizeof(int) + 64, DIGA_EWORKSPACE, "conv2d_wgrad_twin: workspace too small");
+    WgradCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.dy = dy_twin; c.x = x_twin; c.dw = dw; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
     WgradArgs a;
-    a.dy = reinterpret_cast<const float*>(dy_twin); a.x = reinterpret_cast<const float*>(x_twin);
-    a.slab = p.splits > 1 ? (float*)workspace : dw;
-    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.x_ld = (int)Cin;
-    a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.dy_ld = (int)Cout;
-    a.R = (int)R; a.S = (int)S; a.sy = (int)stride_y; a.sx = (int)stride_x;
-    a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
-    a.M = (int)M; a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.splits = p.splits; a.steps_per_split = p.steps_per_split;
-    a.M_pad = (int)M_pad;
+    fill_wgrad_args(a, c, p, M_pad);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)M * (double)Cout * (double)RS * (double)Cin);
-    int* tab = reinterpret_cast<int*>(static_cast<char*>(workspace) + slab_bytes);
-    float* zeros = reinterpret_cast<float*>(tab + RS * M_pad);
-    hipLaunchKernelGGL(wgrad_pixtab_kernel, dim3((unsigned)ceil_div(M_pad, 256), (unsigned)RS), dim3(256), 0, st, tab, zeros, (int)M,
-                       (int)M_pad, (int)Ho, (int)Wo, (int)Hi, (int)Wi, (int)S, (int)stride_y, (int)stride_x, (int)off_y0, (int)off_x0,
-                       (int)off_dy, (int)off_dx);
-    a.ptab = tab;
-    a.zeros = zeros;
-    const unsigned grid = (unsigned)((int64_t)p.tiles_m * p.tiles_n * RS * p.splits);
-    const size_t sh = (size_t)3 * (2 * kBK * 512 + 2 * kBK * 256);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_x3t_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    hipLaunchKernelGGL(conv_wgrad_x3t_kernel, dim3(grid), dim3(512), sh, st, a);
-    if (p.splits > 1) {
-        const int64_t n4 = Cout * RS * Cin / 4;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)workspace, dw, n4,
-                           p.splits);
-    }
+    launch_pixtab(a, c, slab_bytes, st);
+    launch_k<WgradArgs>(conv_wgrad_x3t_kernel, wgrad_grid(a), 512, (size_t)3 * (2 * kBK * 512 + 2 * kBK * 256), st, a);
+    launch_slab_reduce(a, static_cast<const float*>(workspace), dw, st);
     return launch_status("diga_conv2d_wgrad_twin");
 }
 

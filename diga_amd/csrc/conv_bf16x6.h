@@ -710,117 +710,71 @@ extern "C" int diga_split_bf16x6_image(const float* w, void* img, int64_t K, int
     return launch_status("diga_split_bf16x6_image");
 }
 
-// in_ld < 0: `in_triplet` is a triplet image (the pass form); else it is the fp32 tensor with that row pitch (the loader form).
-// inf: the inference epilogue (the `_infer` entry points; forward without statistics and without a backward epilogue), checked by
-// set_infer_epilogue -- the rules of diga_conv2d_nhwc_f32_infer -- before anything is launched.
-static int conv2d_bf16x6_impl(const void* in_triplet, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N, int64_t Hi,
-                              int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R, int64_t S,
-                              int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
-                              float* stats_partial, int prof_tag, void* stream, const diga_bwd_epilogue_t* epi,
-                              const diga_infer_epilogue_t* inf = nullptr, bool taps = false) {
-    DIGA_REQUIRE(in_triplet && wgt_img && out, DIGA_EINVAL, "conv2d_bf16x6: null pointer");
-    DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && Cout > 0, DIGA_EINVAL, "conv2d_bf16x6: bad shape");
-    if (taps) {
+// c.f32in: `in` is the fp32 tensor with row pitch in_ld (the loader form); else a triplet image (the pass form).
+// c.infer: the inference epilogue (the `_infer` entry points; forward without statistics and without a backward epilogue), checked
+// -- the rules of diga_conv2d_nhwc_f32_infer -- before anything is launched.
+static int conv2d_bf16x6(const ConvCall& c) {
+    DIGA_REQUIRE(c.in && c.wgt_img && c.out, DIGA_EINVAL, "conv2d_bf16x6: null pointer");
+    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0 && c.Cout > 0, DIGA_EINVAL, "conv2d_bf16x6: bad shape");
+    if (c.taps) {
         // the `diga_conv_taps_*` entry points (loader form only): up to 64 taps (live_taps' mask), every coordinate the loader
-        // derives -- (Ho - 1) * stride + offset + (R - 1) * step -- within 32 bits
-        DIGA_REQUIRE(in_ld >= 0, DIGA_EINVAL, "conv_taps_bf16x6: in_ld must be at least Cin and a multiple of 4");
-        DIGA_REQUIRE(R >= 1 && S >= 1 && R <= 64 && S <= 64 && R * S <= 64, DIGA_EINVAL, "conv_taps_bf16x6: 1 <= R * S <= 64 taps");
-        DIGA_REQUIRE(stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv_taps_bf16x6: strides must be positive");
-        const int64_t lim = 1ll << 30;
-        DIGA_REQUIRE(stride_y < lim && stride_x < lim && off_y0 > -lim && off_y0 < lim && off_x0 > -lim && off_x0 < lim && off_dy > -lim &&
-                     off_dy < lim && off_dx > -lim && off_dx < lim && Ho * stride_y < lim && Wo * stride_x < lim &&
-                     (off_dy < 0 ? -off_dy : off_dy) * R < lim && (off_dx < 0 ? -off_dx : off_dx) * S < lim,
-                     DIGA_EINVAL, "conv_taps_bf16x6: strides / offsets beyond 32-bit pixel coordinates");
+        // derives within 32 bits (check_tap_coordinates)
+        DIGA_REQUIRE(c.in_ld >= 0, DIGA_EINVAL, "conv_taps_bf16x6: in_ld must be at least Cin and a multiple of 4");
+        DIGA_REQUIRE(c.R >= 1 && c.S >= 1 && c.R <= 64 && c.S <= 64 && c.R * c.S <= 64, DIGA_EINVAL, "conv_taps_bf16x6: 1 <= R * S <= 64 taps");
+        DIGA_REQUIRE(c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL, "conv_taps_bf16x6: strides must be positive");
+        const int rc = check_tap_coordinates(c, "conv_taps_bf16x6");
+        if (rc) return rc;
     } else {
-        DIGA_REQUIRE(R == 1 && S == 1 && stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv2d_bf16x6: pointwise (1x1) convolutions only");
+        DIGA_REQUIRE(c.R == 1 && c.S == 1 && c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL, "conv2d_bf16x6: pointwise (1x1) convolutions only");
     }
-    DIGA_REQUIRE(Cin > 0 && Cin % 32 == 0 && out_ld >= Cout, DIGA_EINVAL, "conv2d_bf16x6: Cin must be a multiple of 32");
-    const bool f32in = in_ld >= 0;
-    DIGA_REQUIRE(!f32in || (in_ld >= Cin && in_ld % 4 == 0 && in_ld < (1ll << 31)), DIGA_EINVAL,
+    DIGA_REQUIRE(c.Cin > 0 && c.Cin % 32 == 0 && c.out_ld >= c.Cout, DIGA_EINVAL, "conv2d_bf16x6: Cin must be a multiple of 32");
+    DIGA_REQUIRE(!c.f32in || (c.in_ld >= c.Cin && c.in_ld % 4 == 0 && c.in_ld < (1ll << 31)), DIGA_EINVAL,
                  "conv2d_bf16x6_f32in: in_ld must be at least Cin and a multiple of 4");
-    DIGA_REQUIRE(aligned16(in_triplet) && aligned16(wgt_img) && ((uintptr_t)out & 3u) == 0, DIGA_EALIGN, "conv2d_bf16x6: alignment");
-    DIGA_REQUIRE(N * Hi * Wi < (1ll << 31) && N * Ho * Wo < (1ll << 31), DIGA_EINVAL, "conv2d_bf16x6: too many pixels");
+    DIGA_REQUIRE(aligned16(c.in) && aligned16(c.wgt_img) && ((uintptr_t)c.out & 3u) == 0, DIGA_EALIGN, "conv2d_bf16x6: alignment");
+    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv2d_bf16x6: too many pixels");
     // every output pixel reads an input pixel inside the image or zeros: the loader checks the coordinate, so any
     // (stride, offset) is in bounds
+    const int tn = c.Cout > 64 ? 2 : 1;                 // (= image_bn(Cout) / 64: the weight image's tile)
+    const int64_t tiles_m = ceil_div(c.N * c.Ho * c.Wo, 256), tiles_n = ceil_div(c.Cout, 64 * tn);
+    DIGA_REQUIRE(!c.taps || tiles_m * tiles_n < (1ll << 31), DIGA_EINVAL, "conv_taps_bf16x6: too many tiles for one launch");
     ConvArgs a;
-    a.in = reinterpret_cast<const float*>(in_triplet); a.wgt = nullptr; a.wgt_hi = nullptr; a.wgt_lo = nullptr;
-    a.wgt_img = reinterpret_cast<const unsigned char*>(wgt_img); a.bias = bias; a.out = out; a.stats = stats_partial;
-    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.in_ld = f32in ? (int)in_ld : (int)Cin;
-    a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.out_ld = (int)out_ld;
-    a.R = (int)R; a.S = (int)S; a.sy = (int)stride_y; a.sx = (int)stride_x;
-    a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
-    a.M = (int)(N * Ho * Wo);
-    a.tiles_m = (int)ceil_div(a.M, 256);
-    a.all_inside = 0;
-    const int tn = Cout > 64 ? 2 : 1;                 // (= image_bn(Cout) / 64: the weight image's tile)
-    a.tiles_n = (int)ceil_div(Cout, 64 * tn);
-    DIGA_REQUIRE(!taps || (int64_t)a.tiles_m * a.tiles_n < (1ll << 31), DIGA_EINVAL, "conv_taps_bf16x6: too many tiles for one launch");
-    set_options(a, nullptr);
-    {
-        int rc = set_bwd_epilogue(a, epi, "conv2d_bf16x6");
-        if (rc) return rc;
-        rc = set_infer_epilogue(a, inf, "conv2d_bf16x6_infer");
-        if (rc) return rc;
-        DIGA_REQUIRE(!inf || (!epi && prof_tag != DIGA_PROF_CONV_BWD_DATA), DIGA_EINVAL,
-                     "conv2d_bf16x6_infer: the inference epilogue comes with the forward (no backward epilogue)");
-    }
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof(prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD, st,
-                   2.0 * (double)a.M * (double)Cout * (double)(R * S) * (double)Cin);
+    const int rc = fill_conv_args(a, c, "conv2d_bf16x6", "conv2d_bf16x6_infer");
+    if (rc) return rc;
+    a.tiles_m = (int)tiles_m;
+    a.tiles_n = (int)tiles_n;
+    DIGA_REQUIRE(!c.infer || (!c.epi && c.prof_tag != DIGA_PROF_CONV_BWD_DATA), DIGA_EINVAL,
+                 "conv2d_bf16x6_infer: the inference epilogue comes with the forward (no backward epilogue)");
+    hipStream_t st = (hipStream_t)c.stream;
+    ProfScope prof(conv_prof_tag(c), st, conv_flops(c));
+    // conv_fwd_x6_kernel<TN, EPI, F32IN, WB, INF, TAPS> by [form][tn - 1][variant]; the name launch_status reports by [form][infer]
+    enum { kPass, kLoader, kTaps };
+    static const ConvKernel kX6[3][2][3] = {
+        {{conv_fwd_x6_kernel<1, false>, conv_fwd_x6_kernel<1, true>, conv_fwd_x6_kernel<1, false, false, false, true>},
+         {conv_fwd_x6_kernel<2, false>, conv_fwd_x6_kernel<2, true>, conv_fwd_x6_kernel<2, false, false, false, true>}},
+        {{conv_fwd_x6_kernel<1, false, true>, conv_fwd_x6_kernel<1, true, true>, conv_fwd_x6_kernel<1, false, true, false, true>},
+         {conv_fwd_x6_kernel<2, false, true>, conv_fwd_x6_kernel<2, true, true>, conv_fwd_x6_kernel<2, false, true, false, true>}},
+        {{conv_fwd_x6_kernel<1, false, true, false, false, true>, conv_fwd_x6_kernel<1, true, true, false, false, true>,
+          conv_fwd_x6_kernel<1, false, true, false, true, true>},
+         {conv_fwd_x6_kernel<2, false, true, false, false, true>, conv_fwd_x6_kernel<2, true, true, false, false, true>,
+          conv_fwd_x6_kernel<2, false, true, false, true, true>}}};
+    static const char* const kName[3][2] = {{"diga_conv2d_nhwc_bf16x6", "diga_infer_conv2d_nhwc_bf16x6"},
+                                            {"diga_conv2d_nhwc_bf16x6_f32in", "diga_infer_conv2d_nhwc_bf16x6_f32in"},
+                                            {"diga_conv_taps_bf16x6_f32in", "diga_infer_conv_taps_bf16x6_f32in"}};
+    const int form = c.taps ? kTaps : c.f32in ? kLoader : kPass;
     const size_t ring = (size_t)2 * (3 * 256 * 64 + 3 * 64 * tn * 64);
     const size_t stg = (size_t)2 * 128 * (64 * tn + 4) * sizeof(float);
-    const size_t sh = ring > stg ? ring : stg;
-    if (taps) {
-        if (inf != nullptr) {
-            if (tn == 2) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true, false, true, true>), 768, sh);
-            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, true, false, true, true>), 768, sh);
-            return launch_status("diga_infer_conv_taps_bf16x6_f32in");
-        }
-        if (tn == 2) {
-            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, true, true, false, false, true>), 768, sh);
-            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true, false, false, true>), 768, sh);
-        } else {
-            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, true, true, false, false, true>), 768, sh);
-            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, true, false, false, true>), 768, sh);
-        }
-        return launch_status("diga_conv_taps_bf16x6_f32in");
-    }
-    if (inf != nullptr) {
-        if (f32in) {
-            if (tn == 2) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true, false, true>), 768, sh);
-            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, true, false, true>), 768, sh);
-            return launch_status("diga_infer_conv2d_nhwc_bf16x6_f32in");
-        }
-        if (tn == 2) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, false, false, true>), 768, sh);
-        else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, false, false, true>), 768, sh);
-        return launch_status("diga_infer_conv2d_nhwc_bf16x6");
-    }
-    if (f32in) {
-        if (tn == 2) {
-            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, true, true>), 768, sh);
-            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true>), 768, sh);
-        } else {
-            if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, true, true>), 768, sh);
-            else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false, true>), 768, sh);
-        }
-        return launch_status("diga_conv2d_nhwc_bf16x6_f32in");
-    }
-    if (tn == 2) {
-        if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, true>), 768, sh);
-        else DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false>), 768, sh);
-    } else {
-        if (epi != nullptr) DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, true>), 768, sh);
-        else DIGA_LAUNCH_K((conv_fwd_x6_kernel<1, false>), 768, sh);
-    }
-    return launch_status("diga_conv2d_nhwc_bf16x6");
+    launch_k(kX6[form][tn - 1][conv_variant(c.epi, c.infer)], (unsigned)(a.tiles_m * a.tiles_n), 768, ring > stg ? ring : stg, st, a);
+    return launch_status(kName[form][c.infer != nullptr]);
 }
 
 extern "C" int diga_conv2d_nhwc_bf16x6(const void* in_triplet, const void* wgt_img, const float* bias, float* out, int64_t N,
                                        int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
                                        int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
                                        int64_t off_dy, int64_t off_dx, float* stats_partial, int prof_tag, void* stream) {
-    return conv2d_bf16x6_impl(in_triplet, -1, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, stats_partial, prof_tag, stream, nullptr);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in_triplet; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld; c.stats = stats_partial; c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
 }
 
 extern "C" int diga_conv2d_nhwc_bf16x6_epi(const void* in_triplet, const void* wgt_img, float* out, int64_t N, int64_t Hi, int64_t Wi,
@@ -828,8 +782,10 @@ extern "C" int diga_conv2d_nhwc_bf16x6_epi(const void* in_triplet, const void* w
                                            int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0, int64_t off_dy,
                                            int64_t off_dx, const diga_bwd_epilogue_t* epi, int prof_tag, void* stream) {
     DIGA_REQUIRE(epi != nullptr, DIGA_EINVAL, "conv2d_bf16x6_epi: null epilogue descriptor");
-    return conv2d_bf16x6_impl(in_triplet, -1, wgt_img, nullptr, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in_triplet; c.wgt_img = wgt_img; c.out = out; c.out_ld = out_ld; c.epi = epi; c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
 }
 
 extern "C" int diga_conv2d_nhwc_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out,
@@ -838,8 +794,11 @@ extern "C" int diga_conv2d_nhwc_bf16x6_f32in(const float* in, int64_t in_ld, con
                                              int64_t off_x0, int64_t off_dy, int64_t off_dx, float* stats_partial, int prof_tag,
                                              void* stream) {
     DIGA_REQUIRE(in_ld >= 0, DIGA_EINVAL, "conv2d_bf16x6_f32in: in_ld must be at least Cin and a multiple of 4");
-    return conv2d_bf16x6_impl(in, in_ld, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, stats_partial, prof_tag, stream, nullptr);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
+    c.stats = stats_partial; c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
 }
 
 extern "C" int diga_conv2d_nhwc_bf16x6_f32in_epi(const float* in, int64_t in_ld, const void* wgt_img, float* out, int64_t N, int64_t Hi,
@@ -849,8 +808,10 @@ extern "C" int diga_conv2d_nhwc_bf16x6_f32in_epi(const float* in, int64_t in_ld,
                                                  int prof_tag, void* stream) {
     DIGA_REQUIRE(epi != nullptr, DIGA_EINVAL, "conv2d_bf16x6_f32in_epi: null epilogue descriptor");
     DIGA_REQUIRE(in_ld >= 0, DIGA_EINVAL, "conv2d_bf16x6_f32in_epi: in_ld must be at least Cin and a multiple of 4");
-    return conv2d_bf16x6_impl(in, in_ld, wgt_img, nullptr, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = true; c.wgt_img = wgt_img; c.out = out; c.out_ld = out_ld; c.epi = epi; c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
 }
 
 // The pointwise forward with the inference epilogue (include/diga_hip.h, diga_infer_epilogue_t): conv_fwd_x6_kernel<TN, ..., INF>.
@@ -860,8 +821,10 @@ extern "C" int diga_infer_conv2d_nhwc_bf16x6(const void* in_triplet, const void*
                                              int64_t off_dy, int64_t off_dx, const diga_infer_epilogue_t* infer, int prof_tag,
                                              void* stream) {
     DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_bf16x6_infer: null epilogue descriptor");
-    return conv2d_bf16x6_impl(in_triplet, -1, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, nullptr, infer);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in_triplet; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld; c.infer = infer; c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
 }
 
 extern "C" int diga_infer_conv2d_nhwc_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out,
@@ -871,8 +834,11 @@ extern "C" int diga_infer_conv2d_nhwc_bf16x6_f32in(const float* in, int64_t in_l
                                                    const diga_infer_epilogue_t* infer, int prof_tag, void* stream) {
     DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_bf16x6_f32in_infer: null epilogue descriptor");
     DIGA_REQUIRE(in_ld >= 0, DIGA_EINVAL, "conv2d_bf16x6_f32in_infer: in_ld must be at least Cin and a multiple of 4");
-    return conv2d_bf16x6_impl(in, in_ld, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, nullptr, infer);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld; c.infer = infer;
+    c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
 }
 
 // Multi-tap convolutions on the loader form (conv_fwd_x6_kernel<..., TAPS>): the argument lists of the pointwise `_f32in` entry
@@ -881,8 +847,11 @@ extern "C" int diga_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld, const
                                            int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
                                            int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
                                            int64_t off_dy, int64_t off_dx, float* stats_partial, int prof_tag, void* stream) {
-    return conv2d_bf16x6_impl(in, in_ld, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, stats_partial, prof_tag, stream, nullptr, nullptr, true);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
+    c.stats = stats_partial; c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
 }
 
 extern "C" int diga_conv_taps_bf16x6_f32in_epi(const float* in, int64_t in_ld, const void* wgt_img, float* out, int64_t N, int64_t Hi,
@@ -891,8 +860,11 @@ extern "C" int diga_conv_taps_bf16x6_f32in_epi(const float* in, int64_t in_ld, c
                                                int64_t off_dy, int64_t off_dx, const diga_bwd_epilogue_t* epi, int prof_tag,
                                                void* stream) {
     DIGA_REQUIRE(epi != nullptr, DIGA_EINVAL, "conv_taps_bf16x6_f32in_epi: null epilogue descriptor");
-    return conv2d_bf16x6_impl(in, in_ld, wgt_img, nullptr, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, epi, nullptr, true);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.out = out; c.out_ld = out_ld; c.epi = epi;
+    c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
 }
 
 extern "C" int diga_infer_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out,
@@ -901,8 +873,11 @@ extern "C" int diga_infer_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld,
                                                  int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx,
                                                  const diga_infer_epilogue_t* infer, int prof_tag, void* stream) {
     DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "infer_conv_taps_bf16x6_f32in: null epilogue descriptor");
-    return conv2d_bf16x6_impl(in, in_ld, wgt_img, bias, out, N, Hi, Wi, Cin, Ho, Wo, Cout, out_ld, R, S, stride_y, stride_x, off_y0,
-                              off_x0, off_dy, off_dx, nullptr, prof_tag, stream, nullptr, infer, true);
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
+    c.infer = infer; c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
 }
 
 namespace {
@@ -928,13 +903,14 @@ WgradPlan plan_wgrad_x6(int64_t M, int64_t Cout, int64_t Cin, int64_t RS = 1) {
     return p;
 }
 // shape rules of the multi-tap weight gradient (shared by the entry point's checks and its workspace query)
-bool taps_wgrad_shape_ok(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R, int64_t S) {
+bool taps_wgrad_shape_ok(const ConvGeometry& g) {
     const int64_t lim = 1ll << 31;
-    if (N <= 0 || Ho <= 0 || Wo <= 0 || R < 1 || S < 1 || R > 64 || S > 64 || R * S > 64 || Cin <= 0 || Cin % 32 != 0 || Cin >= lim ||
-        Cout <= 0 || Cout % 8 != 0 || Cout >= lim || N >= lim || Ho >= lim || Wo >= lim || N * Ho >= lim || N * Ho * Wo >= lim)
+    if (g.N <= 0 || g.Ho <= 0 || g.Wo <= 0 || g.R < 1 || g.S < 1 || g.R > 64 || g.S > 64 || g.R * g.S > 64 || g.Cin <= 0 || g.Cin % 32 != 0 ||
+        g.Cin >= lim || g.Cout <= 0 || g.Cout % 8 != 0 || g.Cout >= lim || g.N >= lim || g.Ho >= lim || g.Wo >= lim || g.N * g.Ho >= lim ||
+        g.N * g.Ho * g.Wo >= lim)
         return false;
-    const WgradPlan p = plan_wgrad_x6(N * Ho * Wo, Cout, Cin, R * S);
-    return ceil_div(Cout, 256) * ceil_div(Cin, 128) * R * S * p.splits < (1ll << 31);
+    const WgradPlan p = plan_wgrad_x6(g.N * g.Ho * g.Wo, g.Cout, g.Cin, g.R * g.S);
+    return ceil_div(g.Cout, 256) * ceil_div(g.Cin, 128) * g.R * g.S * p.splits < (1ll << 31);
 }
 }  // namespace
 
@@ -944,78 +920,47 @@ extern "C" size_t diga_conv2d_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho
     return wgrad_slab_bytes(plan_wgrad_x6(M, Cout, Cin), Cout, Cin, RS) + (size_t)RS * wgrad_mpad(M) * sizeof(int) + 64;
 }
 
-// dy_ld < 0: the operands are triplet images (the pass form); else the fp32 tensors with these row pitches (the loader form)
-static int conv2d_wgrad_bf16x6_impl(const void* dy_triplet, int64_t dy_ld, const void* x_triplet, int64_t x_ld, float* dw,
-                                    void* workspace, size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin,
-                                    int64_t Ho, int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
-                                    int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream,
-                                    bool taps = false) {
-    const bool f32in = dy_ld >= 0;
-    DIGA_REQUIRE(dy_triplet && x_triplet && dw && workspace, DIGA_EINVAL, "conv2d_wgrad_bf16x6: null pointer");
-    DIGA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: bad shape");
-    if (taps) {
+// c.f32in: the operands are the fp32 tensors with row pitches dy_ld / x_ld (the loader form); else triplet images (the pass form)
+static int conv2d_wgrad_bf16x6(const WgradCall& c) {
+    DIGA_REQUIRE(c.dy && c.x && c.dw && c.workspace, DIGA_EINVAL, "conv2d_wgrad_bf16x6: null pointer");
+    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: bad shape");
+    if (c.taps) {
         // diga_conv_taps_wgrad_bf16x6_f32in: one block group per tap from the pixel table of all taps (conv_wgrad_x6_kernel<true>)
-        DIGA_REQUIRE(f32in && taps_wgrad_shape_ok(N, Ho, Wo, Cout, Cin, R, S) && stride_y > 0 && stride_x > 0, DIGA_EINVAL,
+        DIGA_REQUIRE(c.f32in && taps_wgrad_shape_ok(c) && c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL,
                      "conv_taps_wgrad_bf16x6: 1 <= R * S <= 64, Cin %% 32, Cout %% 8, positive strides and a block count below 2^31 required");
-        const int64_t lim = 1ll << 30;
-        DIGA_REQUIRE(stride_y < lim && stride_x < lim && off_y0 > -lim && off_y0 < lim && off_x0 > -lim && off_x0 < lim && off_dy > -lim &&
-                     off_dy < lim && off_dx > -lim && off_dx < lim && Ho * stride_y < lim && Wo * stride_x < lim &&
-                     (off_dy < 0 ? -off_dy : off_dy) * R < lim && (off_dx < 0 ? -off_dx : off_dx) * S < lim,
-                     DIGA_EINVAL, "conv_taps_wgrad_bf16x6: strides / offsets beyond 32-bit pixel coordinates");
+        const int rc = check_tap_coordinates(c, "conv_taps_wgrad_bf16x6");
+        if (rc) return rc;
     } else {
-        DIGA_REQUIRE(R == 1 && S == 1 && stride_y > 0 && stride_x > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: pointwise (1x1) convolutions only");
+        DIGA_REQUIRE(c.R == 1 && c.S == 1 && c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: pointwise (1x1) convolutions only");
     }
-    DIGA_REQUIRE(Cin > 0 && Cin % 8 == 0 && Cout > 0 && Cout % 8 == 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: channel counts must be multiples of 8");
-    DIGA_REQUIRE(!f32in || (dy_ld >= Cout && dy_ld % 4 == 0 && x_ld >= Cin && x_ld % 4 == 0 && dy_ld < (1ll << 31) && x_ld < (1ll << 31)),
+    DIGA_REQUIRE(c.Cin > 0 && c.Cin % 8 == 0 && c.Cout > 0 && c.Cout % 8 == 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: channel counts must be multiples of 8");
+    DIGA_REQUIRE(!c.f32in || (c.dy_ld >= c.Cout && c.dy_ld % 4 == 0 && c.x_ld >= c.Cin && c.x_ld % 4 == 0 && c.dy_ld < (1ll << 31) && c.x_ld < (1ll << 31)),
                  DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count and multiples of 4");
-    DIGA_REQUIRE(aligned16(dy_triplet) && aligned16(x_triplet) && aligned16(dw) && aligned16(workspace), DIGA_EALIGN, "conv2d_wgrad_bf16x6: alignment");
-    DIGA_REQUIRE(N * Hi * Wi < (1ll << 31) && N * Ho * Wo < (1ll << 31), DIGA_EINVAL, "conv2d_wgrad_bf16x6: too many pixels");
-    const int64_t RS = taps ? R * S : 1, M = N * Ho * Wo, M_pad = wgrad_mpad(M);
-    const WgradPlan p = plan_wgrad_x6(M, Cout, Cin, RS);
-    const size_t slab_bytes = wgrad_slab_bytes(p, Cout, Cin, RS);
-    DIGA_REQUIRE(workspace_bytes >= slab_bytes + (size_t)RS * M_pad * sizeof(int) + 64, DIGA_EWORKSPACE, "conv2d_wgrad_bf16x6: workspace too small");
+    DIGA_REQUIRE(aligned16(c.dy) && aligned16(c.x) && aligned16(c.dw) && aligned16(c.workspace), DIGA_EALIGN, "conv2d_wgrad_bf16x6: alignment");
+    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv2d_wgrad_bf16x6: too many pixels");
+    const int64_t RS = c.R * c.S, M = c.N * c.Ho * c.Wo, M_pad = wgrad_mpad(M);
+    const WgradPlan p = plan_wgrad_x6(M, c.Cout, c.Cin, RS);
+    const size_t slab_bytes = wgrad_slab_bytes(p, c.Cout, c.Cin, RS);
+    DIGA_REQUIRE(c.workspace_bytes >= slab_bytes + (size_t)RS * M_pad * sizeof(int) + 64, DIGA_EWORKSPACE, "conv2d_wgrad_bf16x6: workspace too small");
     WgradArgs a;
-    a.dy = reinterpret_cast<const float*>(dy_triplet); a.x = reinterpret_cast<const float*>(x_triplet);
-    a.slab = p.splits > 1 ? (float*)workspace : dw;
-    a.N = (int)N; a.Hi = (int)Hi; a.Wi = (int)Wi; a.Cin = (int)Cin; a.x_ld = f32in ? (int)x_ld : (int)Cin;
-    a.Ho = (int)Ho; a.Wo = (int)Wo; a.Cout = (int)Cout; a.dy_ld = f32in ? (int)dy_ld : (int)Cout;
-    a.R = taps ? (int)R : 1; a.S = taps ? (int)S : 1; a.sy = (int)stride_y; a.sx = (int)stride_x;
-    a.oy0 = (int)off_y0; a.ox0 = (int)off_x0; a.ody = (int)off_dy; a.odx = (int)off_dx;
-    a.M = (int)M; a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.splits = p.splits; a.steps_per_split = p.steps_per_split;
-    a.M_pad = (int)M_pad;
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)M * (double)Cout * (double)RS * (double)Cin);
-    // (output pixel) -> input pixel table, -1 outside the image: in bounds for any stride / offset
-    int* tab = reinterpret_cast<int*>(static_cast<char*>(workspace) + slab_bytes);
-    float* zeros = reinterpret_cast<float*>(tab + RS * M_pad);
-    hipLaunchKernelGGL(wgrad_pixtab_kernel, dim3((unsigned)ceil_div(M_pad, 256), (unsigned)RS), dim3(256), 0, st, tab, zeros, (int)M,
-                       (int)M_pad, (int)Ho, (int)Wo, (int)Hi, (int)Wi, a.S, (int)stride_y, (int)stride_x, (int)off_y0, (int)off_x0,
-                       (int)off_dy, (int)off_dx);
-    a.ptab = tab;
-    a.zeros = zeros;
-    const unsigned grid = (unsigned)((int64_t)p.tiles_m * p.tiles_n * RS * p.splits);
-    const size_t sh = (size_t)2 * (3 * kBK * 512 + 3 * kBK * 256);
-    if (f32in) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_x6_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        hipLaunchKernelGGL(conv_wgrad_x6_kernel<true>, dim3(grid), dim3(512), sh, st, a);
-    } else {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_x6_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        hipLaunchKernelGGL(conv_wgrad_x6_kernel<false>, dim3(grid), dim3(512), sh, st, a);
-    }
-    if (p.splits > 1) {
-        const int64_t n4 = Cout * RS * Cin / 4;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)workspace, dw, n4,
-                           p.splits);
-    }
-    return launch_status(taps ? "diga_conv_taps_wgrad_bf16x6_f32in" : f32in ? "diga_conv2d_wgrad_bf16x6_f32in" : "diga_conv2d_wgrad_bf16x6");
+    fill_wgrad_args(a, c, p, M_pad);
+    hipStream_t st = (hipStream_t)c.stream;
+    ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)M * (double)c.Cout * (double)RS * (double)c.Cin);
+    launch_pixtab(a, c, slab_bytes, st);
+    static const WgradKernel kX6[2] = {conv_wgrad_x6_kernel<false>, conv_wgrad_x6_kernel<true>};                    // [loader form]
+    launch_k(kX6[c.f32in], wgrad_grid(a), 512, (size_t)2 * (3 * kBK * 512 + 3 * kBK * 256), st, a);
+    launch_slab_reduce(a, static_cast<const float*>(c.workspace), c.dw, st);
+    return launch_status(c.taps ? "diga_conv_taps_wgrad_bf16x6_f32in" : c.f32in ? "diga_conv2d_wgrad_bf16x6_f32in" : "diga_conv2d_wgrad_bf16x6");
 }
 
 extern "C" int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_triplet, float* dw, void* workspace,
                                         size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
                                         int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
                                         int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
-    return conv2d_wgrad_bf16x6_impl(dy_triplet, -1, x_triplet, -1, dw, workspace, workspace_bytes, N, Hi, Wi, Cin, Ho, Wo, Cout, R, S,
-                                    stride_y, stride_x, off_y0, off_x0, off_dy, off_dx, stream);
+    WgradCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.dy = dy_triplet; c.x = x_triplet; c.dw = dw; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return conv2d_wgrad_bf16x6(c);
 }
 
 extern "C" int diga_conv2d_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
@@ -1023,15 +968,19 @@ extern "C" int diga_conv2d_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, co
                                               int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
                                               int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
     DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
-    return conv2d_wgrad_bf16x6_impl(dy, dy_ld, x, x_ld, dw, workspace, workspace_bytes, N, Hi, Wi, Cin, Ho, Wo, Cout, R, S, stride_y,
-                                    stride_x, off_y0, off_x0, off_dy, off_dx, stream);
+    WgradCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.f32in = true; c.dw = dw; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return conv2d_wgrad_bf16x6(c);
 }
 
 // The weight gradient of a multi-tap convolution on the loader form: diga_conv2d_wgrad_bf16x6_f32in's arguments with
 // 1 <= R * S <= 64, dw [Cout][R][S][Cin]; the split-K plan counts the taps (plan_wgrad_x6(M, Cout, Cin, R * S)).
 extern "C" size_t diga_conv_taps_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R,
                                                               int64_t S) {
-    if (!taps_wgrad_shape_ok(N, Ho, Wo, Cout, Cin, R, S)) return 0;
+    ConvGeometry g;
+    g.N = N; g.Ho = Ho; g.Wo = Wo; g.Cout = Cout; g.Cin = Cin; g.R = R; g.S = S;
+    if (!taps_wgrad_shape_ok(g)) return 0;
     const int64_t M = N * Ho * Wo, RS = R * S;
     return wgrad_slab_bytes(plan_wgrad_x6(M, Cout, Cin, RS), Cout, Cin, RS) + (size_t)RS * wgrad_mpad(M) * sizeof(int) + 64;
 }
@@ -1041,8 +990,11 @@ extern "C" int diga_conv_taps_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld,
                                                  int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
                                                  int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
     DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv_taps_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
-    return conv2d_wgrad_bf16x6_impl(dy, dy_ld, x, x_ld, dw, workspace, workspace_bytes, N, Hi, Wi, Cin, Ho, Wo, Cout, R, S, stride_y,
-                                    stride_x, off_y0, off_x0, off_dy, off_dx, stream, true);
+    WgradCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.f32in = c.taps = true; c.dw = dw; c.workspace = workspace;
+    c.workspace_bytes = workspace_bytes;
+    return conv2d_wgrad_bf16x6(c);
 }
 
 // ---- the Winograd-domain GEMMs on bf16x6 (winograd.hip: diga_conv2d_winograd_bf16x6 / diga_conv2d_wgrad_winograd_bf16x6)
@@ -1076,27 +1028,20 @@ int gemm_batched_bf16x6(const float* A, int64_t rows_per_batch, int batches, int
     DIGA_REQUIRE(gemm_batched_bf16x6_ok(rows_per_batch, batches, K, Cout), DIGA_EINVAL,
                  "gemm_batched_bf16x6: rows %% 256, K %% 32, Cout %% 4 (> 64) required; rows * batches and the tile count below 2^31");
     const int64_t M = rows_per_batch * batches;
+    ConvCall c;                                            // the stacked rows as an M / 256 x 256 image under a 1x1 convolution
+    c.in = A; c.in_ld = K; c.wgt_img = imgs; c.out = out; c.out_ld = Cout;
+    c.N = 1; c.Hi = c.Ho = M / 256; c.Wi = c.Wo = 256; c.Cin = K; c.Cout = Cout;
+    c.R = c.S = c.stride_y = c.stride_x = c.off_dy = c.off_dx = 1;
     ConvArgs a;
-    a.in = A; a.wgt = nullptr; a.wgt_hi = nullptr; a.wgt_lo = nullptr;
-    a.wgt_img = reinterpret_cast<const unsigned char*>(imgs); a.bias = nullptr; a.out = out; a.stats = nullptr;
-    a.N = 1; a.Hi = (int)(M / 256); a.Wi = 256; a.Cin = (int)K; a.in_ld = (int)K;
-    a.Ho = a.Hi; a.Wo = 256; a.Cout = (int)Cout; a.out_ld = (int)Cout;
-    a.R = 1; a.S = 1; a.sy = 1; a.sx = 1; a.oy0 = 0; a.ox0 = 0; a.ody = 1; a.odx = 1;
-    a.M = (int)M;
+    (void)fill_conv_args(a, c, "gemm_batched_bf16x6", "gemm_batched_bf16x6");
     a.tiles_m = (int)(M / 256);
     a.tiles_n = (int)ceil_div(Cout, 128);
     a.all_inside = 1;
-    set_options(a, nullptr);
-    {
-        const int rc = set_bwd_epilogue(a, nullptr, "gemm_batched_bf16x6");
-        if (rc) return rc;
-    }
     a.wb_tiles = (int)(rows_per_batch / 256);
     a.wb_stride = (int64_t)diga_split_bf16x6_image_bytes(Cout, 1, K);        // (bytes: the images are byte arrays)
     const size_t ring = (size_t)2 * (3 * 256 * 64 + 3 * 128 * 64);
     const size_t stg = (size_t)2 * 128 * (128 + 4) * sizeof(float);
-    const size_t sh = ring > stg ? ring : stg;
-    DIGA_LAUNCH_K((conv_fwd_x6_kernel<2, false, true, true>), 768, sh);
+    launch_k<ConvArgs>(conv_fwd_x6_kernel<2, false, true, true>, (unsigned)(a.tiles_m * a.tiles_n), 768, ring > stg ? ring : stg, st, a);
     return DIGA_OK;
 }
 
@@ -1118,24 +1063,10 @@ int wgrad_batched_bf16x6(const float* Z, const float* V, float* dU, float* slab,
                          hipStream_t st) {
     DIGA_REQUIRE(wgrad_batched_bf16x6_ok(rows, batches, Cout, Cin), DIGA_EINVAL,
                  "wgrad_batched_bf16x6: rows %% 32, Cout %% 256, Cin %% 128 required; rows and the block count below 2^31");
-    const WgradPlan p = plan_wgrad_x6(rows, Cout, Cin, batches);
     WgradArgs a;
-    a.dy = Z; a.x = V; a.slab = p.splits > 1 ? slab : dU;
-    a.N = 1; a.Hi = 1; a.Wi = (int)rows; a.Cin = (int)Cin; a.x_ld = (int)Cin;
-    a.Ho = 1; a.Wo = (int)rows; a.Cout = (int)Cout; a.dy_ld = (int)Cout;
-    a.R = 1; a.S = batches; a.sy = 1; a.sx = 1; a.oy0 = 0; a.ox0 = 0; a.ody = 1; a.odx = 1;
-    a.M = (int)rows; a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.splits = p.splits; a.steps_per_split = p.steps_per_split;
-    a.ptab = nullptr; a.zeros = nullptr; a.M_pad = (int)rows;
-    a.dy_tap_stride = rows * Cout;
-    a.x_tap_stride = rows * Cin;
-    const unsigned grid = (unsigned)((int64_t)p.tiles_m * p.tiles_n * batches * p.splits);
-    const size_t sh = (size_t)2 * (3 * kBK * 512 + 3 * kBK * 256);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_x6_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    hipLaunchKernelGGL((conv_wgrad_x6_kernel<true, true>), dim3(grid), dim3(512), sh, st, a);
-    if (p.splits > 1) {
-        const int64_t n4 = Cout * batches * Cin / 4;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)slab, dU, n4, p.splits);
-    }
+    fill_wgrad_batched(a, Z, V, dU, slab, rows, batches, Cout, Cin, plan_wgrad_x6(rows, Cout, Cin, batches));
+    launch_k<WgradArgs>(conv_wgrad_x6_kernel<true, true>, wgrad_grid(a), 512, (size_t)2 * (3 * kBK * 512 + 3 * kBK * 256), st, a);
+    launch_slab_reduce(a, slab, dU, st);
     return DIGA_OK;
 }
 

@@ -17,6 +17,7 @@
 // 256 (rows of padding tiles are zero).  HBM traffic on top of the GEMM: V is written and read once (4x the input
 // tensor), M likewise (4x the output) -- both transforms are plain bandwidth passes.
 #include "common.h"
+#include "conv_call.h"
 
 namespace diga {
 
@@ -1106,6 +1107,40 @@ WinoLayout wino_layout(const WinoGeom& g, int64_t Cin, int64_t Cout, bool x6 = f
     return l;
 }
 
+// The call records of the two launchers below.  The entry points name the shared parameters alike: DIGA_FILL_WINO copies them by name.
+struct WinoShape {
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    int64_t N = 0, H = 0, W = 0, Cin = 0, Cout = 0, dilation = 0, tile = 0;
+    const void* tile_table = nullptr;        // nullable: a kept table of diga_conv2d_winograd_tile_table
+    void* stream = nullptr;
+    bool x6 = false;                         // the Winograd-domain products on the bf16x6 GEMMs (conv_bf16x6.h)
+};
+#define DIGA_FILL_WINO(c_)                                                                                              \
+    do {                                                                                                               \
+        (c_).workspace = workspace; (c_).workspace_bytes = workspace_bytes; (c_).N = N; (c_).H = H; (c_).W = W; (c_).Cin = Cin;     \
+        (c_).Cout = Cout; (c_).dilation = dilation; (c_).tile = tile; (c_).tile_table = tile_table; (c_).stream = stream;          \
+    } while (0)
+struct WinoCall : WinoShape {                // forward / backward-data
+    const float* in = nullptr;
+    const float* wgt = nullptr;
+    const float* bias = nullptr;
+    float* out = nullptr;
+    int64_t in_ld = 0, out_ld = 0;
+    int flip = 0, reflect = 0, prof_tag = 0;
+    float* v_keep = nullptr;                 // nullable: keeps the input transform for the weight gradient
+    float* stats = nullptr;
+    const diga_bwd_epilogue_t* epi = nullptr;
+    const diga_infer_epilogue_t* infer = nullptr;
+};
+struct WinoWgradCall : WinoShape {           // weight gradient
+    const float* dy = nullptr;
+    const float* x = nullptr;                // or
+    const float* v_kept = nullptr;           // the forward's kept input transform
+    float* dw = nullptr;
+    int64_t x_ld = 0, dy_ld = 0;
+};
+
 }  // namespace wino
 }  // namespace diga
 
@@ -1117,25 +1152,28 @@ extern "C" size_t diga_conv2d_winograd_workspace_bytes(int64_t N, int64_t H, int
     return wino_layout(make_wino(N, H, W, dilation, tile), Cin, Cout).total;
 }
 
-static int winograd_impl(const float* in, const float* wgt, const float* bias, float* out, void* workspace,
-                         size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld,
-                         int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile, int flip, const diga_bwd_epilogue_t* epi, int prof_tag,
-                         void* stream, float* v_keep = nullptr, float* stats = nullptr,
-                         const void* tile_table = nullptr, int reflect = 0, const diga_infer_epilogue_t* inf = nullptr,
-                         bool x6 = false) {
+static int winograd_conv(const WinoCall& c) {
     // x6 (diga_conv2d_winograd_bf16x6 / _infer): the products on the bf16x6 GEMM; tile table, transforms, v_keep, statistics, the backward
     // epilogue and the inference epilogue as below.  Not with reflection padding (that form stays exact fp32).
+    const float *in = c.in, *wgt = c.wgt, *bias = c.bias;
+    float *out = c.out, *stats = c.stats;
+    const int64_t N = c.N, H = c.H, W = c.W, Cin = c.Cin, in_ld = c.in_ld, Cout = c.Cout, out_ld = c.out_ld, dilation = c.dilation, tile = c.tile;
+    const int flip = c.flip, reflect = c.reflect;
+    const bool x6 = c.x6;
+    const diga_bwd_epilogue_t* epi = c.epi;
+    const diga_infer_epilogue_t* inf = c.infer;
+    const void* tile_table = c.tile_table;
     DIGA_REQUIRE(!x6 || !reflect, DIGA_EINVAL, "conv2d_winograd_bf16x6: no reflection padding");
     DIGA_REQUIRE(!inf || ((tile == 4 || tile == 6) && !flip && !epi && !stats && !reflect), DIGA_EINVAL,
                  "conv2d_winograd_infer: the inference epilogue comes with the plain forward of 4x4 / 6x6 tiles");
     DIGA_REQUIRE(!reflect || (tile != 2 && !flip && !epi && dilation < H && dilation < W), DIGA_EINVAL,
                  "conv2d_winograd: reflection padding comes with the forward of 4x4 / 6x6 tiles (pad < H, W)");
-    DIGA_REQUIRE(in && wgt && out && workspace, DIGA_EINVAL, "conv2d_winograd: null pointer");
+    DIGA_REQUIRE(in && wgt && out && c.workspace, DIGA_EINVAL, "conv2d_winograd: null pointer");
     DIGA_REQUIRE(N > 0 && H > 0 && W > 0 && dilation > 0 && dilation < 4096, DIGA_EINVAL, "conv2d_winograd: bad shape");
     DIGA_REQUIRE(tile_ok(tile), DIGA_EINVAL, "conv2d_winograd: tile must be 2, 4 or 6 (F(2x2,3x3) / F(4x4,3x3) / F(6x6,3x3))");
     DIGA_REQUIRE(Cin % 32 == 0 && Cout % 4 == 0 && Cout > 64 && in_ld >= Cin && in_ld % 4 == 0 && out_ld >= Cout && out_ld % 4 == 0,
                  DIGA_EINVAL, "conv2d_winograd: Cin %% 32, Cout %% 4 (> 64) and leading dimensions %% 4 required");
-    DIGA_REQUIRE(aligned16(in) && aligned16(wgt) && aligned16(out) && aligned16(workspace) && (!bias || aligned16(bias)), DIGA_EALIGN,
+    DIGA_REQUIRE(aligned16(in) && aligned16(wgt) && aligned16(out) && aligned16(c.workspace) && (!bias || aligned16(bias)), DIGA_EALIGN,
                  "conv2d_winograd: pointers must be 16-byte aligned");
     DIGA_REQUIRE(N * H * W < (1ll << 31), DIGA_EINVAL, "conv2d_winograd: too many pixels");
     const WinoGeom g = make_wino(N, H, W, dilation, tile);
@@ -1144,18 +1182,18 @@ static int winograd_impl(const float* in, const float* wgt, const float* bias, f
     DIGA_REQUIRE(!x6 || gemm_batched_bf16x6_ok(g.Tp, P, Cin, Cout), DIGA_EINVAL,
                  "conv2d_winograd_bf16x6: products * padded tiles and the GEMM's tile count must stay below 2^31");
     const WinoLayout l = wino_layout(g, Cin, Cout, x6);
-    DIGA_REQUIRE(workspace_bytes >= l.total, DIGA_EWORKSPACE, "conv2d_winograd: workspace too small (%zu < %zu)", workspace_bytes, l.total);
+    DIGA_REQUIRE(c.workspace_bytes >= l.total, DIGA_EWORKSPACE, "conv2d_winograd: workspace too small (%zu < %zu)", c.workspace_bytes, l.total);
     DIGA_REQUIRE(!stats || (epi == nullptr && tile != 2 && aligned16(stats)), DIGA_EINVAL,
                  "conv2d_winograd: statistics come with the forward output transform of 4x4 / 6x6 tiles (16-byte aligned buffer)");
     DIGA_REQUIRE(!tile_table || aligned16(tile_table), DIGA_EALIGN, "conv2d_winograd: tile_table must be 16-byte aligned");
-    char* ws = static_cast<char*>(workspace);
+    char* ws = static_cast<char*>(c.workspace);
     const int4* tab = tile_table != nullptr ? static_cast<const int4*>(tile_table) : reinterpret_cast<const int4*>(ws + l.tab);
     float* U = reinterpret_cast<float*>(ws + l.U);
-    float* V = v_keep != nullptr ? v_keep : reinterpret_cast<float*>(ws + l.V);
+    float* V = c.v_keep != nullptr ? c.v_keep : reinterpret_cast<float*>(ws + l.V);
     float* Mb = reinterpret_cast<float*>(ws + l.M);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     // priced as the direct convolution it replaces (the algorithmic FLOPs of the layer)
-    ProfScope prof(prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD, st,
+    ProfScope prof(c.prof_tag == DIGA_PROF_CONV_BWD_DATA ? DIGA_PROF_CONV_BWD_DATA : DIGA_PROF_CONV_FWD, st,
                    2.0 * (double)(N * H * W) * (double)Cout * 9.0 * (double)Cin);
     // (the table depends on the geometry only: a caller that keeps one per geometry -- diga_conv2d_winograd_tile_table -- saves the launch)
     if (tile_table == nullptr)
@@ -1233,8 +1271,11 @@ extern "C" int diga_conv2d_winograd_f32(const float* in, const float* wgt, const
                                         size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld,
                                         int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile, int flip, float* stats_partial,
                                         const void* tile_table, int prof_tag, void* stream) {
-    return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, flip, nullptr,
-                         prof_tag, stream, nullptr, stats_partial, tile_table);
+    WinoCall c;
+    DIGA_FILL_WINO(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.flip = flip; c.stats = stats_partial;
+    c.prof_tag = prof_tag;
+    return winograd_conv(c);
 }
 
 extern "C" int diga_conv2d_winograd_f32_opts(const float* in, const float* wgt, const float* bias, float* out, void* workspace,
@@ -1244,8 +1285,11 @@ extern "C" int diga_conv2d_winograd_f32_opts(const float* in, const float* wgt, 
     DIGA_REQUIRE(opts != nullptr, DIGA_EINVAL, "conv2d_winograd_opts: null options");
     DIGA_REQUIRE(opts->upsample_shift == 0 && opts->activation == 0, DIGA_EINVAL,
                  "conv2d_winograd_opts: only reflect_pad is folded on the Winograd path (upsampling / tanh: the direct `_opts` kernels)");
-    return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, 0, nullptr,
-                         prof_tag, stream, nullptr, nullptr, tile_table, opts->reflect_pad ? 1 : 0);
+    WinoCall c;
+    DIGA_FILL_WINO(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.reflect = opts->reflect_pad ? 1 : 0;
+    c.prof_tag = prof_tag;
+    return winograd_conv(c);
 }
 
 extern "C" int diga_conv2d_winograd_f32_infer(const float* in, const float* wgt, const float* bias, float* out, void* workspace,
@@ -1253,13 +1297,12 @@ extern "C" int diga_conv2d_winograd_f32_infer(const float* in, const float* wgt,
                                               int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile,
                                               const diga_infer_epilogue_t* infer, const void* tile_table, int prof_tag, void* stream) {
     DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_winograd_infer: null epilogue descriptor");
-    DIGA_REQUIRE(infer->ab != nullptr && aligned16(infer->ab), DIGA_EINVAL,
-                 "conv2d_winograd_infer: the inference epilogue needs 16-byte aligned coefficients ab [2][Cout]");
-    DIGA_REQUIRE(!infer->residual || (aligned16(infer->residual) && infer->residual_ld >= Cout && infer->residual_ld % 4 == 0 &&
-                                      infer->residual != out),
-                 DIGA_EINVAL, "conv2d_winograd_infer: bad residual (16-byte aligned, residual_ld %% 4 == 0 and >= Cout, not the output)");
-    return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, 0, nullptr,
-                         prof_tag, stream, nullptr, nullptr, tile_table, 0, infer);
+    const int rc = check_infer_epilogue(infer, Cout, out, "conv2d_winograd_infer");
+    if (rc) return rc;
+    WinoCall c;
+    DIGA_FILL_WINO(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.infer = infer; c.prof_tag = prof_tag;
+    return winograd_conv(c);
 }
 
 extern "C" size_t diga_conv2d_winograd_v_floats(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t dilation, int64_t tile) {
@@ -1272,8 +1315,11 @@ extern "C" int diga_conv2d_winograd_f32_keep(const float* in, const float* wgt, 
                                              int64_t in_ld, int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile,
                                              float* stats_partial, const void* tile_table, int prof_tag, void* stream) {
     DIGA_REQUIRE(v_keep != nullptr && aligned16(v_keep), DIGA_EINVAL, "conv2d_winograd_keep: v_keep must be a 16-byte aligned buffer");
-    return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, 0, nullptr,
-                         prof_tag, stream, v_keep, stats_partial, tile_table);
+    WinoCall c;
+    DIGA_FILL_WINO(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.v_keep = v_keep; c.stats = stats_partial;
+    c.prof_tag = prof_tag;
+    return winograd_conv(c);
 }
 
 extern "C" int diga_conv2d_winograd_f32_epi(const float* in, const float* wgt, float* out, void* workspace, size_t workspace_bytes,
@@ -1281,18 +1327,12 @@ extern "C" int diga_conv2d_winograd_f32_epi(const float* in, const float* wgt, f
                                             int64_t out_ld, int64_t dilation, int64_t tile, int flip, const diga_bwd_epilogue_t* e,
                                             const void* tile_table, int prof_tag, void* stream) {
     DIGA_REQUIRE(e != nullptr, DIGA_EINVAL, "conv2d_winograd_epi: null epilogue descriptor");
-    DIGA_REQUIRE(e->addend || e->mask_y || e->mask_bits || e->x, DIGA_EINVAL, "conv2d_winograd_epi: empty epilogue descriptor");
-    DIGA_REQUIRE(!e->addend || (aligned16(e->addend) && e->addend_ld >= Cout && e->addend_ld % 4 == 0), DIGA_EINVAL, "conv2d_winograd_epi: bad addend");
-    DIGA_REQUIRE(!e->mask_y || (aligned16(e->mask_y) && e->mask_ld >= Cout && e->mask_ld % 4 == 0), DIGA_EINVAL, "conv2d_winograd_epi: bad mask_y");
-    DIGA_REQUIRE(!e->x || (aligned16(e->x) && e->x_ld >= Cout && e->x_ld % 4 == 0), DIGA_EINVAL, "conv2d_winograd_epi: bad x");
-    DIGA_REQUIRE((e->mask_y != nullptr) + (e->relu_ab != nullptr) + (e->mask_bits != nullptr) <= 1, DIGA_EINVAL,
-                 "conv2d_winograd_epi: give one of mask_y, mask_bits, relu_ab");
-    DIGA_REQUIRE(!e->mask_bits || e->mask_bits_ld * 8 >= Cout, DIGA_EINVAL, "conv2d_winograd_epi: bad mask_bits");
-    DIGA_REQUIRE(!e->relu_ab || (e->x && aligned16(e->relu_ab)), DIGA_EINVAL, "conv2d_winograd_epi: relu_ab needs x");
-    DIGA_REQUIRE(!e->partials || (e->x && e->mean && e->invstd && aligned16(e->mean) && aligned16(e->invstd)), DIGA_EINVAL,
-                 "conv2d_winograd_epi: partials need x, mean and invstd");
-    return winograd_impl(in, wgt, nullptr, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, flip, e, prof_tag,
-                         stream, nullptr, nullptr, tile_table);
+    const int rc = check_bwd_epilogue(e, Cout, "conv2d_winograd_epi");
+    if (rc) return rc;
+    WinoCall c;
+    DIGA_FILL_WINO(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.out = out; c.out_ld = out_ld; c.flip = flip; c.epi = e; c.prof_tag = prof_tag;
+    return winograd_conv(c);
 }
 
 extern "C" size_t diga_conv2d_wgrad_winograd_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
@@ -1301,10 +1341,13 @@ extern "C" size_t diga_conv2d_wgrad_winograd_workspace_bytes(int64_t N, int64_t 
     return wino_wgrad_layout(make_wino(N, H, W, dilation, tile), Cin, Cout, v_kept == 0).total;
 }
 
-static int wgrad_winograd_impl(const float* dy, const float* x, const float* v_kept, float* dw, void* workspace,
-                               size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t x_ld,
-                               int64_t Cout, int64_t dy_ld, int64_t dilation, int64_t tile, const void* tile_table, void* stream,
-                               bool x6 = false) {
+static int winograd_wgrad(const WinoWgradCall& c) {
+    const float *dy = c.dy, *x = c.x, *v_kept = c.v_kept;
+    float* dw = c.dw;
+    void* workspace = c.workspace;
+    const int64_t N = c.N, H = c.H, W = c.W, Cin = c.Cin, x_ld = c.x_ld, Cout = c.Cout, dy_ld = c.dy_ld, dilation = c.dilation, tile = c.tile;
+    const void* tile_table = c.tile_table;
+    const bool x6 = c.x6;
     DIGA_REQUIRE(!tile_table || aligned16(tile_table), DIGA_EALIGN, "conv2d_wgrad_winograd: tile_table must be 16-byte aligned");
     DIGA_REQUIRE(dy && (x || v_kept) && dw && workspace, DIGA_EINVAL, "conv2d_wgrad_winograd: null pointer");
     DIGA_REQUIRE(!v_kept || aligned16(v_kept), DIGA_EALIGN, "conv2d_wgrad_winograd: v_kept must be 16-byte aligned");
@@ -1318,7 +1361,7 @@ static int wgrad_winograd_impl(const float* dy, const float* x, const float* v_k
     DIGA_REQUIRE(!x6 || wgrad_batched_bf16x6_ok(g.Tp, products(tile), Cout, Cin), DIGA_EINVAL,
                  "conv2d_wgrad_winograd_bf16x6: padded tiles and the GEMM's block count must stay below 2^31");
     const WinoWgradLayout l = wino_wgrad_layout(g, Cin, Cout, v_kept == nullptr, x6);
-    DIGA_REQUIRE(workspace_bytes >= l.total, DIGA_EWORKSPACE, "conv2d_wgrad_winograd: workspace too small (%zu < %zu)", workspace_bytes,
+    DIGA_REQUIRE(c.workspace_bytes >= l.total, DIGA_EWORKSPACE, "conv2d_wgrad_winograd: workspace too small (%zu < %zu)", c.workspace_bytes,
                  l.total);
     char* ws = static_cast<char*>(workspace);
     const int4* tab = tile_table != nullptr ? static_cast<const int4*>(tile_table) : reinterpret_cast<const int4*>(ws + l.tab);
@@ -1326,7 +1369,7 @@ static int wgrad_winograd_impl(const float* dy, const float* x, const float* v_k
     float* Z = reinterpret_cast<float*>(ws + l.Z);
     float* dU = reinterpret_cast<float*>(ws + l.dU);
     float* slab = reinterpret_cast<float*>(ws + l.slab);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)(N * H * W) * (double)Cout * 9.0 * (double)Cin);
     if (tile_table == nullptr)
         hipLaunchKernelGGL(wino_tiles_kernel, dim3((unsigned)ceil_div(g.Tp, 256)), dim3(256), 0, st, reinterpret_cast<int4*>(ws + l.tab), g);
@@ -1351,8 +1394,10 @@ extern "C" int diga_conv2d_wgrad_winograd_f32(const float* dy, const float* x, c
                                               size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t x_ld,
                                               int64_t Cout, int64_t dy_ld, int64_t dilation, int64_t tile, const void* tile_table,
                                               void* stream) {
-    return wgrad_winograd_impl(dy, x, v_kept, dw, workspace, workspace_bytes, N, H, W, Cin, x_ld, Cout, dy_ld, dilation, tile,
-                               tile_table, stream);
+    WinoWgradCall c;
+    DIGA_FILL_WINO(c);
+    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.v_kept = v_kept; c.dw = dw;
+    return winograd_wgrad(c);
 }
 
 // ---- the same layers with the Winograd-domain products on bf16x6 (conv_bf16x6.h; include/diga_hip.h)
@@ -1373,21 +1418,14 @@ extern "C" int diga_conv2d_winograd_bf16x6(const float* in, const float* wgt, co
                                            void* stream) {
     DIGA_REQUIRE(!v_keep || aligned16(v_keep), DIGA_EALIGN, "conv2d_winograd_bf16x6: v_keep must be 16-byte aligned");
     DIGA_REQUIRE(!v_keep || (!flip && !e), DIGA_EINVAL, "conv2d_winograd_bf16x6: v_keep comes with the forward (flip = 0, no epilogue)");
-    if (e != nullptr) {
-        DIGA_REQUIRE(!bias && !stats_partial, DIGA_EINVAL, "conv2d_winograd_bf16x6: a backward epilogue takes no bias and no statistics");
-        DIGA_REQUIRE(e->addend || e->mask_y || e->mask_bits || e->x, DIGA_EINVAL, "conv2d_winograd_bf16x6: empty epilogue descriptor");
-        DIGA_REQUIRE(!e->addend || (aligned16(e->addend) && e->addend_ld >= Cout && e->addend_ld % 4 == 0), DIGA_EINVAL, "conv2d_winograd_bf16x6: bad addend");
-        DIGA_REQUIRE(!e->mask_y || (aligned16(e->mask_y) && e->mask_ld >= Cout && e->mask_ld % 4 == 0), DIGA_EINVAL, "conv2d_winograd_bf16x6: bad mask_y");
-        DIGA_REQUIRE(!e->x || (aligned16(e->x) && e->x_ld >= Cout && e->x_ld % 4 == 0), DIGA_EINVAL, "conv2d_winograd_bf16x6: bad x");
-        DIGA_REQUIRE((e->mask_y != nullptr) + (e->relu_ab != nullptr) + (e->mask_bits != nullptr) <= 1, DIGA_EINVAL,
-                     "conv2d_winograd_bf16x6: give one of mask_y, mask_bits, relu_ab");
-        DIGA_REQUIRE(!e->mask_bits || e->mask_bits_ld * 8 >= Cout, DIGA_EINVAL, "conv2d_winograd_bf16x6: bad mask_bits");
-        DIGA_REQUIRE(!e->relu_ab || (e->x && aligned16(e->relu_ab)), DIGA_EINVAL, "conv2d_winograd_bf16x6: relu_ab needs x");
-        DIGA_REQUIRE(!e->partials || (e->x && e->mean && e->invstd && aligned16(e->mean) && aligned16(e->invstd)), DIGA_EINVAL,
-                     "conv2d_winograd_bf16x6: partials need x, mean and invstd");
-    }
-    return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, flip, e, prof_tag,
-                         stream, v_keep, stats_partial, tile_table, 0, nullptr, true);
+    DIGA_REQUIRE(!e || (!bias && !stats_partial), DIGA_EINVAL, "conv2d_winograd_bf16x6: a backward epilogue takes no bias and no statistics");
+    const int rc = check_bwd_epilogue(e, Cout, "conv2d_winograd_bf16x6");
+    if (rc) return rc;
+    WinoCall c;
+    DIGA_FILL_WINO(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.flip = flip; c.v_keep = v_keep;
+    c.stats = stats_partial; c.epi = e; c.prof_tag = prof_tag; c.x6 = true;
+    return winograd_conv(c);
 }
 
 // diga_conv2d_winograd_f32_infer with the products on the bf16x6 GEMM: the batched GEMM of diga_conv2d_winograd_bf16x6, then the
@@ -1397,13 +1435,12 @@ extern "C" int diga_infer_conv2d_winograd_bf16x6(const float* in, const float* w
                                                  int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile,
                                                  const diga_infer_epilogue_t* infer, const void* tile_table, int prof_tag, void* stream) {
     DIGA_REQUIRE(infer != nullptr, DIGA_EINVAL, "conv2d_winograd_bf16x6_infer: null epilogue descriptor");
-    DIGA_REQUIRE(infer->ab != nullptr && aligned16(infer->ab), DIGA_EINVAL,
-                 "conv2d_winograd_bf16x6_infer: the inference epilogue needs 16-byte aligned coefficients ab [2][Cout]");
-    DIGA_REQUIRE(!infer->residual || (aligned16(infer->residual) && infer->residual_ld >= Cout && infer->residual_ld % 4 == 0 &&
-                                      infer->residual != out),
-                 DIGA_EINVAL, "conv2d_winograd_bf16x6_infer: bad residual (16-byte aligned, residual_ld %% 4 == 0 and >= Cout, not the output)");
-    return winograd_impl(in, wgt, bias, out, workspace, workspace_bytes, N, H, W, Cin, in_ld, Cout, out_ld, dilation, tile, 0, nullptr,
-                         prof_tag, stream, nullptr, nullptr, tile_table, 0, infer, true);
+    const int rc = check_infer_epilogue(infer, Cout, out, "conv2d_winograd_bf16x6_infer");
+    if (rc) return rc;
+    WinoCall c;
+    DIGA_FILL_WINO(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.infer = infer; c.prof_tag = prof_tag; c.x6 = true;
+    return winograd_conv(c);
 }
 
 extern "C" size_t diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
@@ -1420,6 +1457,8 @@ extern "C" int diga_conv2d_wgrad_winograd_bf16x6(const float* dy, const float* x
                                                  size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t x_ld,
                                                  int64_t Cout, int64_t dy_ld, int64_t dilation, int64_t tile, const void* tile_table,
                                                  void* stream) {
-    return wgrad_winograd_impl(dy, x, v_kept, dw, workspace, workspace_bytes, N, H, W, Cin, x_ld, Cout, dy_ld, dilation, tile,
-                               tile_table, stream, true);
+    WinoWgradCall c;
+    DIGA_FILL_WINO(c);
+    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.v_kept = v_kept; c.dw = dw; c.x6 = true;
+    return winograd_wgrad(c);
 }
