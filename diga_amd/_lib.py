@@ -90,6 +90,9 @@ SIGNATURES = {
     "diga_infer_conv_taps_bf16x6_f32in": (INT, [P, I64, P, P, P] + [I64] * 16 + [P, INT, P]),
     "diga_conv_taps_wgrad_bf16x6_workspace_bytes": (SZ, [I64] * 7),
     "diga_conv_taps_wgrad_bf16x6_f32in": (INT, [P, I64, P, I64, P, P, SZ] + [I64] * 15 + [P]),
+    "diga_wgrad_bf16x6_tile": (INT, [I64, I64, P, P]),
+    "diga_wgrad_bf16x6_tiled_workspace_bytes": (SZ, [I64] * 7),
+    "diga_wgrad_bf16x6_tiled_f32in": (INT, [P, I64, P, I64, P, P, SZ] + [I64] * 15 + [P]),
     "diga_im2col_nchw": (INT, [P, P] + [I64] * 11 + [P]),
     "diga_norm_workspace_bytes": (SZ, [I64, I64, I64]),
     "diga_bn_fwd": (INT, [P, I64, P, I64, P, I64, P, P, P, P, P, P, P, I64, I64, INT, INT, INT, P, F32, F32, P, SZ, P]),

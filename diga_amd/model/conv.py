@@ -88,6 +88,18 @@ def _taps_ok(cin, r, s, copt):
     return 1 < r * s <= 64 and cin % 32 == 0 and not copt
 
 
+def _x6_fit(kp, cp):
+    """True when config.x6_wgrad_tile = "fit" is in force (conv_math = 2; both read per call) AND the library's tile rule
+    (diga_wgrad_bf16x6_tile, the one place that decides) gives a layer with kp (padded) output and cp input channels something other
+    than the 256 x 128 tile: its loader-form weight gradient ("x6ls" / "x6rs") then runs on diga_wgrad_bf16x6_tiled_f32in.  The pass
+    form ("x6"), Winograd and every forward / backward-data call never ask."""
+    if _lib.get_conv_math() != 2 or config.active().x6_wgrad_tile != "fit":
+        return False
+    bm, bn = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.call("diga_wgrad_bf16x6_tile", kp, cp, ctypes.byref(bm), ctypes.byref(bn))
+    return (bm.value, bn.value) != (256, 128)
+
+
 def _x6_loader():
     """bf16x6 operand form of the active configuration (config.x6_split, read per call): True = "loader", the GEMMs' loader waves
     split the fp32 tensors themselves (the `_f32in` entry points: no triplet pass, no triplet buffer, channel slices read in place);
@@ -145,7 +157,8 @@ flop_log = None
 # arithmetic in "f32" / "bf16x3" / "bf16x6" / "bf16x6/ls" (bf16x6 with the operands split by the loader waves, config.x6_split = "loader") /
 # "winograd" / "winograd/x6" (the Winograd path with its products on bf16x6, config.x6_winograd); "f32+bn" / "winograd+bn": a forward with the eval-mode BatchNorm behind it
 # folded into its epilogue (config.fold_eval_bn); "bf16x6+bn" / "bf16x6/ls+bn" / "winograd/x6+bn": the same on the bf16x6 kernels
-# (config.fold_eval_bn_x6); "bf16x6/taps" / "bf16x6/taps+bn": a multi-tap call on the bf16x6 kernels (config.x6_taps)
+# (config.fold_eval_bn_x6); "bf16x6/taps" / "bf16x6/taps+bn": a multi-tap call on the bf16x6 kernels (config.x6_taps);
+# "bf16x6/ls/fit" / "bf16x6/taps/fit" (wgrad only): the loader-form weight gradient on a narrow tile (config.x6_wgrad_tile = "fit")
 path_log = None
 
 
@@ -284,6 +297,7 @@ class _Path(NamedTuple):
     ratio: float = 1.0
     x6w: bool = False          # Winograd: the Winograd-domain products run on bf16x6 (_wino_x6)
     flops: bool = True         # counted in flop_log (all but the bf16x3 forward / backward-data kernels, the twin weight gradient, the stem's)
+    fit: bool = False          # weight gradient of "x6ls" / "x6rs": on the narrow tile of diga_wgrad_bf16x6_tiled_f32in (_x6_fit)
 
 
 def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, stats=None, epi=False, opts=None, infer=False,
@@ -350,11 +364,14 @@ def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, sta
 def _wgrad_plan(n, hi, wi, cp, kp, r, s, stride, padding, dilation, ho, wo, x_twin=False, stem=False):
     """_plan's sibling for the weight gradient of a layer with (padded) cp input and kp output channels.  x_twin: the forward left
     the split twin of its input and the layer may use it (bf16x3); stem: the im2col GEMM of _StemConvFn, which stays off bf16x6
-    unless config.x6_taps is on."""
+    unless config.x6_taps is on.  A loader-form bf16x6 answer ("x6ls" / "x6rs") carries fit = _x6_fit(kp, cp), read now: nothing the
+    forward saved depends on it."""
     stem_x6 = stem and _x6_taps()
     math = _layer_math(r, s, cp, not stem or stem_x6)
     if math == 2:
-        return _Path("x6ls", "", 2, "bf16x6/ls") if (_x6_loader() or stem_x6) else _Path("x6", "", 2, "bf16x6")
+        if _x6_loader() or stem_x6:
+            return _Path("x6ls", "", 2, "bf16x6/ls/fit", fit=True) if _x6_fit(kp, cp) else _Path("x6ls", "", 2, "bf16x6/ls")
+        return _Path("x6", "", 2, "bf16x6")
     if math == 1 and x_twin:
         return _Path("twin", "", 1, "bf16x3", flops=False)
     if (math == 0 and kp % 256 == 0 and cp % 128 == 0
@@ -363,7 +380,7 @@ def _wgrad_plan(n, hi, wi, cp, kp, r, s, stride, padding, dilation, ho, wo, x_tw
         x6w = _wino_x6()                               # (read per call: a kept V is fp32 whichever arithmetic the forward ran)
         return _Path("winograd", "", 0, "winograd/x6" if x6w else "winograd", tile, ratio, x6w)
     if math == 0 and _x6_taps() and _taps_ok(cp, r, s, False):
-        return _Path("x6rs", "", 2, "bf16x6/taps")
+        return _Path("x6rs", "", 2, "bf16x6/taps/fit", fit=True) if _x6_fit(kp, cp) else _Path("x6rs", "", 2, "bf16x6/taps")
     return _Path("f32", "", math, "bf16x3" if math == 1 else "f32", flops=not stem)
 
 
@@ -567,6 +584,7 @@ _WGRAD = {
     "twin": ("diga_conv2d_wgrad_twin", _lib.lib.diga_conv2d_wgrad_twin_workspace_bytes),
     "f32": ("diga_conv2d_wgrad_nhwc_f32", _lib.lib.diga_conv2d_wgrad_workspace_bytes),
 }
+_WGRAD_FIT = ("diga_wgrad_bf16x6_tiled_f32in", _lib.lib.diga_wgrad_bf16x6_tiled_workspace_bytes)      # _Path.fit ("x6ls" / "x6rs")
 _WGRAD_WINOGRAD = {
     False: ("diga_conv2d_wgrad_winograd_f32", _lib.lib.diga_conv2d_wgrad_winograd_workspace_bytes),
     True: ("diga_conv2d_wgrad_winograd_bf16x6", _lib.lib.diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes),
@@ -589,7 +607,7 @@ def _wgrad_launch(path, gy, x, dwp, r, s, stride, padding, dilation, splits=None
         _lib.call(name, _lib.ptr(gy), _lib.ptr(x), _lib.ptr(wino_v), _lib.ptr(dwp), _lib.ptr(ws), ws.numel(), n, hi, wi, cp, x.stride(2),
                   kp, gy.stride(2), dilation[0], path.tile, _lib.ptr(tab), _lib.stream())
         return
-    name, size = _WGRAD[path.family]
+    name, size = _WGRAD_FIT if path.fit else _WGRAD[path.family]
     ws = _lib.workspace(size(n, ho, wo, kp, cp, r, s), x.device, "wgrad")
     f32 = path.family == "f32"                         # (reads pitched fp32 tensors and takes the layer's arithmetic)
     if path.family in ("x6ls", "x6rs"):                # fp32 dy and x as they are (a saved triplet of x, if any, is ignored)

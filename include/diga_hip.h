@@ -571,6 +571,27 @@ int diga_conv_taps_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const floa
                                       int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0,
                                       int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream);
 
+/* The loader-form weight gradient on the tile that fits the layer (opt-in: StepConfig.x6_wgrad_tile = "fit" under conv_math = 2).
+ * The two entry points above run one tile, 256 (Cout) x 128 (Cin); a narrow layer pays six MFMAs per product on the padding.
+ *
+ * diga_wgrad_bf16x6_tile: a pure query, the one statement of the tile rule.  *bm = 64 if Cout <= 64, 128 if Cout <= 128, else 256;
+ *   *bn = 64 if Cin <= 64, else 128; (128, 64) is not built and answers (128, 128).  Non-positive or non-multiple-of-8 channel
+ *   counts, null pointers: DIGA_EINVAL.
+ * diga_wgrad_bf16x6_tiled_f32in: the argument list and checks of diga_conv_taps_wgrad_bf16x6_f32in with 1 <= R * S <= 64,
+ *   Cin % 32 == 0 when R * S > 1, else Cin % 8 == 0, and Cout % 8 == 0.  A shape whose tile is (256, 128) runs exactly what
+ *   diga_conv2d_wgrad_bf16x6_f32in (R * S = 1) / diga_conv_taps_wgrad_bf16x6_f32in run.  Any other tile runs the same arithmetic --
+ *   product order, fold accumulator, clamps, slab layout, fixed-order reduce -- on its own split-K plan: at least 8 K-steps per
+ *   block, at most 512 ranges, about two rounds of resident blocks (3 / 2 / 1 / 1 blocks per CU at 64x64 / 64x128 / 128x128 / 256x64).  Where both
+ *   plans cut the pixels into the same ranges dw is bit-identical to the wide tile's; otherwise it is another split-K tree of the
+ *   same error level.
+ * diga_wgrad_bf16x6_tiled_workspace_bytes: its workspace; 0 for a shape the entry point rejects. */
+int diga_wgrad_bf16x6_tile(int64_t Cout, int64_t Cin, int* bm, int* bn);
+size_t diga_wgrad_bf16x6_tiled_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R, int64_t S);
+int diga_wgrad_bf16x6_tiled_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
+                                  size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo,
+                                  int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0,
+                                  int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream);
+
 /* bf16x6 for the Winograd-domain GEMMs of the stride-1 3x3 layers (opt-in: StepConfig.x6_winograd under conv_math = 2).  The
  * Winograd transforms stay fp32; the (tile + 2)^2 products per layer run on the loader-split bf16x6 kernels in ONE batched launch.
  *

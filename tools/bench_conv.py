@@ -4,6 +4,7 @@ geometries of ResNet-101 DeepLabV2 at the C2 size (16 images of 768x768 -> 193x1
 
     python tools/bench_conv.py [--images 16] [--reps 5] [--math f32|bf16x3|bf16x6] [--x6-split pass|loader] [--pointwise-only]
                                  [--x6-winograd] [--winograd-only] [--x6-taps] [--no-winograd] [--winograd-max-tile 2|4|6] [--taps-only]
+                                 [--x6-wgrad-tile wide|fit] [--narrow-only]
 Prints one line per (shape, pass): ms, TFLOP/s, fraction of the 157.3 TFLOP/s fp32 MFMA peak, and the
 share of a training step's conv time that shape accounts for (count x time).
 --math bf16x6: the pointwise layers run on bf16x6, the rest on the exact-fp32 paths; the operand split passes are part of the
@@ -16,8 +17,12 @@ weight-image split is inside the timed calls.  --winograd-only: time the rows th
 the weight-image split of the backward (booked as elementwise) is added to dgrad as for the pointwise rows.  --no-winograd sets
 config.winograd = False for the run (every 3x3 row on the direct kernels -- or, with --x6-taps, on the multi-tap bf16x6 kernels);
 --winograd-max-tile 2 is the F(2x2,3x3) cap of the "exact" setting.  --taps-only: time the rows with more than one tap only.
+--x6-wgrad-tile fit (with --math bf16x6): the loader-form weight gradients on the tile that fits the layer (config.x6_wgrad_tile); the rows
+whose weight gradient ran on a narrow tile are marked `fit` and summed on a line of their own.  --narrow-only: time the rows whose
+(padded) channel counts pick a narrow tile only -- in any arithmetic, so the same rows can be timed in mode 0.
 """
 import argparse
+import ctypes
 import os
 import sys
 
@@ -59,6 +64,13 @@ def timed(fn, reps):
     return s.elapsed_time(e) / reps
 
 
+def _wgrad_tile(cout, cin):
+    """diga_wgrad_bf16x6_tile: the (BM, BN) tile config.x6_wgrad_tile = "fit" gives a weight gradient of these (padded) channel counts."""
+    bm, bn = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.call("diga_wgrad_bf16x6_tile", cout, cin, ctypes.byref(bm), ctypes.byref(bn))
+    return bm.value, bn.value
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=16)
@@ -73,11 +85,14 @@ def main():
     ap.add_argument("--no-winograd", action="store_true", help="config.winograd = False for the run")
     ap.add_argument("--winograd-max-tile", type=int, default=None, choices=[2, 4, 6], help="config.winograd_max_tile for the run")
     ap.add_argument("--taps-only", action="store_true", help="time the rows with more than one tap only (what --x6-taps can change)")
+    ap.add_argument("--x6-wgrad-tile", default="wide", choices=["wide", "fit"], help="tile of the loader-form bf16x6 weight gradient (config.x6_wgrad_tile)")
+    ap.add_argument("--narrow-only", action="store_true", help="time the rows that pick a narrow weight-gradient tile only (what --x6-wgrad-tile can change)")
     a = ap.parse_args()
     _lib.set_conv_math(a.math)
     config.active().x6_split = a.x6_split
     config.active().x6_winograd = a.x6_winograd
     config.active().x6_taps = a.x6_taps
+    config.active().x6_wgrad_tile = a.x6_wgrad_tile
     if a.no_winograd:
         config.active().winograd = False
     if a.winograd_max_tile is not None:
@@ -89,9 +104,15 @@ def main():
     pw = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the pointwise (1x1) rows alone
     wn = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the rows on the Winograd path (aspp.d24 stays direct: its ratio)
     tp = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the rows with more than one tap
+    nr = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}                 # the rows that pick a narrow weight-gradient tile
+    pad32 = lambda c: (c + 31) // 32 * 32  # noqa: E731
     for name, count, cin, cout, k, stride, dil, hw in SHAPES:
         wino_row = k == 3 and stride == 1 and cin >= 128 and cout >= 128 and name != "aspp.d24"
         if (a.only and a.only not in name) or (a.pointwise_only and k != 1) or (a.winograd_only and not wino_row) or (a.taps_only and k == 1):
+            continue
+        # the tile of the layer's weight-gradient GEMM (the stem's is the im2col GEMM: k * k * cin columns); the library's rule
+        narrow = _wgrad_tile(pad32(cout), pad32(cin * k * k if cin == 3 else cin)) != (256, 128)
+        if a.narrow_only and not narrow:
             continue
         pad = dil * (k - 1) // 2
         m = DigaConv2d(cin, cout, k, stride=stride, padding=pad, dilation=dil, bias=False).to(dev)
@@ -127,12 +148,13 @@ def main():
         t_d = td / nd if nd else 0.0
         t_w = tw / nw if nw else 0.0
         on_taps = any(arith.startswith("bf16x6") for (p, arith) in dc.path_log if p in ("dgrad", "wgrad"))
+        on_fit = any(arith.endswith("/fit") for (p, arith) in dc.path_log if p == "wgrad")
         dc.path_log = None
         if a.math == "bf16x6" and (k == 1 or (a.x6_taps and on_taps)):
             # the split passes of the backward (triplet of dy, the weight image; booked as elementwise) belong to the layer's time
             ne, te = _lib.prof_query("elementwise")
             t_d += te / a.reps
-        rows.append((name, count, flops, t_f, t_d, t_w))
+        rows.append((name, count, flops, t_f, t_d, t_w, on_fit))
         tot["fwd"] += count * t_f
         tot["dgrad"] += count * t_d
         tot["wgrad"] += count * t_w
@@ -144,6 +166,10 @@ def main():
             tp["fwd"] += count * t_f
             tp["dgrad"] += count * t_d
             tp["wgrad"] += count * t_w
+        if narrow:
+            nr["fwd"] += count * t_f
+            nr["dgrad"] += count * t_d
+            nr["wgrad"] += count * t_w
         if wino_row:
             wn["fwd"] += count * t_f
             wn["dgrad"] += count * t_d
@@ -152,16 +178,17 @@ def main():
         torch.cuda.empty_cache()
     print(f"{'shape':18s} {'cnt':>3s} {'GFLOP':>8s} | {'fwd ms':>8s} {'TF/s':>6s} {'frac':>5s} | {'dgrad ms':>8s} {'TF/s':>6s} | "
           f"{'wgrad ms':>8s} {'TF/s':>6s} | share fwd/dgrad/wgrad")
-    for name, count, flops, t_f, t_d, t_w in rows:
+    for name, count, flops, t_f, t_d, t_w, on_fit in rows:
         tf = lambda t: flops / (t * 1e-3) / 1e12 if t > 0 else 0.0  # noqa: E731
         print(f"{name:18s} {count:3d} {flops / 1e9:8.1f} | {t_f:8.3f} {tf(t_f):6.1f} {tf(t_f) / PEAK:5.2f} | {t_d:8.3f} {tf(t_d):6.1f} | "
               f"{t_w:8.3f} {tf(t_w):6.1f} | {100 * count * t_f / tot['fwd']:.1f}% {100 * count * t_d / max(tot['dgrad'], 1e-9):.1f}% "
-              f"{100 * count * t_w / max(tot['wgrad'], 1e-9):.1f}%")
+              f"{100 * count * t_w / max(tot['wgrad'], 1e-9):.1f}%{' fit' if on_fit else ''}")
     print(f"sum over one forward: fwd {tot['fwd']:.1f} ms, dgrad {tot['dgrad']:.1f} ms, wgrad {tot['wgrad']:.1f} ms")
     print(f"pointwise rows, count-weighted ({a.math}{'/' + a.x6_split if a.math == 'bf16x6' else ''}): fwd {pw['fwd']:.2f} ms, dgrad {pw['dgrad']:.2f} ms, wgrad {pw['wgrad']:.2f} ms")
     print(f"winograd rows, count-weighted ({a.math}{'/x6-winograd' if a.x6_winograd else ''}): fwd {wn['fwd']:.2f} ms, dgrad {wn['dgrad']:.2f} ms, wgrad {wn['wgrad']:.2f} ms")
-    setting = a.math + ("/x6-taps" if a.x6_taps else "") + ("/no-winograd" if a.no_winograd else "") + (f"/tile{a.winograd_max_tile}" if a.winograd_max_tile else "")
+    setting = a.math + ("/x6-taps" if a.x6_taps else "") + ("/" + a.x6_wgrad_tile if a.math == "bf16x6" else "") + ("/no-winograd" if a.no_winograd else "") + (f"/tile{a.winograd_max_tile}" if a.winograd_max_tile else "")
     print(f"multi-tap rows, count-weighted ({setting}): fwd {tp['fwd']:.2f} ms, dgrad {tp['dgrad']:.2f} ms, wgrad {tp['wgrad']:.2f} ms")
+    print(f"narrow-tile rows, count-weighted ({setting}): fwd {nr['fwd']:.2f} ms, dgrad {nr['dgrad']:.2f} ms, wgrad {nr['wgrad']:.2f} ms")
 
 
 if __name__ == "__main__":
