@@ -873,7 +873,7 @@ class _Conv2dFn(torch.autograd.Function):
                         epi.addend, epi.addend_ld = _lib.ptr(prev), cp
                         if cbox is not None:
                             m_rows = n * hi * wi
-                            part = torch.empty(((m_rows + 63) // 64) * 2 * cp, dtype=torch.float32, device=w.device)      # (room for 64-row chunks)
+                            part = torch.empty(((m_rows + 63) // 64) * 2 * cp, dtype=torch.float32, device=w.device)      # (the size include/diga_hip.h asks for; the epilogue writes 128-row records into its first half)
                             _set_mask(epi, cbox, xn, cp)
                             epi.x, epi.x_ld = _lib.ptr(cbox["x"]), cp
                             epi.relu_ab = _lib.ptr(cbox["relu_ab"]) if not cbox["has_res"] else None
@@ -885,7 +885,7 @@ class _Conv2dFn(torch.autograd.Function):
                     # finish the gradient of the BatchNorm in front of this conv in the epilogue: + residual-branch
                     # gradient, ReLU mask, sum g / sum g*xhat per 128-row chunk (include/diga_hip.h, diga_bwd_epilogue_t)
                     m_rows = n * hi * wi
-                    part = torch.empty(((m_rows + 63) // 64) * 2 * cp, dtype=torch.float32, device=w.device)      # (room for 64-row chunks)
+                    part = torch.empty(((m_rows + 63) // 64) * 2 * cp, dtype=torch.float32, device=w.device)      # (the size include/diga_hip.h asks for; the epilogue writes 128-row records into its first half)
                     # the residual-branch gradient of the tensor this conv reads, left by the BatchNorm that took it as
                     # residual -- whether or not the producing BN itself had a residual (the epilogue combines `addend`
                     # with either mask form)

@@ -256,9 +256,10 @@ int diga_conv2d_epi_chunk_rows(int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, i
  *     partials[chunk] = { sum out, sum out*xhat } per 128-row chunk and channel, xhat = (x - mean) * invstd
  * `out` is then the MASKED gradient g of that BatchNorm and `partials` what diga_bn_bwd_partials finalises -- its
  * reduce pass over (g, x), the separate add and the residual-gradient copy are gone.  All tensors [M][ld] fp32 with
- * M = N*Ho*Wo rows, ld % 4 == 0, 16-byte aligned; Cout % 4 == 0; partials holds ceil(M/64)*2*Cout floats: one {sum, sum*xhat}
- * record per chunk of diga_conv2d_epi_chunk_rows(...) rows (128; 64 on the persistent fp32 GEMM) -- pass that chunk size
- * to diga_bn_bwd_partials.
+ * M = N*Ho*Wo rows, ld % 4 == 0, 16-byte aligned; Cout % 4 == 0; partials holds ceil(M/64)*2*Cout floats, of which the first
+ * ceil(M/128)*2*Cout are written: one {sum, sum*xhat} record per chunk of diga_conv2d_epi_chunk_rows(...) rows -- 128 for every
+ * shape and arithmetic (a call with an epilogue never runs on the persistent fp32 GEMM) -- pass that chunk size to
+ * diga_bn_bwd_partials.
  * ---------------------------------------------------------------------------------- */
 typedef struct {
     const float* addend;   /* nullable */
