@@ -442,24 +442,65 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// backward-weight on the triplets of dy and x: conv_wgrad_x3t_kernel with a third plane, six products in the order above
-// with the fold accumulator, and a two-stage ring (72 KB stages).  256 (Cout) x 128 (Cin) tile per pixel range; four
-// MFMA waves (wave tile 128 x 64) + four loader waves; fragments through the transposing LDS reads.
+// backward-weight: conv_wgrad_x3t_kernel with a third plane, six products in the order above with the fold accumulator, and a
+// two-stage ring.  One BM (Cout) x BN (Cin) tile per pixel range, tap and split: four MFMA waves as 2 x 2 (wave tile BM/2 x BN/2 =
+// MT x NT sub-tiles of 16 x 16, MT = BM / 32, NT = BN / 32) + four loader waves; fragments through the transposing LDS reads; the
+// zero-started correction chain folded in with one `acc += tt` per 32-pixel K-step; the pixel clamp on dy; zero planes for x outside
+// the image or past the pixel range; the channel-chunk clamp (kmax / cmax) with masked stores; the tap walk over a.ptab + tap *
+// a.M_pad; the slab layout [split][Cout][RS][Cin].  Seven instantiations: 256 x 128 in the three forms below (238 of 256 VGPRs), and
+// the loader form on 64 x 64, 64 x 128, 128 x 128, 256 x 64 for the layers that fill an eighth to a half of 256 x 128 and would pay
+// six MFMAs per product on the padding (diga_wgrad_bf16x6_tiled_f32in).  A 16 x 16 sub-tile sees the same fragments and the same
+// MFMA sequence on every tile: given the same pixel ranges a dw element has the same bits on any of them.
 // ---------------------------------------------------------------------------------------------
 //
-// LS (diga_conv2d_wgrad_bf16x6_f32in): dy and x are the fp32 tensors ([pixel][dy_ld] / [pixel][x_ld]); the loader lanes keep row,
+// LS = false (the pass form, diga_conv2d_wgrad_bf16x6; 256 x 128 only): dy and x are triplet images, staged by LDS-DMA.
+//
+// LS (the `_f32in` entry points): dy and x are the fp32 tensors ([pixel][dy_ld] / [pixel][x_ld]); the loader lanes keep row,
 // destination chunk, source-side swizzle and clamps, read their chunk's 8 channels as two float4, split (split3x4) and write the
 // three planes into the lane-linear LDS slots of the DMA form -- the same LDS bytes, so the same dw bits.
+// Loader split.  A plane is 32 pixel rows x CH / 8 chunks of 16 bytes (CH = BM or BN channels); the 256 loader lanes take
+// 64 * 8 / CH rows per wave instruction, CH / 32 instructions per wave (4 / 2 / 1 at 256 / 128 / 64 channels): instruction j of wave
+// wv covers rows 8 wv + (512 / CH) j + lane / (CH / 8), destination chunk lane % (CH / 8), and writes lane-linear (1 KB per plane
+// and instruction).
 //
-// WB (wgrad_batched_bf16x6, the Winograd-domain weight gradient): `R * S` independent products dU_b = Z_b^T V_b, the batch riding
-// on the tap index as in conv_wgrad_dma_kernel -- tap b reads dy + b * a.dy_tap_stride and x + b * a.x_tap_stride (a.M rows each),
-// the pixel table is the identity (a.ptab is null and not read), and a block's pixel range is clamped (dy) and zero-filled (x)
-// within its batch's a.M rows.  The store is the un-batched one: slab [Cout][batches][Cin].
-template <bool LS = false, bool WB = false>
-__global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
-    constexpr int BM = 256, BN = 128, MT = 8, NT = 4;
+// WB (wgrad_batched_bf16x6, the Winograd-domain weight gradient; loader form, 256 x 128 only): `R * S` independent products
+// dU_b = Z_b^T V_b, the batch riding on the tap index as in conv_wgrad_dma_kernel -- tap b reads dy + b * a.dy_tap_stride and
+// x + b * a.x_tap_stride (a.M rows each), the pixel table is the identity (a.ptab is null and not read), and a block's pixel range is
+// clamped (dy) and zero-filled (x) within its batch's a.M rows.  The store is the un-batched one: slab [Cout][batches][Cin].
+//
+// Swizzle.  At CH >= 128 a pixel row is a whole number of 256-byte bank lines: chunk ^ (tr_key(r) << 1) moves the 32 bytes a lane
+// group reads to one of 8 positions of the line.  At CH = 64 a row is 128 bytes: rows r and r + 1 share a bank line, so the row's
+// parity already picks the half and the key has two bits,
+//     key64(r) = ((r >> 1) & 1) | (((r >> 3) & 1) << 1),      chunk ^ (key64(r) << 1)   (bits 1..2 of the 3-bit chunk index).
+// A transposing read serves 32 lanes at a time = the pixel rows {0..3, 8..11} (+ 4 for the second read, + 16 for the upper half), 32
+// bytes of each.  The even rows of such a set (0, 2, 8, 10) lie on the low 128 bytes of their lines with the four keys 0, 1, 2, 3,
+// the odd ones (1, 3, 9, 11) on the high 128 bytes with the same four: eight different 32-byte positions of the 256-byte line, all 64
+// banks once, no conflict -- the property the wide key gives a 256-byte row.  The XOR touches bits below the row's chunk count only
+// (0..6 of 8 chunks, 0..14 of 16 / 32), so every lane's address stays inside its own row and plane.  The MFMA waves never diverge:
+// EXEC is full around every ds_read_tr16_b64.
+//
+// Residency (the ring is 2 x 3 x 32 x (BM + BN) x 2 bytes of the CU's 160 KB; a block is 8 waves, 2 per SIMD):
+//     64 x 64: 48 KB, 3 blocks per CU (6 waves per SIMD: 80 VGPRs)        64 x 128: 72 KB, 2 blocks per CU (128 VGPRs)
+//     128 x 128: 96 KB, 256 x 64: 120 KB and 256 x 128: 144 KB, 1 block per CU (no second ring fits) -- the first two win the padding only.
+// wgrad_x6_tile_blocks is the one statement of that; __launch_bounds__, the dynamic LDS size and the split-K plan read it.
+constexpr int wgrad_x6_tile_ring_bytes(int bm, int bn) { return 2 * 3 * kBK * (bm + bn) * 2; }
+constexpr int wgrad_x6_tile_blocks(int bm, int bn) { return 160 * 1024 / wgrad_x6_tile_ring_bytes(bm, bn); }
+
+template <int CH>
+__device__ __forceinline__ int tile_key(int r) {
+    if constexpr (CH >= 128) return tr_key(r) << 1;
+    else return (((r >> 1) & 1) | (((r >> 3) & 1) << 1)) << 1;
+}
+
+template <int BM, int BN, bool LS = true, bool WB = false>
+__global__ __launch_bounds__(512, 2 * wgrad_x6_tile_blocks(BM, BN)) void conv_wgrad_x6_kernel(WgradArgs a) {
+    static_assert((BM == 64 || BM == 128 || BM == 256) && (BN == 64 || BN == 128), "tiles of 64 / 128 / 256 x 64 / 128 channels");
+    static_assert(LS || (BM == 256 && BN == 128), "the LDS-DMA loader of the pass form is written for the 256 x 128 tile");
+    static_assert(!WB || (LS && BM == 256 && BN == 128), "the batched form is the loader form on the 256 x 128 tile");
+    constexpr int MT = BM / 32, NT = BN / 32;
     constexpr int A_ROW = BM * 2, B_ROW = BN * 2;                       // bytes per pixel row and plane
-    constexpr int A_PLANE = kBK * A_ROW, B_PLANE = kBK * B_ROW, STAGE = 3 * A_PLANE + 3 * B_PLANE;   // 72 KB
+    constexpr int A_PLANE = kBK * A_ROW, B_PLANE = kBK * B_ROW, STAGE = 3 * A_PLANE + 3 * B_PLANE;
+    static_assert(2 * STAGE == wgrad_x6_tile_ring_bytes(BM, BN), "the ring the launch asks for");
     extern __shared__ __align__(16) unsigned char smem_b[];
     const int t = threadIdx.x & 255, lane = t & 63, wv = t >> 6;
     const bool loader = threadIdx.x >= 256;
@@ -480,40 +521,39 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
 
     if constexpr (LS) {
       if (loader) {
+        constexpr int A_CPR = BM / 8, B_CPR = BN / 8;                   // 16-byte chunks per pixel row
+        constexpr int A_RPI = 64 / A_CPR, B_RPI = 64 / B_CPR;           // pixel rows per wave instruction
+        constexpr int A_NI = 8 / A_RPI, B_NI = 8 / B_RPI;               // instructions per loader wave and plane
         const int* tab = WB ? nullptr : a.ptab + (int64_t)tap * a.M_pad;
-        const float* dyb = a.dy;
-        const float* xb = a.x;
-        if constexpr (WB) {
-            dyb += (int64_t)tap * a.dy_tap_stride;
-            xb += (int64_t)tap * a.x_tap_stride;
-        }
-        const int a_chunk_dst = lane & 31, b_chunk_dst = lane & 15;
+        // (a.dy / a.x are read where they are used, the table read is one conditional expression and the swizzle keys are derived at
+        // their use: spelled so, every instantiation keeps the registers and the narrow tiles the instruction streams they had as
+        // two templates -- profiles/r17_kernel_resources.md)
+        const int64_t dy_tap = WB ? (int64_t)tap * a.dy_tap_stride : 0, x_tap = WB ? (int64_t)tap * a.x_tap_stride : 0;
+        const int a_chunk_dst = lane & (A_CPR - 1), b_chunk_dst = lane & (B_CPR - 1);
         const int kgrp = k0 / 8, cgrp = c0 / 8, kmax = a.Cout / 8 - 1, cmax = a.Cin / 8 - 1;
-        float4 va[4][2], vb[2][2];
-        bool okb[2];
+        float4 va[A_NI][2], vb[B_NI][2];
+        bool okb[B_NI];
         auto issue = [&](int ks) {                          // global loads of step ks into registers
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = 8 * wv + 2 * j + (lane >> 5);
+            for (int j = 0; j < A_NI; ++j) {
+                const int row = 8 * wv + A_RPI * j + lane / A_CPR;
                 const int p = min(p_begin + ks * kBK + row, a.M - 1);
-                const int chunk = min(kgrp + (a_chunk_dst ^ (tr_key(row) << 1)), kmax);
-                const float* src = dyb + (int64_t)p * a.dy_ld + chunk * 8;
+                const int chunk = min(kgrp + (a_chunk_dst ^ tile_key<BM>(row)), kmax);
+                const float* src = a.dy + dy_tap + (int64_t)p * a.dy_ld + chunk * 8;
                 va[j][0] = *reinterpret_cast<const float4*>(src);
                 va[j][1] = *reinterpret_cast<const float4*>(src + 4);
             }
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int row = 8 * wv + 4 * j + (lane >> 4);
+            for (int j = 0; j < B_NI; ++j) {
+                const int row = 8 * wv + B_RPI * j + lane / B_CPR;
                 const int p = p_begin + ks * kBK + row;
-                int xi = -1;
-                if (p < p_end) {
-                    if constexpr (WB) xi = p;
-                    else xi = tab[p];
-                }
+                int xi;                                     // (WB: the identity table)
+                if constexpr (WB) xi = p < p_end ? p : -1;
+                else xi = p < p_end ? tab[p] : -1;
                 okb[j] = xi >= 0;
                 if (okb[j]) {
-                    const int chunk = min(cgrp + (b_chunk_dst ^ (tr_key(row) << 1)), cmax);
-                    const float* src = xb + (int64_t)xi * a.x_ld + chunk * 8;
+                    const int chunk = min(cgrp + (b_chunk_dst ^ tile_key<BN>(row)), cmax);
+                    const float* src = a.x + x_tap + (int64_t)xi * a.x_ld + chunk * 8;
                     vb[j][0] = *reinterpret_cast<const float4*>(src);
                     vb[j][1] = *reinterpret_cast<const float4*>(src + 4);
                 }
@@ -522,17 +562,17 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
         auto write = [&](int stg) {                         // split + ds_write_b128 of the three planes, then wait for them
             unsigned char* stage = smem_b + stg * STAGE;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
+            for (int j = 0; j < A_NI; ++j) {
                 uint2 a0, a1, a2, b0, b1, b2;
                 split3x4(va[j][0], a0, a1, a2);
                 split3x4(va[j][1], b0, b1, b2);
-                unsigned char* dst = stage + (8 * wv + 2 * j) * A_ROW + lane * 16;
+                unsigned char* dst = stage + (8 * wv + A_RPI * j) * A_ROW + lane * 16;
                 *reinterpret_cast<uint4*>(dst) = make_uint4(a0.x, a0.y, b0.x, b0.y);
                 *reinterpret_cast<uint4*>(dst + A_PLANE) = make_uint4(a1.x, a1.y, b1.x, b1.y);
                 *reinterpret_cast<uint4*>(dst + 2 * A_PLANE) = make_uint4(a2.x, a2.y, b2.x, b2.y);
             }
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
+            for (int j = 0; j < B_NI; ++j) {
                 uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // outside the image / past the pixel range: zero planes
                 if (okb[j]) {
                     uint2 a0, a1, a2, b0, b1, b2;
@@ -542,7 +582,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
                     q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
                     q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
                 }
-                unsigned char* dst = stage + 3 * A_PLANE + (8 * wv + 4 * j) * B_ROW + lane * 16;
+                unsigned char* dst = stage + 3 * A_PLANE + (8 * wv + B_RPI * j) * B_ROW + lane * 16;
                 *reinterpret_cast<uint4*>(dst) = q0;
                 *reinterpret_cast<uint4*>(dst + B_PLANE) = q1;
                 *reinterpret_cast<uint4*>(dst + 2 * B_PLANE) = q2;
@@ -620,214 +660,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_x6_kernel(WgradArgs a) {
     // transposing read of this lane (conv_wgrad_x3t_kernel): group g = lane >> 4 takes pixel rows 8 g + q (+ 4 for the second read)
     const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
     const int row0 = 8 * g + q, row1 = row0 + 4;
-    const int key0 = tr_key(row0) << 1, key1 = tr_key(row1) << 1;
-    auto a_off = [&](int tile, int row, int key) { return row * A_ROW + (((2 * (wm * 8 + tile) + (pp >> 1)) ^ key) << 4) + ((pp & 1) << 3); };
-    auto b_off = [&](int tile, int row, int key) { return row * B_ROW + (((2 * (wn * 4 + tile) + (pp >> 1)) ^ key) << 4) + ((pp & 1) << 3); };
-
-    __builtin_amdgcn_s_barrier();                          // stage 0 has landed
-    for (int ks = 0; ks < ksteps; ++ks) {
-        const unsigned char* Ap = smem_b + (ks & 1) * STAGE;
-        const unsigned char* Bp = Ap + 3 * A_PLANE;
-        bf16x8_t b0[NT], b1[NT], b2[NT];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            b0[j] = tr_frag(Bp + b_off(j, row0, key0), Bp + b_off(j, row1, key1));
-            b1[j] = tr_frag(Bp + B_PLANE + b_off(j, row0, key0), Bp + B_PLANE + b_off(j, row1, key1));
-            b2[j] = tr_frag(Bp + 2 * B_PLANE + b_off(j, row0, key0), Bp + 2 * B_PLANE + b_off(j, row1, key1));
-        }
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const bf16x8_t a0 = tr_frag(Ap + a_off(i, row0, key0), Ap + a_off(i, row1, key1));
-            const bf16x8_t a1 = tr_frag(Ap + A_PLANE + a_off(i, row0, key0), Ap + A_PLANE + a_off(i, row1, key1));
-            const bf16x8_t a2 = tr_frag(Ap + 2 * A_PLANE + a_off(i, row0, key0), Ap + 2 * A_PLANE + a_off(i, row1, key1));
-            f32x4 tt[NT];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1[j], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] += tt[j];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    }
-
-    float* out = a.slab + (int64_t)split * a.Cout * RS * a.Cin;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int c = c0 + wn * 64 + j * 16 + (lane & 15);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int kk = k0 + wm * 128 + i * 16 + (lane >> 4) * 4 + e;
-                if (kk < a.Cout && c < a.Cin) out[((int64_t)kk * RS + tap) * a.Cin + c] = acc[i][j][e];
-            }
-        }
-    }
-}
-
-#undef DIGA_LDS_DMA16
-
-// ---------------------------------------------------------------------------------------------
-// Narrow tiles for the loader form of the weight gradient (diga_wgrad_bf16x6_tiled_f32in): conv_wgrad_x6_kernel<true> on a
-// BM (Cout) x BN (Cin) tile -- 64 x 64, 64 x 128, 128 x 128, 256 x 64 -- for the layers that fill an eighth to a half of 256 x 128
-// and pay six MFMAs per product on the padding.  A sibling, not a template parameter of the kernel above, so that kernel's three
-// instantiations keep their registers.  Kept from it, piece by piece: four MFMA waves as 2 x 2 (wave tile BM/2 x BN/2 = MT x NT
-// sub-tiles of 16 x 16, MT = BM / 32, NT = BN / 32) + four loader waves; the six products in the order of the file header; the
-// zero-started correction chain folded in with one `acc += tt` per 32-pixel K-step; the two-stage ring and its barriers; the pixel
-// clamp on dy; zero planes for x outside the image or past the pixel range; the channel-chunk clamp (kmax / cmax) with masked
-// stores; the tap walk over a.ptab + tap * a.M_pad; the slab layout [split][Cout][RS][Cin].  A 16 x 16 sub-tile therefore sees the
-// fragments and the MFMA sequence it sees in the wide kernel: given the same pixel ranges a dw element has the same bits on any tile.
-//
-// Loader split.  A plane is 32 pixel rows x CH / 8 chunks of 16 bytes (CH = BM or BN channels); the 256 loader lanes take
-// 64 * 8 / CH rows per wave instruction, CH / 32 instructions per wave (4 / 2 / 1 at 256 / 128 / 64 channels): instruction j of wave
-// wv covers rows 8 wv + (512 / CH) j + lane / (CH / 8), destination chunk lane % (CH / 8), and writes lane-linear (1 KB per plane
-// and instruction, as above).
-//
-// Swizzle.  At CH >= 128 a pixel row is a whole number of 256-byte bank lines and the key is the wide kernel's: chunk ^ (tr_key(r)
-// << 1) moves the 32 bytes a lane group reads to one of 8 positions of the line.  At CH = 64 a row is 128 bytes: rows r and r + 1
-// share a bank line, so the row's parity already picks the half and the key has two bits,
-//     key64(r) = ((r >> 1) & 1) | (((r >> 3) & 1) << 1),      chunk ^ (key64(r) << 1)   (bits 1..2 of the 3-bit chunk index).
-// A transposing read serves 32 lanes at a time = the pixel rows {0..3, 8..11} (+ 4 for the second read, + 16 for the upper half), 32
-// bytes of each.  The even rows of such a set (0, 2, 8, 10) lie on the low 128 bytes of their lines with the four keys 0, 1, 2, 3,
-// the odd ones (1, 3, 9, 11) on the high 128 bytes with the same four: eight different 32-byte positions of the 256-byte line, all 64
-// banks once, no conflict -- the property the wide key gives a 256-byte row.  The XOR touches bits below the row's chunk count only
-// (0..6 of 8 chunks, 0..14 of 16 / 32), so every lane's address stays inside its own row and plane.  The MFMA waves never diverge:
-// EXEC is full around every ds_read_tr16_b64.
-//
-// Residency (the ring is 2 x 3 x 32 x (BM + BN) x 2 bytes of the CU's 160 KB; a block is 8 waves, 2 per SIMD):
-//     64 x 64: 48 KB, 3 blocks per CU (6 waves per SIMD: 80 VGPRs)        64 x 128: 72 KB, 2 blocks per CU (128 VGPRs)
-//     128 x 128: 96 KB and 256 x 64: 120 KB, 1 block per CU (no second ring fits) -- these two win the padding only.
-// wgrad_x6_tile_blocks is the one statement of that; __launch_bounds__, the dynamic LDS size and the split-K plan read it.
-constexpr int wgrad_x6_tile_ring_bytes(int bm, int bn) { return 2 * 3 * kBK * (bm + bn) * 2; }
-constexpr int wgrad_x6_tile_blocks(int bm, int bn) { return 160 * 1024 / wgrad_x6_tile_ring_bytes(bm, bn); }
-
-template <int CH>
-__device__ __forceinline__ int tile_key(int r) {
-    if constexpr (CH >= 128) return tr_key(r) << 1;
-    else return (((r >> 1) & 1) | (((r >> 3) & 1) << 1)) << 1;
-}
-
-template <int BM, int BN>
-__global__ __launch_bounds__(512, 2 * wgrad_x6_tile_blocks(BM, BN)) void conv_wgrad_x6_tile_kernel(WgradArgs a) {
-    static_assert((BM == 64 || BM == 128 || BM == 256) && (BN == 64 || BN == 128), "tiles of 64 / 128 / 256 x 64 / 128 channels");
-    constexpr int MT = BM / 32, NT = BN / 32;
-    constexpr int A_ROW = BM * 2, B_ROW = BN * 2;                       // bytes per pixel row and plane
-    constexpr int A_PLANE = kBK * A_ROW, B_PLANE = kBK * B_ROW, STAGE = 3 * A_PLANE + 3 * B_PLANE;
-    constexpr int A_CPR = BM / 8, B_CPR = BN / 8;                       // 16-byte chunks per pixel row
-    constexpr int A_RPI = 64 / A_CPR, B_RPI = 64 / B_CPR;               // pixel rows per wave instruction
-    constexpr int A_NI = 8 / A_RPI, B_NI = 8 / B_RPI;                   // instructions per loader wave and plane
-    extern __shared__ __align__(16) unsigned char smem_b[];
-    const int t = threadIdx.x & 255, lane = t & 63, wv = t >> 6;
-    const bool loader = threadIdx.x >= 256;
-    const int wm = wv >> 1, wn = wv & 1;
-    const int RS = a.R * a.S;
-    int wg = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_n = wg % a.tiles_n;
-    wg /= a.tiles_n;
-    const int tile_m = wg % a.tiles_m;
-    wg /= a.tiles_m;
-    const int tap = wg % RS;
-    const int split = wg / RS;
-    const int k0 = tile_m * BM, c0 = tile_n * BN;
-    const int p_begin = split * a.steps_per_split * kBK;
-    int p_end = p_begin + a.steps_per_split * kBK;
-    if (p_end > a.M) p_end = a.M;
-    const int ksteps = p_end > p_begin ? (p_end - p_begin + kBK - 1) / kBK : 0;
-
-    if (loader) {
-        const int* tab = a.ptab + (int64_t)tap * a.M_pad;
-        const int a_chunk_dst = lane & (A_CPR - 1), b_chunk_dst = lane & (B_CPR - 1);
-        const int kgrp = k0 / 8, cgrp = c0 / 8, kmax = a.Cout / 8 - 1, cmax = a.Cin / 8 - 1;
-        float4 va[A_NI][2], vb[B_NI][2];
-        bool okb[B_NI];
-        auto issue = [&](int ks) {                          // global loads of step ks into registers
-#pragma unroll
-            for (int j = 0; j < A_NI; ++j) {
-                const int row = 8 * wv + A_RPI * j + lane / A_CPR;
-                const int p = min(p_begin + ks * kBK + row, a.M - 1);
-                const int chunk = min(kgrp + (a_chunk_dst ^ tile_key<BM>(row)), kmax);
-                const float* src = a.dy + (int64_t)p * a.dy_ld + chunk * 8;
-                va[j][0] = *reinterpret_cast<const float4*>(src);
-                va[j][1] = *reinterpret_cast<const float4*>(src + 4);
-            }
-#pragma unroll
-            for (int j = 0; j < B_NI; ++j) {
-                const int row = 8 * wv + B_RPI * j + lane / B_CPR;
-                const int p = p_begin + ks * kBK + row;
-                const int xi = p < p_end ? tab[p] : -1;
-                okb[j] = xi >= 0;
-                if (okb[j]) {
-                    const int chunk = min(cgrp + (b_chunk_dst ^ tile_key<BN>(row)), cmax);
-                    const float* src = a.x + (int64_t)xi * a.x_ld + chunk * 8;
-                    vb[j][0] = *reinterpret_cast<const float4*>(src);
-                    vb[j][1] = *reinterpret_cast<const float4*>(src + 4);
-                }
-            }
-        };
-        auto write = [&](int stg) {                         // split + ds_write_b128 of the three planes, then wait for them
-            unsigned char* stage = smem_b + stg * STAGE;
-#pragma unroll
-            for (int j = 0; j < A_NI; ++j) {
-                uint2 a0, a1, a2, b0, b1, b2;
-                split3x4(va[j][0], a0, a1, a2);
-                split3x4(va[j][1], b0, b1, b2);
-                unsigned char* dst = stage + (8 * wv + A_RPI * j) * A_ROW + lane * 16;
-                *reinterpret_cast<uint4*>(dst) = make_uint4(a0.x, a0.y, b0.x, b0.y);
-                *reinterpret_cast<uint4*>(dst + A_PLANE) = make_uint4(a1.x, a1.y, b1.x, b1.y);
-                *reinterpret_cast<uint4*>(dst + 2 * A_PLANE) = make_uint4(a2.x, a2.y, b2.x, b2.y);
-            }
-#pragma unroll
-            for (int j = 0; j < B_NI; ++j) {
-                uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // outside the image / past the pixel range: zero planes
-                if (okb[j]) {
-                    uint2 a0, a1, a2, b0, b1, b2;
-                    split3x4(vb[j][0], a0, a1, a2);
-                    split3x4(vb[j][1], b0, b1, b2);
-                    q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
-                    q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
-                    q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
-                }
-                unsigned char* dst = stage + 3 * A_PLANE + (8 * wv + B_RPI * j) * B_ROW + lane * 16;
-                *reinterpret_cast<uint4*>(dst) = q0;
-                *reinterpret_cast<uint4*>(dst + B_PLANE) = q1;
-                *reinterpret_cast<uint4*>(dst + 2 * B_PLANE) = q2;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        };
-        if (ksteps > 0) {
-            issue(0);
-            write(0);
-        }
-        __builtin_amdgcn_s_barrier();                      // stage 0 has landed
-        for (int ks = 0; ks < ksteps; ++ks) {
-            if (ks + 1 < ksteps) {                         // (its stage was read by step ks - 1: behind the last barrier)
-                issue(ks + 1);
-                write((ks + 1) & 1);
-            }
-            __builtin_amdgcn_s_barrier();
-        }
-        return;
-    }
-
-    // ---------------------------------------------------------------------- MFMA waves
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // transposing read of this lane, as in conv_wgrad_x6_kernel: group g = lane >> 4 takes pixel rows 8 g + q (+ 4 for the second read)
-    const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-    const int row0 = 8 * g + q, row1 = row0 + 4;
     auto a_off = [&](int tile, int row) { return row * A_ROW + (((2 * (wm * MT + tile) + (pp >> 1)) ^ tile_key<BM>(row)) << 4) + ((pp & 1) << 3); };
     auto b_off = [&](int tile, int row) { return row * B_ROW + (((2 * (wn * NT + tile) + (pp >> 1)) ^ tile_key<BN>(row)) << 4) + ((pp & 1) << 3); };
 
@@ -881,6 +713,8 @@ __global__ __launch_bounds__(512, 2 * wgrad_x6_tile_blocks(BM, BN)) void conv_wg
         }
     }
 }
+
+#undef DIGA_LDS_DMA16
 
 }  // namespace diga
 
@@ -1086,130 +920,13 @@ extern "C" int diga_infer_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld,
 }
 
 namespace {
-// 256 x 128 tiles at one block per CU: about two rounds of 256 blocks, at least 8 K-steps (256 pixels) per block.  Short pixel
-// ranges are also what keeps the weight gradient's error at the exact-fp32 kernels' level: the running sum of a range is
-// rounded twice per K-step, the slabs are then added in fixed order by slab_reduce_kernel.  (plan_wgrad_wide, tuned for the
-// widest layers, leaves a narrow layer on ONE block walking every pixel: measured 5x the fp32 kernel's error on a 64 -> 64
-// layer over 37 636 pixels.)
-// RS: independent products sharing the launch (the batched Winograd-domain form; 1 for a pointwise layer).
-WgradPlan plan_wgrad_x6(int64_t M, int64_t Cout, int64_t Cin, int64_t RS = 1) {
-    WgradPlan p;
-    p.tm = 4;
-    p.tn = 2;
-    p.tiles_m = (int)ceil_div(Cout, 256);
-    p.tiles_n = (int)ceil_div(Cin, 128);
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n * RS, ksteps = ceil_div(M, kBK);
-    int64_t splits = ceil_div(512, tiles);
-    const int64_t max_splits = ksteps / 8 > 0 ? ksteps / 8 : 1;
-    if (splits > max_splits) splits = max_splits;
-    if (splits > 512) splits = 512;
-    p.steps_per_split = (int)ceil_div(ksteps, splits);
-    p.splits = (int)ceil_div(ksteps, p.steps_per_split);
-    return p;
-}
-// shape rules of the multi-tap weight gradient (shared by the entry point's checks and its workspace query)
-bool taps_wgrad_shape_ok(const ConvGeometry& g) {
-    const int64_t lim = 1ll << 31;
-    if (g.N <= 0 || g.Ho <= 0 || g.Wo <= 0 || g.R < 1 || g.S < 1 || g.R > 64 || g.S > 64 || g.R * g.S > 64 || g.Cin <= 0 || g.Cin % 32 != 0 ||
-        g.Cin >= lim || g.Cout <= 0 || g.Cout % 8 != 0 || g.Cout >= lim || g.N >= lim || g.Ho >= lim || g.Wo >= lim || g.N * g.Ho >= lim ||
-        g.N * g.Ho * g.Wo >= lim)
-        return false;
-    const WgradPlan p = plan_wgrad_x6(g.N * g.Ho * g.Wo, g.Cout, g.Cin, g.R * g.S);
-    return ceil_div(g.Cout, 256) * ceil_div(g.Cin, 128) * g.R * g.S * p.splits < (1ll << 31);
-}
-}  // namespace
-
-extern "C" size_t diga_conv2d_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin,
-                                                           int64_t R, int64_t S) {
-    const int64_t M = N * Ho * Wo, RS = R * S;
-    return wgrad_slab_bytes(plan_wgrad_x6(M, Cout, Cin), Cout, Cin, RS) + (size_t)RS * wgrad_mpad(M) * sizeof(int) + 64;
-}
-
-// c.f32in: the operands are the fp32 tensors with row pitches dy_ld / x_ld (the loader form); else triplet images (the pass form)
-static int conv2d_wgrad_bf16x6(const WgradCall& c) {
-    DIGA_REQUIRE(c.dy && c.x && c.dw && c.workspace, DIGA_EINVAL, "conv2d_wgrad_bf16x6: null pointer");
-    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: bad shape");
-    if (c.taps) {
-        // diga_conv_taps_wgrad_bf16x6_f32in: one block group per tap from the pixel table of all taps (conv_wgrad_x6_kernel<true>)
-        DIGA_REQUIRE(c.f32in && taps_wgrad_shape_ok(c) && c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL,
-                     "conv_taps_wgrad_bf16x6: 1 <= R * S <= 64, Cin %% 32, Cout %% 8, positive strides and a block count below 2^31 required");
-        const int rc = check_tap_coordinates(c, "conv_taps_wgrad_bf16x6");
-        if (rc) return rc;
-    } else {
-        DIGA_REQUIRE(c.R == 1 && c.S == 1 && c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: pointwise (1x1) convolutions only");
-    }
-    DIGA_REQUIRE(c.Cin > 0 && c.Cin % 8 == 0 && c.Cout > 0 && c.Cout % 8 == 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: channel counts must be multiples of 8");
-    DIGA_REQUIRE(!c.f32in || (c.dy_ld >= c.Cout && c.dy_ld % 4 == 0 && c.x_ld >= c.Cin && c.x_ld % 4 == 0 && c.dy_ld < (1ll << 31) && c.x_ld < (1ll << 31)),
-                 DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count and multiples of 4");
-    DIGA_REQUIRE(aligned16(c.dy) && aligned16(c.x) && aligned16(c.dw) && aligned16(c.workspace), DIGA_EALIGN, "conv2d_wgrad_bf16x6: alignment");
-    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv2d_wgrad_bf16x6: too many pixels");
-    const int64_t RS = c.R * c.S, M = c.N * c.Ho * c.Wo, M_pad = wgrad_mpad(M);
-    const WgradPlan p = plan_wgrad_x6(M, c.Cout, c.Cin, RS);
-    const size_t slab_bytes = wgrad_slab_bytes(p, c.Cout, c.Cin, RS);
-    DIGA_REQUIRE(c.workspace_bytes >= slab_bytes + (size_t)RS * M_pad * sizeof(int) + 64, DIGA_EWORKSPACE, "conv2d_wgrad_bf16x6: workspace too small");
-    WgradArgs a;
-    fill_wgrad_args(a, c, p, M_pad);
-    hipStream_t st = (hipStream_t)c.stream;
-    ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)M * (double)c.Cout * (double)RS * (double)c.Cin);
-    launch_pixtab(a, c, slab_bytes, st);
-    static const WgradKernel kX6[2] = {conv_wgrad_x6_kernel<false>, conv_wgrad_x6_kernel<true>};                    // [loader form]
-    launch_k(kX6[c.f32in], wgrad_grid(a), 512, (size_t)2 * (3 * kBK * 512 + 3 * kBK * 256), st, a);
-    launch_slab_reduce(a, static_cast<const float*>(c.workspace), c.dw, st);
-    return launch_status(c.taps ? "diga_conv_taps_wgrad_bf16x6_f32in" : c.f32in ? "diga_conv2d_wgrad_bf16x6_f32in" : "diga_conv2d_wgrad_bf16x6");
-}
-
-extern "C" int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_triplet, float* dw, void* workspace,
-                                        size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
-                                        int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
-                                        int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
-    WgradCall c;
-    DIGA_FILL_GEOMETRY(c);
-    c.dy = dy_triplet; c.x = x_triplet; c.dw = dw; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
-    return conv2d_wgrad_bf16x6(c);
-}
-
-extern "C" int diga_conv2d_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
-                                              size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
-                                              int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
-                                              int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
-    DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
-    WgradCall c;
-    DIGA_FILL_GEOMETRY(c);
-    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.f32in = true; c.dw = dw; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
-    return conv2d_wgrad_bf16x6(c);
-}
-
-// The weight gradient of a multi-tap convolution on the loader form: diga_conv2d_wgrad_bf16x6_f32in's arguments with
-// 1 <= R * S <= 64, dw [Cout][R][S][Cin]; the split-K plan counts the taps (plan_wgrad_x6(M, Cout, Cin, R * S)).
-extern "C" size_t diga_conv_taps_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R,
-                                                              int64_t S) {
-    ConvGeometry g;
-    g.N = N; g.Ho = Ho; g.Wo = Wo; g.Cout = Cout; g.Cin = Cin; g.R = R; g.S = S;
-    if (!taps_wgrad_shape_ok(g)) return 0;
-    const int64_t M = N * Ho * Wo, RS = R * S;
-    return wgrad_slab_bytes(plan_wgrad_x6(M, Cout, Cin, RS), Cout, Cin, RS) + (size_t)RS * wgrad_mpad(M) * sizeof(int) + 64;
-}
-
-extern "C" int diga_conv_taps_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
-                                                 size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
-                                                 int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
-                                                 int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
-    DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv_taps_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
-    WgradCall c;
-    DIGA_FILL_GEOMETRY(c);
-    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.f32in = c.taps = true; c.dw = dw; c.workspace = workspace;
-    c.workspace_bytes = workspace_bytes;
-    return conv2d_wgrad_bf16x6(c);
-}
-
-// ---- the loader-form weight gradient on the tile that fits the layer (conv_wgrad_x6_tile_kernel)
-namespace {
 // THE tile rule (diga_wgrad_bf16x6_tile answers it, nothing else decides): BM by Cout, BN by Cin; 128 x 64 is not instantiated
-// (no layer of either network needs it) and answers 128 x 128; 256 x 128 is conv_wgrad_x6_kernel with plan_wgrad_x6.
+// (no layer of either network needs it) and answers 128 x 128.  Every entry point but diga_wgrad_bf16x6_tiled_f32in runs 256 x 128.
 struct X6Tile {
     int bm, bn;
     bool wide() const { return bm == 256 && bn == 128; }
 };
+constexpr X6Tile kX6Wide = {256, 128};
 X6Tile wgrad_x6_tile(int64_t Cout, int64_t Cin) {
     X6Tile t;
     t.bm = Cout <= 64 ? 64 : Cout <= 128 ? 128 : 256;
@@ -1217,15 +934,19 @@ X6Tile wgrad_x6_tile(int64_t Cout, int64_t Cin) {
     if (t.bm == 128 && t.bn == 64) t.bn = 128;
     return t;
 }
-// plan_wgrad_x6 for a narrow tile: tiles counted at bm x bn, the same floor of 8 K-steps (256 pixels) per block -- the floor is what
-// holds the error, see above -- and about two rounds of RESIDENT blocks, 256 CUs x wgrad_x6_tile_blocks(bm, bn) of them, under
-// plan_wgrad_x6's cap of 512 ranges:
+// The split-K plan: tiles counted at bm x bn, about two rounds of RESIDENT blocks -- 256 CUs x wgrad_x6_tile_blocks(bm, bn) of
+// them: 512 on the 256 x 128 tile -- at least 8 K-steps (256 pixels) per block, at most 512 ranges:
 //     splits = min( ceil(2 * 256 * blocks_per_cu / (tiles_m * tiles_n * RS)),  max(floor(ceil(M / 32) / 8), 1),  512 )
 //     steps_per_split = ceil(ceil(M / 32) / splits),   splits = ceil(ceil(M / 32) / steps_per_split)
-// The cap binds where one or two tiles cover the layer (64 -> 64 1x1: 1536 wanted).  slab_reduce_kernel adds the ranges one after
-// the other in 256-thread blocks of four dw elements per thread -- four blocks for a 64 x 64 dw -- so its time grows with the range
-// count whatever the tile: measured on 64 -> 64 over 16 x 193 x 193 pixels, 1536 ranges 0.49 ms against the wide tile's 0.38 ms at 512.
-WgradPlan plan_wgrad_x6_tile(int64_t M, int64_t Cout, int64_t Cin, int64_t RS, X6Tile t) {
+// Short pixel ranges are also what keeps the weight gradient's error at the exact-fp32 kernels' level: the running sum of a range is
+// rounded twice per K-step, the slabs are then added in fixed order by slab_reduce_kernel.  (plan_wgrad_wide, tuned for the
+// widest layers, leaves a narrow layer on ONE block walking every pixel: measured 5x the fp32 kernel's error on a 64 -> 64
+// layer over 37 636 pixels.)  The cap binds where one or two tiles cover the layer (64 -> 64 1x1: 1536 wanted).  slab_reduce_kernel
+// adds the ranges one after the other in 256-thread blocks of four dw elements per thread -- four blocks for a 64 x 64 dw -- so its
+// time grows with the range count whatever the tile: measured on 64 -> 64 over 16 x 193 x 193 pixels, 1536 ranges 0.49 ms against
+// the wide tile's 0.38 ms at 512.
+// RS: independent products sharing the launch (taps; the batches of the Winograd-domain form; 1 for a pointwise layer).
+WgradPlan plan_wgrad_x6(int64_t M, int64_t Cout, int64_t Cin, int64_t RS = 1, X6Tile t = kX6Wide) {
     WgradPlan p;
     p.tm = t.bm / 64;
     p.tn = t.bn / 64;
@@ -1240,22 +961,135 @@ WgradPlan plan_wgrad_x6_tile(int64_t M, int64_t Cout, int64_t Cin, int64_t RS, X
     p.splits = (int)ceil_div(ksteps, p.steps_per_split);
     return p;
 }
-WgradPlan plan_wgrad_x6_fit(int64_t M, int64_t Cout, int64_t Cin, int64_t RS) {
-    const X6Tile t = wgrad_x6_tile(Cout, Cin);
-    return t.wide() ? plan_wgrad_x6(M, Cout, Cin, RS) : plan_wgrad_x6_tile(M, Cout, Cin, RS, t);
-}
-// shape rules of diga_wgrad_bf16x6_tiled_f32in (shared by the entry point's checks and its workspace query)
-bool tiled_wgrad_shape_ok(const ConvGeometry& g) {
+// Shape rules of the loader-form weight gradients that take taps, on tile t (shared by the entry points' checks and their workspace
+// queries).  fit: diga_wgrad_bf16x6_tiled_f32in, where Cin % 8 is enough for a single tap.
+bool wgrad_x6_shape_ok(const ConvGeometry& g, X6Tile t, bool fit) {
     const int64_t lim = 1ll << 31;
     if (g.N <= 0 || g.Ho <= 0 || g.Wo <= 0 || g.R < 1 || g.S < 1 || g.R > 64 || g.S > 64 || g.R * g.S > 64 || g.Cin <= 0 ||
-        g.Cin % (g.R * g.S > 1 ? 32 : 8) != 0 || g.Cin >= lim || g.Cout <= 0 || g.Cout % 8 != 0 || g.Cout >= lim || g.N >= lim || g.Ho >= lim ||
+        g.Cin % (fit && g.R * g.S == 1 ? 8 : 32) != 0 || g.Cin >= lim || g.Cout <= 0 || g.Cout % 8 != 0 || g.Cout >= lim || g.N >= lim || g.Ho >= lim ||
         g.Wo >= lim || g.N * g.Ho >= lim || g.N * g.Ho * g.Wo >= lim)
         return false;
-    const WgradPlan p = plan_wgrad_x6_fit(g.N * g.Ho * g.Wo, g.Cout, g.Cin, g.R * g.S);
+    const WgradPlan p = plan_wgrad_x6(g.N * g.Ho * g.Wo, g.Cout, g.Cin, g.R * g.S, t);
     return (int64_t)p.tiles_m * p.tiles_n * g.R * g.S * p.splits < lim;
+}
+// split-K slabs, the pixel table of all taps, 16 zero bytes
+size_t wgrad_x6_workspace_bytes(const WgradPlan& p, int64_t M, int64_t Cout, int64_t Cin, int64_t RS) {
+    return wgrad_slab_bytes(p, Cout, Cin, RS) + (size_t)RS * wgrad_mpad(M) * sizeof(int) + 64;
+}
+size_t wgrad_x6_workspace_query(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R, int64_t S, bool fit) {
+    ConvGeometry g;
+    g.N = N; g.Ho = Ho; g.Wo = Wo; g.Cout = Cout; g.Cin = Cin; g.R = R; g.S = S;
+    const X6Tile t = fit ? wgrad_x6_tile(Cout, Cin) : kX6Wide;
+    if (!wgrad_x6_shape_ok(g, t, fit)) return 0;
+    const int64_t M = N * Ho * Wo, RS = R * S;
+    return wgrad_x6_workspace_bytes(plan_wgrad_x6(M, Cout, Cin, RS, t), M, Cout, Cin, RS);
 }
 }  // namespace
 
+// (the pointwise entry points' query checks no shape: its plan is the single-tap one)
+extern "C" size_t diga_conv2d_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin,
+                                                           int64_t R, int64_t S) {
+    return wgrad_x6_workspace_bytes(plan_wgrad_x6(N * Ho * Wo, Cout, Cin), N * Ho * Wo, Cout, Cin, R * S);
+}
+
+namespace {
+// The words of one family of entry points: `who` in most messages, `ld` in the pitch rule's, `taps` in the tap-coordinate rule's
+// (null: a pointwise family, which takes any offsets), `launch` for launch_status.
+struct X6WgradNames {
+    const char *who, *ld, *taps, *launch;
+};
+enum X6WgradFamily { kX6Pass, kX6Loader, kX6Taps, kX6Tiled };
+const X6WgradNames kX6WgradNames[4] = {
+    {"conv2d_wgrad_bf16x6", "conv2d_wgrad_bf16x6_f32in", nullptr, "diga_conv2d_wgrad_bf16x6"},
+    {"conv2d_wgrad_bf16x6", "conv2d_wgrad_bf16x6_f32in", nullptr, "diga_conv2d_wgrad_bf16x6_f32in"},
+    {"conv2d_wgrad_bf16x6", "conv2d_wgrad_bf16x6_f32in", "conv_taps_wgrad_bf16x6", "diga_conv_taps_wgrad_bf16x6_f32in"},
+    {"wgrad_bf16x6_tiled_f32in", "wgrad_bf16x6_tiled_f32in", "wgrad_bf16x6_tiled_f32in", "diga_wgrad_bf16x6_tiled_f32in"}};
+}  // namespace
+
+// The one launcher of conv_wgrad_x6_kernel's un-batched forms, on tile t.  c.f32in: the operands are the fp32 tensors with row
+// pitches dy_ld / x_ld (the loader form); else triplet images (the pass form).  c.taps: diga_conv_taps_wgrad_bf16x6_f32in, one block
+// group per tap from the pixel table of all taps.  c.fit: diga_wgrad_bf16x6_tiled_f32in with t = wgrad_x6_tile's answer; every other
+// entry point passes the 256 x 128 tile.  A tiled call whose tile is 256 x 128 continues, once its shape rule has passed, as the older
+// entry point of its tap count: that family's checks, words and launch name.
+static int conv2d_wgrad_bf16x6(const WgradCall& c, X6Tile t) {
+    const X6WgradNames& entry = kX6WgradNames[c.fit ? kX6Tiled : c.taps ? kX6Taps : kX6Pass];
+    DIGA_REQUIRE(c.dy && c.x && c.dw && c.workspace, DIGA_EINVAL, "%s: null pointer", entry.who);
+    DIGA_REQUIRE(c.fit || (c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0), DIGA_EINVAL, "conv2d_wgrad_bf16x6: bad shape");
+    DIGA_REQUIRE(!entry.taps || (c.f32in && c.Hi > 0 && c.Wi > 0 && wgrad_x6_shape_ok(c, t, c.fit) && c.stride_y > 0 && c.stride_x > 0),
+                 DIGA_EINVAL, "%s: 1 <= R * S <= 64, Cin %% 32%s, Cout %% 8, positive strides and a block count below 2^31 required",
+                 entry.taps, c.fit ? " (% 8 for 1x1)" : "");
+    const bool one_tap = c.R == 1 && c.S == 1;
+    const X6WgradNames& n = kX6WgradNames[c.fit && !t.wide() ? kX6Tiled : c.taps || (c.fit && !one_tap) ? kX6Taps : c.f32in ? kX6Loader : kX6Pass];
+    if (n.taps) {
+        const int rc = check_tap_coordinates(c, n.taps);
+        if (rc) return rc;
+    } else {
+        DIGA_REQUIRE(one_tap && c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: pointwise (1x1) convolutions only");
+        DIGA_REQUIRE(c.Cin > 0 && c.Cin % 8 == 0 && c.Cout > 0 && c.Cout % 8 == 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6: channel counts must be multiples of 8");
+    }
+    DIGA_REQUIRE(!c.f32in || (c.dy_ld >= c.Cout && c.dy_ld % 4 == 0 && c.x_ld >= c.Cin && c.x_ld % 4 == 0 && c.dy_ld < (1ll << 31) && c.x_ld < (1ll << 31)),
+                 DIGA_EINVAL, "%s: dy_ld / x_ld must be at least the channel count and multiples of 4", n.ld);
+    DIGA_REQUIRE(aligned16(c.dy) && aligned16(c.x) && aligned16(c.dw) && aligned16(c.workspace), DIGA_EALIGN, "%s: alignment", n.who);
+    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "%s: too many pixels", n.who);
+    const int64_t RS = c.R * c.S, M = c.N * c.Ho * c.Wo, M_pad = wgrad_mpad(M);
+    const WgradPlan p = plan_wgrad_x6(M, c.Cout, c.Cin, RS, t);
+    DIGA_REQUIRE(c.workspace_bytes >= wgrad_x6_workspace_bytes(p, M, c.Cout, c.Cin, RS), DIGA_EWORKSPACE, "%s: workspace too small", n.who);
+    WgradArgs a;
+    fill_wgrad_args(a, c, p, M_pad);
+    hipStream_t st = (hipStream_t)c.stream;
+    ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)M * (double)c.Cout * (double)RS * (double)c.Cin);
+    launch_pixtab(a, c, wgrad_slab_bytes(p, c.Cout, c.Cin, RS), st);
+    // conv_wgrad_x6_kernel<BM, BN, LS> by [BM / 128][BN / 128][loader form]; the pass form exists on the 256 x 128 tile only
+    static const WgradKernel kX6[3][2][2] = {
+        {{nullptr, conv_wgrad_x6_kernel<64, 64>}, {nullptr, conv_wgrad_x6_kernel<64, 128>}},
+        {{nullptr, nullptr}, {nullptr, conv_wgrad_x6_kernel<128, 128>}},
+        {{nullptr, conv_wgrad_x6_kernel<256, 64>}, {conv_wgrad_x6_kernel<256, 128, false>, conv_wgrad_x6_kernel<256, 128, true>}}};
+    launch_k(kX6[t.bm / 128][t.bn / 128][c.f32in], wgrad_grid(a), 512, (size_t)wgrad_x6_tile_ring_bytes(t.bm, t.bn), st, a);
+    launch_slab_reduce(a, static_cast<const float*>(c.workspace), c.dw, st);
+    return launch_status(n.launch);
+}
+
+extern "C" int diga_conv2d_wgrad_bf16x6(const void* dy_triplet, const void* x_triplet, float* dw, void* workspace,
+                                        size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
+                                        int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
+                                        int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
+    WgradCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.dy = dy_triplet; c.x = x_triplet; c.dw = dw; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return conv2d_wgrad_bf16x6(c, kX6Wide);
+}
+
+extern "C" int diga_conv2d_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
+                                              size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
+                                              int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
+                                              int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
+    DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv2d_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
+    WgradCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.f32in = true; c.dw = dw; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return conv2d_wgrad_bf16x6(c, kX6Wide);
+}
+
+// The weight gradient of a multi-tap convolution on the loader form: diga_conv2d_wgrad_bf16x6_f32in's arguments with
+// 1 <= R * S <= 64, dw [Cout][R][S][Cin]; the split-K plan counts the taps (plan_wgrad_x6(M, Cout, Cin, R * S)).
+extern "C" size_t diga_conv_taps_wgrad_bf16x6_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R,
+                                                              int64_t S) {
+    return wgrad_x6_workspace_query(N, Ho, Wo, Cout, Cin, R, S, false);
+}
+
+extern "C" int diga_conv_taps_wgrad_bf16x6_f32in(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw, void* workspace,
+                                                 size_t workspace_bytes, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho,
+                                                 int64_t Wo, int64_t Cout, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x,
+                                                 int64_t off_y0, int64_t off_x0, int64_t off_dy, int64_t off_dx, void* stream) {
+    DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "conv_taps_wgrad_bf16x6_f32in: dy_ld / x_ld must be at least the channel count");
+    WgradCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.f32in = c.taps = true; c.dw = dw; c.workspace = workspace;
+    c.workspace_bytes = workspace_bytes;
+    return conv2d_wgrad_bf16x6(c, kX6Wide);
+}
+
+// ---- the loader-form weight gradient on the tile that fits the layer
 extern "C" int diga_wgrad_bf16x6_tile(int64_t Cout, int64_t Cin, int* bm, int* bn) {
     DIGA_REQUIRE(bm && bn, DIGA_EINVAL, "wgrad_bf16x6_tile: null pointer");
     DIGA_REQUIRE(Cout > 0 && Cout % 8 == 0 && Cin > 0 && Cin % 8 == 0, DIGA_EINVAL, "wgrad_bf16x6_tile: channel counts must be positive multiples of 8");
@@ -1266,11 +1100,7 @@ extern "C" int diga_wgrad_bf16x6_tile(int64_t Cout, int64_t Cin, int* bm, int* b
 }
 
 extern "C" size_t diga_wgrad_bf16x6_tiled_workspace_bytes(int64_t N, int64_t Ho, int64_t Wo, int64_t Cout, int64_t Cin, int64_t R, int64_t S) {
-    ConvGeometry g;
-    g.N = N; g.Ho = Ho; g.Wo = Wo; g.Cout = Cout; g.Cin = Cin; g.R = R; g.S = S;
-    if (!tiled_wgrad_shape_ok(g)) return 0;
-    const int64_t M = N * Ho * Wo, RS = R * S;
-    return wgrad_slab_bytes(plan_wgrad_x6_fit(M, Cout, Cin, RS), Cout, Cin, RS) + (size_t)RS * wgrad_mpad(M) * sizeof(int) + 64;
+    return wgrad_x6_workspace_query(N, Ho, Wo, Cout, Cin, R, S, true);
 }
 
 // The weight gradient of a pointwise or multi-tap convolution on the loader form, on the tile wgrad_x6_tile picks for the layer:
@@ -1282,36 +1112,9 @@ extern "C" int diga_wgrad_bf16x6_tiled_f32in(const float* dy, int64_t dy_ld, con
     DIGA_REQUIRE(dy_ld >= 0 && x_ld >= 0, DIGA_EINVAL, "wgrad_bf16x6_tiled_f32in: dy_ld / x_ld must be at least the channel count");
     WgradCall c;
     DIGA_FILL_GEOMETRY(c);
-    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.f32in = true; c.dw = dw; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
-    DIGA_REQUIRE(c.dy && c.x && c.dw && c.workspace, DIGA_EINVAL, "wgrad_bf16x6_tiled_f32in: null pointer");
-    DIGA_REQUIRE(c.Hi > 0 && c.Wi > 0 && tiled_wgrad_shape_ok(c) && c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL,
-                 "wgrad_bf16x6_tiled_f32in: 1 <= R * S <= 64, Cin %% 32 (%% 8 for 1x1), Cout %% 8, positive strides and a block count below 2^31 required");
-    const int64_t RS = c.R * c.S, M = c.N * c.Ho * c.Wo, M_pad = wgrad_mpad(M);
-    const X6Tile t = wgrad_x6_tile(c.Cout, c.Cin);
-    if (t.wide()) {                                        // the existing kernel, plan, checks and launch
-        c.taps = RS > 1;
-        return conv2d_wgrad_bf16x6(c);
-    }
-    const int rc = check_tap_coordinates(c, "wgrad_bf16x6_tiled_f32in");
-    if (rc) return rc;
-    DIGA_REQUIRE(c.dy_ld >= c.Cout && c.dy_ld % 4 == 0 && c.x_ld >= c.Cin && c.x_ld % 4 == 0 && c.dy_ld < (1ll << 31) && c.x_ld < (1ll << 31),
-                 DIGA_EINVAL, "wgrad_bf16x6_tiled_f32in: dy_ld / x_ld must be at least the channel count and multiples of 4");
-    DIGA_REQUIRE(aligned16(c.dy) && aligned16(c.x) && aligned16(c.dw) && aligned16(c.workspace), DIGA_EALIGN, "wgrad_bf16x6_tiled_f32in: alignment");
-    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31), DIGA_EINVAL, "wgrad_bf16x6_tiled_f32in: too many pixels");
-    const WgradPlan p = plan_wgrad_x6_tile(M, c.Cout, c.Cin, RS, t);
-    const size_t slab_bytes = wgrad_slab_bytes(p, c.Cout, c.Cin, RS);
-    DIGA_REQUIRE(c.workspace_bytes >= slab_bytes + (size_t)RS * M_pad * sizeof(int) + 64, DIGA_EWORKSPACE, "wgrad_bf16x6_tiled_f32in: workspace too small");
-    WgradArgs a;
-    fill_wgrad_args(a, c, p, M_pad);
-    hipStream_t st = (hipStream_t)c.stream;
-    ProfScope prof(DIGA_PROF_CONV_BWD_WEIGHT, st, 2.0 * (double)M * (double)c.Cout * (double)RS * (double)c.Cin);
-    launch_pixtab(a, c, slab_bytes, st);
-    static const WgradKernel kTile[3][2] = {{conv_wgrad_x6_tile_kernel<64, 64>, conv_wgrad_x6_tile_kernel<64, 128>},      // [BM][BN]
-                                            {nullptr, conv_wgrad_x6_tile_kernel<128, 128>},
-                                            {conv_wgrad_x6_tile_kernel<256, 64>, nullptr}};
-    launch_k(kTile[t.bm / 128][t.bn / 128], wgrad_grid(a), 512, (size_t)wgrad_x6_tile_ring_bytes(t.bm, t.bn), st, a);
-    launch_slab_reduce(a, static_cast<const float*>(c.workspace), c.dw, st);
-    return launch_status("diga_wgrad_bf16x6_tiled_f32in");
+    c.dy = dy; c.dy_ld = dy_ld; c.x = x; c.x_ld = x_ld; c.f32in = c.fit = true; c.dw = dw; c.workspace = workspace;
+    c.workspace_bytes = workspace_bytes;
+    return conv2d_wgrad_bf16x6(c, wgrad_x6_tile(Cout, Cin));
 }
 
 // ---- the Winograd-domain GEMMs on bf16x6 (winograd.hip: diga_conv2d_winograd_bf16x6 / diga_conv2d_wgrad_winograd_bf16x6)
@@ -1373,7 +1176,7 @@ size_t wgrad_batched_bf16x6_slab_bytes(int64_t rows, int batches, int64_t Cout, 
     return wgrad_slab_bytes(plan_wgrad_x6(rows, Cout, Cin, batches), Cout, Cin, batches);
 }
 // dU_b [Cout x Cin] = Z_b^T V_b (contraction over the rows) for `batches` products in one launch of
-// conv_wgrad_x6_kernel<true, true>: Z [batches][rows][Cout], V [batches][rows][Cin] fp32, dU [Cout][batches][Cin]; split-K by
+// conv_wgrad_x6_kernel<256, 128, true, true>: Z [batches][rows][Cout], V [batches][rows][Cin] fp32, dU [Cout][batches][Cin]; split-K by
 // plan_wgrad_x6 (at least 8 K-steps per block, about two rounds of blocks), partial sums in `slab`
 // (wgrad_batched_bf16x6_slab_bytes), added in fixed order.  The arguments must pass wgrad_batched_bf16x6_ok.
 int wgrad_batched_bf16x6(const float* Z, const float* V, float* dU, float* slab, int64_t rows, int batches, int64_t Cout, int64_t Cin,
@@ -1382,7 +1185,7 @@ int wgrad_batched_bf16x6(const float* Z, const float* V, float* dU, float* slab,
                  "wgrad_batched_bf16x6: rows %% 32, Cout %% 256, Cin %% 128 required; rows and the block count below 2^31");
     WgradArgs a;
     fill_wgrad_batched(a, Z, V, dU, slab, rows, batches, Cout, Cin, plan_wgrad_x6(rows, Cout, Cin, batches));
-    launch_k<WgradArgs>(conv_wgrad_x6_kernel<true, true>, wgrad_grid(a), 512, (size_t)2 * (3 * kBK * 512 + 3 * kBK * 256), st, a);
+    launch_k<WgradArgs>(conv_wgrad_x6_kernel<256, 128, true, true>, wgrad_grid(a), 512, (size_t)wgrad_x6_tile_ring_bytes(256, 128), st, a);
     launch_slab_reduce(a, slab, dU, st);
     return DIGA_OK;
 }

@@ -50,6 +50,7 @@ struct WgradCall : ConvGeometry {
     void* workspace = nullptr;
     size_t workspace_bytes = 0;
     bool f32in = false, taps = false;  // as in ConvCall
+    bool fit = false;                  // bf16x6: diga_wgrad_bf16x6_tiled_f32in (the tile by the tile rule, Cin % 8 for a single tap)
 };
 
 // kernel variant by epilogue: the index of the per-family kernel tables

@@ -7,6 +7,7 @@ EWORKSPACE) before anything is launched; the fixture keeps (return code, message
 shapes.  Only `_lib.SIGNATURES`, `_lib.lib` and the descriptor structures are used, so the same file records from any revision:
 
     DIGA_LIB=<library of the revision to record> python tests/conv_entry_check_cases.py --record [--relist-valid]
+    DIGA_LIB=<...> python tests/conv_entry_check_cases.py --merge <name prefix>       (adds entry points, keeps every recorded entry)
 """
 import ctypes
 import itertools
@@ -66,9 +67,12 @@ SPECS = {
     "diga_conv2d_wgrad_winograd_bf16x6": f"dyp xp v_kept? dw ws ws_bytes {WB} tile_table? stream",
     "diga_gemm_batched_bf16x6_f32in": "in rows batches k img cout out stream",
     "diga_wgrad_batched_bf16x6_f32in": "dyp xp dw ws ws_bytes rows batches cout cin stream",
+    "diga_wgrad_bf16x6_tiled_f32in": f"dyp dy_ld xp x_ld dw ws ws_bytes {W15} stream",
+    "diga_wgrad_bf16x6_tile": "cout cin bm bn",
 }
 POINTERS = ("in", "wgt", "wgt_hi", "wgt_lo", "img", "bias", "out", "stats", "dyp", "xp", "dw", "ws", "table", "tile_table", "v_keep", "v_kept")
 DESCRIPTORS = ("epi", "infer", "opts")
+OUT_INTS = ("bm", "bn")          # results written through an int*: a real int unless the case passes null (0)
 
 
 def params(name):
@@ -85,11 +89,11 @@ def is_winograd(name):
 
 def has_taps(name):
     """The entry point takes more than one tap (R, S are not pinned to 1)."""
-    return "r" in params(name) and not ("bf16x6" in name and "taps" not in name)
+    return "r" in params(name) and not ("bf16x6" in name and "taps" not in name and "tiled" not in name)
 
 
 def multi_tap_form(name):
-    return "conv_taps" in name
+    return "conv_taps" in name or "tiled" in name
 
 
 def base(name):
@@ -97,7 +101,7 @@ def base(name):
     ps = params(name)
     v = {p: A + 0x1000 * (i + 1) for i, p in enumerate(POINTERS)}
     v.update({p: None for p in optional(name)})
-    v.update(stream=None, tag=0, math=0, flip=0, ws_bytes=BIG)
+    v.update(stream=None, tag=0, math=0, flip=0, ws_bytes=BIG, bm=1, bn=1)
     if is_winograd(name):
         v.update(n=1, h=12, w=12, cin=128, in_ld=128, x_ld=128, cout=256, out_ld=256, dy_ld=256, dil=1, tile=4)
     elif "batched" in name:
@@ -168,14 +172,24 @@ def descriptor_cases(name, kind):
             yield "reflect_beyond_2^31", dict(reflect_pad=1)     # (bf16x3: with an in_ld that leaves the 32-bit kernel, below)
 
 
+def variants(name):
+    """(case id prefix, changes to the base call): the tiled weight gradient is walked once per family of answers -- a narrow tile
+    with taps, a narrow tile at 1x1 (Cin % 8 is enough, the tap coordinates are still checked), and the 256 x 128 tile with taps and at
+    1x1, whose rejections past the shape rule come in the words of the wide entry points."""
+    if name != "diga_wgrad_bf16x6_tiled_f32in":
+        return [("", {})]
+    pw, wide = dict(r=1, s=1, oy=0, ox=0), dict(cout=512, cin=256, dy_ld=512, x_ld=256)
+    return [("", {}), ("1x1:", pw), ("wide:", wide), ("wide1x1:", {**wide, **pw})]
+
+
 def cases(valid=False):
     """(case id, entry point, argument values) of every rejected call (valid: and of the generated calls that break no rule)."""
-    for name in SPECS:
-        b, ps, opt = base(name), params(name), optional(name)
+    for name, (prefix, over) in ((n, v) for n in SPECS for v in variants(n)):
+        b, ps, opt = {**base(name), **over}, params(name), optional(name)
 
         def one(cid, **kw):
             # a case changes parameters the entry point has (None: the generated case does not apply to it)
-            return (f"{name}::{cid}", name, {**b, **kw}) if all(k in b and k in ps for k in kw) else None
+            return (f"{name}::{prefix}{cid}", name, {**b, **kw}) if all(k in b and k in ps for k in kw) else None
 
         out = []
         for p in ps:
@@ -184,6 +198,8 @@ def cases(valid=False):
                     out.append(one(f"{p}=null", **{p: 0}))
                 for off in (2, 4, 8):
                     out.append(one(f"{p}+{off}", **{p: A + 0x1000 * (POINTERS.index(p) + 1) + off}))
+            elif p in OUT_INTS:
+                out.append(one(f"{p}=null", **{p: 0}))
             elif p in ("n", "hi", "wi", "ho", "wo", "h", "w", "cout", "cin", "r", "s", "rows", "batches", "k", "dil", "tile"):
                 if p in ("cin", "cout") and "wgrad_winograd" in name:
                     continue                                     # (the weight-gradient split-K plan divides by the tile count: not a call to make)
@@ -260,6 +276,13 @@ def cases(valid=False):
             first = "in" if "in" in ps else "dyp"
             two = [{first: 0, "n": 0}, {first: 0, "cin": 48}, {first: A + 4, "cin": 48}, {first: A + 4, "n": 1 << 12, "ho": 1 << 10, "wo": 1 << 9},
                    {"cin": 48, "r": 65, "s": 1}, {"sy": 0, "r": 0}, {"oy": 1 << 31, "cin": 48}, {"n": 0, "r": 65}]
+            if "tiled" in name:
+                # Cin % 8 is the rule at 1x1, Cin % 32 with taps; the tap coordinates answer before pitch, alignment, pixel count, workspace
+                out += [one("cin=72+ld+ws_bytes=64", cin=72, x_ld=72, ws_bytes=64), one("cin=44+ld", cin=44, x_ld=44)]
+                two += [{"oy": 1 << 31, "dy_ld": 66}, {"oy": 1 << 31, "dyp": A + 4}, {"oy": 1 << 31, "n": 1 << 12, "hi": 1 << 10, "wi": 1 << 9},
+                        {"oy": 1 << 31, "ws_bytes": 0}, {"dy_ld": 66, "dyp": A + 4}, {"dyp": A + 4, "n": 1 << 12, "hi": 1 << 10, "wi": 1 << 9}]
+            if "bm" in ps:
+                two += [{"bm": 0, "cout": 0}, {"bm": 0, "bn": 0}]
             if "ws_bytes" in ps:
                 two += [{"ws_bytes": 0, first: A + 4}, {"ws_bytes": 0, "n": 1 << 12, "ho": 1 << 10, "wo": 1 << 9}, {"ws_bytes": 0, "cin": 48},
                         {"ws_bytes": 0, "math": 2}, {"ws": 0, "n": 0}]
@@ -319,6 +342,9 @@ def call(_lib, name, vals):
                 setattr(d, k, val)
             held.append(d)
             x = ctypes.byref(d)
+        if p in OUT_INTS:
+            held.append(ctypes.c_int(-7))
+            x = ctypes.byref(held[-1]) if x else None
         args.append(x)
     assert len(args) == len(_lib.SIGNATURES[name][1]), name
     rc = getattr(_lib.lib, name)(*args)
@@ -332,7 +358,8 @@ def is_query(name):
 
 
 def in_scope(name, restype_is_int):
-    conv = name.startswith(("diga_conv2d_", "diga_conv_taps_", "diga_infer_conv", "diga_split_bf16")) or "batched_bf16x6" in name
+    conv = name.startswith(("diga_conv2d_", "diga_conv_taps_", "diga_infer_conv", "diga_split_bf16", "diga_wgrad_bf16x6_")) or \
+        "batched_bf16x6" in name
     return conv and (is_query(name) or (restype_is_int and name in SPECS))
 
 
@@ -346,6 +373,9 @@ def queries():
               for co, ci in ((64, 64), (256, 128), (512, 1024), (62, 64), (64, 48), (0, 64), (64, 0), (19, 256))
               for r, s in ((1, 1), (3, 3), (7, 7), (0, 3), (5, 13), (65, 1))]
     # (the queries that do not check their shape -- they divide by the tile count -- see valid shapes only)
+    # the tiled weight gradient: the grid above (64 x 64, the wide tile, refused shapes) and one shape per further tile
+    tiled = direct + [(n, h, w, co, ci, r, s) for n, h, w in ((2, 33, 29), (2, 193, 193))
+                      for co, ci in ((64, 256), (128, 512), (256, 64), (128, 64), (40, 72), (320, 72)) for r, s in ((1, 1), (3, 3))]
     plain = [g for g in direct if g[0] == 1 or g[0] == 2 if g[3] > 0 and g[4] > 0 and g[5] > 0 and g[5] * g[6] <= 64]
     grids = {
         "diga_conv2d_winograd_workspace_bytes": wino, "diga_conv2d_winograd_bf16x6_workspace_bytes": wino,
@@ -357,6 +387,7 @@ def queries():
         "diga_conv2d_winograd_v_floats": sorted({(n, h, w, ci, d, t) for n, h, w, ci, _, d, t in wino}),
         "diga_conv2d_wgrad_workspace_bytes": plain, "diga_conv2d_wgrad_twin_workspace_bytes": plain,
         "diga_conv2d_wgrad_bf16x6_workspace_bytes": plain, "diga_conv_taps_wgrad_bf16x6_workspace_bytes": direct,
+        "diga_wgrad_bf16x6_tiled_workspace_bytes": tiled,
         "diga_conv2d_stats_floats": list(itertools.product(n_, hw, (12, 29), ch)),
         "diga_split_bf16_image_bytes": list(itertools.product((0, 19, 64, 65, 256), (0, 1, 9, 49), (0, 32, 48, 64, 160))),
         "diga_split_bf16x6_image_bytes": list(itertools.product((0, 19, 64, 65, 256), (0, 1, 9, 49), (0, 32, 48, 64, 160))),
@@ -379,10 +410,13 @@ if os.path.exists(FIXTURE):
     VALID_CALLS = set(load_fixture()["valid_calls"])
 
 
-def record(_lib, relist):
-    """relist: rewrite the list of valid calls from what this library accepts (to be read through before it is committed)."""
+def record(_lib, relist, only=""):
+    """relist: rewrite the list of valid calls from what this library accepts (to be read through before it is committed).
+    only: the entry points and queries whose names start with it (for --merge)."""
     got, accepted = {}, []
     for cid, name, vals in cases(valid=relist):
+        if not name.startswith(only):
+            continue
         rc, msg = call(_lib, name, vals)
         if rc in REJECTED:
             got[cid] = [rc, msg]
@@ -390,14 +424,22 @@ def record(_lib, relist):
             accepted.append(cid)
     if accepted and not relist:
         raise SystemExit("calls that no argument check rejects and that are not listed as valid calls:\n" + "\n".join(accepted))
-    q = {qid: getattr(_lib.lib, name)(*args) for qid, name, args in queries()}
+    q = {qid: getattr(_lib.lib, name)(*args) for qid, name, args in queries() if name.startswith(only)}
     return {"calls": got, "queries": q, "valid_calls": sorted(accepted) if relist else sorted(VALID_CALLS)}
 
 
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
     from diga_amd import _lib
-    if "--record" in sys.argv:
+    if "--merge" in sys.argv:
+        # entry points that join the fixture later: their answers are recorded (valid calls relisted), every other entry is kept as it is
+        data, new = load_fixture(), record(_lib, True, sys.argv[sys.argv.index("--merge") + 1])
+        data["calls"].update(new["calls"])
+        data["queries"].update(new["queries"])
+        data["valid_calls"] = sorted(set(data["valid_calls"]) | set(new["valid_calls"]))
+        dump_fixture(data)
+        print(f"{len(new['calls'])} calls, {len(new['queries'])} queries, {len(new['valid_calls'])} valid calls merged into {FIXTURE}")
+    elif "--record" in sys.argv:
         data = record(_lib, "--relist-valid" in sys.argv)
         dump_fixture(data)
         print(f"{len(data['calls'])} calls, {len(data['queries'])} queries, {len(data['valid_calls'])} valid calls -> {FIXTURE}")

@@ -35,7 +35,7 @@ def wide_splits(m, cout, cin, rs=1):
 
 
 def fit_splits(m, cout, cin, rs=1):
-    """plan_wgrad_x6_tile: two rounds of resident blocks (256 CUs x blocks per CU) over the BM x BN tiles, the same 8-K-step floor and
+    """plan_wgrad_x6 on the tile of the tile rule: two rounds of resident blocks (256 CUs x blocks per CU) over the BM x BN tiles, the same 8-K-step floor and
     the same cap of 512 ranges; a (256, 128) shape keeps the wide plan."""
     bm, bn = tile_rule(cout, cin)
     if (bm, bn) == (256, 128):

@@ -2,7 +2,9 @@
 of tests/conv_entry_check_cases.py the return code and the message of tests/golden/conv_entry_checks.json -- which rule answers, in which
 words, and, in the cases with two faults, which rule answers first -- and for every size / row query the recorded value.
 
-The fixture was recorded from the library of the commit before the launch layer moved onto call records (ConvCall, csrc/conv_call.h).  Every
+The fixture was recorded from the library of the commit before the launch layer moved onto call records (ConvCall, csrc/conv_call.h); the
+tiled weight gradient (diga_wgrad_bf16x6_tile, diga_wgrad_bf16x6_tiled_f32in and its workspace query) joined it from the last commit with
+a launcher of its own, before the bf16x6 weight gradients shared one -- a 256 x 128 shape answers there in the wide entry points' words.  Every
 recorded call was rejected by an argument check, so none can reach a launch; the subject is host code, and where a device is visible
 the test skips itself rather than hand fake addresses to a library that could launch on them."""
 import pytest

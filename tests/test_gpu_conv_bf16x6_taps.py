@@ -1,5 +1,5 @@
 """GPU tests of bf16x6 for multi-tap convolutions and the stem (config.x6_taps under conv_math = 2; csrc/conv_bf16x6.h: the TAPS
-instantiations of conv_fwd_x6_kernel, conv_wgrad_x6_kernel<true> with R * S > 1; model/conv.py: the "x6rs" family).
+instantiations of conv_fwd_x6_kernel, conv_wgrad_x6_kernel<256, 128, true> with R * S > 1; model/conv.py: the "x6rs" family).
 
   1. forward / backward-data bit for bit against the POINTWISE kernel on the torch-built im2col of the same input;
   2. the weight gradient bit for bit, tap by tap, against the pointwise weight gradient on the tap-shifted input;

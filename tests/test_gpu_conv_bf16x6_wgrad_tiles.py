@@ -1,5 +1,5 @@
 """GPU tests of the narrow tiles of the bf16x6 weight gradient (config.x6_wgrad_tile = "fit" under conv_math = 2; csrc/conv_bf16x6.h:
-conv_wgrad_x6_tile_kernel<64, 64> / <64, 128> / <128, 128> / <256, 64>, diga_wgrad_bf16x6_tiled_f32in; model/conv.py: _Path.fit).
+conv_wgrad_x6_kernel<64, 64> / <64, 128> / <128, 128> / <256, 64>, diga_wgrad_bf16x6_tiled_f32in; model/conv.py: _Path.fit).
 
   (a) dw bit for bit against the wide tile's entry points where both split-K plans cut the pixels into the same ranges;
   (b) a shape whose ranges differ: against float64 and against the wide tile's error;
