@@ -88,6 +88,7 @@ SIGNATURES = {
     "diga_conv_taps_bf16x6_f32in": (INT, [P, I64, P, P, P] + [I64] * 16 + [P, INT, P]),
     "diga_conv_taps_bf16x6_f32in_epi": (INT, [P, I64, P, P] + [I64] * 16 + [P, INT, P]),
     "diga_infer_conv_taps_bf16x6_f32in": (INT, [P, I64, P, P, P] + [I64] * 16 + [P, INT, P]),
+    "diga_conv_taps_bf16x6_f32in_opts": (INT, [P, I64, P, P, P] + [I64] * 16 + [P, P, INT, P]),
     "diga_conv_taps_wgrad_bf16x6_workspace_bytes": (SZ, [I64] * 7),
     "diga_conv_taps_wgrad_bf16x6_f32in": (INT, [P, I64, P, I64, P, P, SZ] + [I64] * 15 + [P]),
     "diga_wgrad_bf16x6_tile": (INT, [I64, I64, P, P]),
@@ -115,6 +116,7 @@ SIGNATURES = {
     "diga_conv2d_winograd_stats_floats": (SZ, [I64] * 6),
     "diga_conv2d_winograd_f32": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [INT, P, P, INT, P]),
     "diga_conv2d_winograd_f32_opts": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P, INT, P]),
+    "diga_conv_winograd_bf16x6_opts": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P, INT, P]),
     "diga_conv2d_winograd_f32_epi": (INT, [P, P, P, P, SZ] + [I64] * 9 + [INT, P, P, INT, P]),
     "diga_conv2d_winograd_f32_infer": (INT, [P, P, P, P, P, SZ] + [I64] * 9 + [P, P, INT, P]),
     "diga_conv2d_wgrad_winograd_workspace_bytes": (SZ, [I64] * 7 + [INT]),

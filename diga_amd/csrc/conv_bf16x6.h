@@ -159,10 +159,18 @@ __global__ __launch_bounds__(256) void split_image3_batched_kernel(const float* 
 // lgkmcnt(0) / barrier schedule; per row they keep the image's first pixel and (y0, x0) = (ho * sy + oy0, wo * sx + ox0), per tap they
 // derive (y0 + r * ody, x0 + q * odx) and the pointer -- null outside the image: no load is issued, the planes written are zero.  The
 // MFMA waves learn the new K-step count and nothing else; drain_stage, the fold accumulator and the ring are untouched.
-template <int TN, bool EPI = false, bool LS = false, bool WB = false, bool INF = false, bool TAPS = false>
+//
+// OPT (diga_conv_taps_bf16x6_f32in_opts; TAPS, plain variant only): the input map of diga_conv_options_t folded into the tap walk.  A
+// row's (y0, x0) are then coordinates in the LOGICAL image -- `in` upsampled by 2^up_shift, (Hi << up_shift) x (Wi << up_shift) -- and
+// each tap's (y0 + r * ody, x0 + q * odx) goes through map_tap: mirrored at both borders under pad_reflect, clamped (so no geometry can
+// form an address outside the tensor), shifted back to the source pixel; pix0 stays the SOURCE image's first pixel.  A tap that reads
+// zero padding keeps the null pointer and the zero planes.  live_taps already counts in the logical extent and keeps every tap under
+// pad_reflect; drain_stage already applies tanh under a.act.  An instantiation of its own: the others keep their instruction streams.
+template <int TN, bool EPI = false, bool LS = false, bool WB = false, bool INF = false, bool TAPS = false, bool OPT = false>
 __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
     static_assert(!(INF && (EPI || WB)), "the inference epilogue comes with the plain pointwise forward");
     static_assert(!TAPS || (LS && !WB), "the tap walk lives in the loader-split form");
+    static_assert(!OPT || (TAPS && !EPI && !INF), "the folded input map comes with the plain multi-tap forward");
     constexpr int BM = 256, BN = 64 * TN, NT = 2 * TN, MT = 4;
     constexpr int A_PLANE = BM * 64, B_PLANE = BN * 64, STAGE = 3 * A_PLANE + 3 * B_PLANE;
     extern __shared__ __align__(16) unsigned char smem_b[];
@@ -206,8 +214,14 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int iy = y0[j] + dy, ix = x0[j] + dx;
-                const bool ok = (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
-                pa[j] = ok ? a.in + ((int64_t)pix0[j] + (int64_t)iy * a.Wi + ix) * a.in_ld + kslot * 8 : nullptr;
+                if constexpr (OPT) {
+                    int py, px;                                  // (always a pixel of the source image: map_tap clamps)
+                    const bool ok = map_tap(a, iy, ix, py, px);
+                    pa[j] = ok ? a.in + ((int64_t)pix0[j] + (int64_t)py * a.Wi + px) * a.in_ld + kslot * 8 : nullptr;
+                } else {
+                    const bool ok = (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
+                    pa[j] = ok ? a.in + ((int64_t)pix0[j] + (int64_t)iy * a.Wi + ix) * a.in_ld + kslot * 8 : nullptr;
+                }
             }
         };
         const unsigned char* bimg = a.wgt_img + (int64_t)tile_n * ((int64_t)a.R * a.S * cchunks) * (3 * B_PLANE) + (lw * 3 * TN) * 1024 + lane * 16;
@@ -761,7 +775,12 @@ static int conv2d_bf16x6(const ConvCall& c) {
         DIGA_REQUIRE(c.in_ld >= 0, DIGA_EINVAL, "conv_taps_bf16x6: in_ld must be at least Cin and a multiple of 4");
         DIGA_REQUIRE(c.R >= 1 && c.S >= 1 && c.R <= 64 && c.S <= 64 && c.R * c.S <= 64, DIGA_EINVAL, "conv_taps_bf16x6: 1 <= R * S <= 64 taps");
         DIGA_REQUIRE(c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL, "conv_taps_bf16x6: strides must be positive");
-        const int rc = check_tap_coordinates(c, "conv_taps_bf16x6");
+        // c.opts (diga_conv_taps_bf16x6_f32in_opts): the plain forward only, and the tap coordinates are the upsampled image's
+        DIGA_REQUIRE(!c.opts || (!c.stats && !c.epi && !c.infer), DIGA_EINVAL,
+                     "conv_taps_bf16x6_opts: a folded input map / activation comes without statistics and without an epilogue");
+        int rc = check_options(c.opts, "conv_taps_bf16x6_opts");
+        if (rc) return rc;
+        rc = check_tap_coordinates(c, "conv_taps_bf16x6", c.opts ? c.opts->upsample_shift : -1);
         if (rc) return rc;
     } else {
         DIGA_REQUIRE(c.R == 1 && c.S == 1 && c.stride_y > 0 && c.stride_x > 0, DIGA_EINVAL, "conv2d_bf16x6: pointwise (1x1) convolutions only");
@@ -799,11 +818,15 @@ static int conv2d_bf16x6(const ConvCall& c) {
     static const char* const kName[3][2] = {{"diga_conv2d_nhwc_bf16x6", "diga_infer_conv2d_nhwc_bf16x6"},
                                             {"diga_conv2d_nhwc_bf16x6_f32in", "diga_infer_conv2d_nhwc_bf16x6_f32in"},
                                             {"diga_conv_taps_bf16x6_f32in", "diga_infer_conv_taps_bf16x6_f32in"}};
+    // ... and the multi-tap form with the folded input map (OPT; plain variant only) by [tn - 1]
+    static const ConvKernel kX6Opt[2] = {conv_fwd_x6_kernel<1, false, true, false, false, true, true>,
+                                         conv_fwd_x6_kernel<2, false, true, false, false, true, true>};
     const int form = c.taps ? kTaps : c.f32in ? kLoader : kPass;
     const size_t ring = (size_t)2 * (3 * 256 * 64 + 3 * 64 * tn * 64);
     const size_t stg = (size_t)2 * 128 * (64 * tn + 4) * sizeof(float);
-    launch_k(kX6[form][tn - 1][conv_variant(c.epi, c.infer)], (unsigned)(a.tiles_m * a.tiles_n), 768, ring > stg ? ring : stg, st, a);
-    return launch_status(kName[form][c.infer != nullptr]);
+    launch_k(c.opts ? kX6Opt[tn - 1] : kX6[form][tn - 1][conv_variant(c.epi, c.infer)], (unsigned)(a.tiles_m * a.tiles_n), 768,
+             ring > stg ? ring : stg, st, a);
+    return launch_status(c.opts ? "diga_conv_taps_bf16x6_f32in_opts" : kName[form][c.infer != nullptr]);
 }
 
 extern "C" int diga_conv2d_nhwc_bf16x6(const void* in_triplet, const void* wgt_img, const float* bias, float* out, int64_t N,
@@ -916,6 +939,22 @@ extern "C" int diga_infer_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld,
     DIGA_FILL_GEOMETRY(c);
     c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
     c.infer = infer; c.prof_tag = prof_tag;
+    return conv2d_bf16x6(c);
+}
+
+// diga_conv_taps_bf16x6_f32in with the input map and the activation of diga_conv_options_t folded into the kernel
+// (conv_fwd_x6_kernel<..., TAPS, OPT>): `in` is the SOURCE tensor [N][Hi][Wi], the offsets address its 2^upsample_shift upsampling,
+// reflect_pad mirrors the taps outside it, activation 1 is tanh on the output.  Forward only: stats_partial must be null.
+extern "C" int diga_conv_taps_bf16x6_f32in_opts(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out,
+                                                int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout,
+                                                int64_t out_ld, int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0,
+                                                int64_t off_x0, int64_t off_dy, int64_t off_dx, float* stats_partial,
+                                                const diga_conv_options_t* opts, int prof_tag, void* stream) {
+    DIGA_REQUIRE(opts != nullptr, DIGA_EINVAL, "conv_taps_bf16x6_opts: null options");
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
+    c.stats = stats_partial; c.opts = opts; c.prof_tag = prof_tag;
     return conv2d_bf16x6(c);
 }
 

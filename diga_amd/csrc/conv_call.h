@@ -90,8 +90,12 @@ static int check_infer_epilogue(const diga_infer_epilogue_t* e, int64_t Cout, co
 }
 
 // The multi-tap forms derive (Ho - 1) * stride + offset + (R - 1) * step in 32 bits: every term stays below 2^30.
-static int check_tap_coordinates(const ConvGeometry& g, const char* who) {
+// up_shift >= 0 (the `_opts` form: a checked diga_conv_options_t's upsample_shift): the coordinates are those of the upsampled image
+// and map_tap mirrors them at 2 * (extent - 1), so the upsampled extents (Hi << up_shift, Wi << up_shift) stay below 2^30 as well.
+static int check_tap_coordinates(const ConvGeometry& g, const char* who, int up_shift = -1) {
     const int64_t lim = 1ll << 30;
+    DIGA_REQUIRE(up_shift < 0 || (g.Hi < lim && g.Wi < lim && (g.Hi << up_shift) < lim && (g.Wi << up_shift) < lim), DIGA_EINVAL,
+                 "%s: the upsampled image lies beyond 32-bit pixel coordinates", who);
     DIGA_REQUIRE(g.stride_y < lim && g.stride_x < lim && g.off_y0 > -lim && g.off_y0 < lim && g.off_x0 > -lim && g.off_x0 < lim &&
                      g.off_dy > -lim && g.off_dy < lim && g.off_dx > -lim && g.off_dx < lim && g.Ho * g.stride_y < lim &&
                      g.Wo * g.stride_x < lim && (g.off_dy < 0 ? -g.off_dy : g.off_dy) * g.R < lim &&

@@ -1154,7 +1154,8 @@ extern "C" size_t diga_conv2d_winograd_workspace_bytes(int64_t N, int64_t H, int
 
 static int winograd_conv(const WinoCall& c) {
     // x6 (diga_conv2d_winograd_bf16x6 / _infer): the products on the bf16x6 GEMM; tile table, transforms, v_keep, statistics, the backward
-    // epilogue and the inference epilogue as below.  Not with reflection padding (that form stays exact fp32).
+    // epilogue and the inference epilogue as below.  Reflection padding (diga_conv_winograd_bf16x6_opts) lives in the input transform alone
+    // -- the GEMM behind it never sees it -- so it comes under the fp32 form's rule: the plain forward of 4x4 / 6x6 tiles.
     const float *in = c.in, *wgt = c.wgt, *bias = c.bias;
     float *out = c.out, *stats = c.stats;
     const int64_t N = c.N, H = c.H, W = c.W, Cin = c.Cin, in_ld = c.in_ld, Cout = c.Cout, out_ld = c.out_ld, dilation = c.dilation, tile = c.tile;
@@ -1163,7 +1164,6 @@ static int winograd_conv(const WinoCall& c) {
     const diga_bwd_epilogue_t* epi = c.epi;
     const diga_infer_epilogue_t* inf = c.infer;
     const void* tile_table = c.tile_table;
-    DIGA_REQUIRE(!x6 || !reflect, DIGA_EINVAL, "conv2d_winograd_bf16x6: no reflection padding");
     DIGA_REQUIRE(!inf || ((tile == 4 || tile == 6) && !flip && !epi && !stats && !reflect), DIGA_EINVAL,
                  "conv2d_winograd_infer: the inference epilogue comes with the plain forward of 4x4 / 6x6 tiles");
     DIGA_REQUIRE(!reflect || (tile != 2 && !flip && !epi && dilation < H && dilation < W), DIGA_EINVAL,
@@ -1240,7 +1240,7 @@ static int winograd_conv(const WinoCall& c) {
             hipLaunchKernelGGL(wino_output_epi_kernel, dim3((unsigned)G, (unsigned)ceil_div(Cout, 256)), dim3(256), 0, st, Mb, tab, out,
                                out_ld, g.T, g.Tp, (int)Cout, (int)H, (int)W, (int)dilation, tpb, ep);
     }
-    return launch_status(x6 ? "diga_conv2d_winograd_bf16x6" : "diga_conv2d_winograd_f32");
+    return launch_status(x6 ? (reflect ? "diga_conv_winograd_bf16x6_opts" : "diga_conv2d_winograd_bf16x6") : "diga_conv2d_winograd_f32");
 }
 
 extern "C" size_t diga_conv2d_winograd_tile_table_bytes(int64_t N, int64_t H, int64_t W, int64_t dilation, int64_t tile) {
@@ -1440,6 +1440,24 @@ extern "C" int diga_infer_conv2d_winograd_bf16x6(const float* in, const float* w
     WinoCall c;
     DIGA_FILL_WINO(c);
     c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.infer = infer; c.prof_tag = prof_tag; c.x6 = true;
+    return winograd_conv(c);
+}
+
+// diga_conv2d_winograd_f32_opts with the products on the bf16x6 GEMM (its argument list; the workspace of
+// diga_conv2d_winograd_bf16x6_workspace_bytes): the input transform mirrors the border, the batched GEMM and the output transform are
+// diga_conv2d_winograd_bf16x6's.  Forward of 4x4 / 6x6 tiles, no statistics, no epilogue.
+extern "C" int diga_conv_winograd_bf16x6_opts(const float* in, const float* wgt, const float* bias, float* out, void* workspace,
+                                              size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld,
+                                              int64_t Cout, int64_t out_ld, int64_t dilation, int64_t tile, const diga_conv_options_t* opts,
+                                              const void* tile_table, int prof_tag, void* stream) {
+    DIGA_REQUIRE(opts != nullptr, DIGA_EINVAL, "conv_winograd_bf16x6_opts: null options");
+    DIGA_REQUIRE(opts->upsample_shift == 0 && opts->activation == 0, DIGA_EINVAL,
+                 "conv_winograd_bf16x6_opts: only reflect_pad is folded on the Winograd path (upsampling / tanh: diga_conv_taps_bf16x6_f32in_opts)");
+    DIGA_REQUIRE(tile == 4 || tile == 6, DIGA_EINVAL, "conv_winograd_bf16x6_opts: tiles of 4x4 / 6x6 (F(4x4,3x3) / F(6x6,3x3))");
+    WinoCall c;
+    DIGA_FILL_WINO(c);
+    c.in = in; c.in_ld = in_ld; c.wgt = wgt; c.bias = bias; c.out = out; c.out_ld = out_ld; c.prof_tag = prof_tag;
+    c.x6 = true; c.reflect = opts->reflect_pad ? 1 : 0;
     return winograd_conv(c);
 }
 

@@ -82,10 +82,17 @@ def _x6_taps():
     return _lib.get_conv_math() == 2 and config.active().x6_taps
 
 
+def _x6_opts():
+    """True when config.x6_opts is in force (conv_math = 2; both read per call): a call with a folded input map / activation (`opts`:
+    the frozen translator's reflection padding, nearest upsampling and tanh) is planned by the rules of a call without -- _taps_ok
+    admits it, and a "winograd_reflect" call asks _wino_x6.  Nothing else reads it; pointwise calls with options stay exact fp32."""
+    return _lib.get_conv_math() == 2 and config.active().x6_opts
+
+
 def _taps_ok(cin, r, s, copt):
     """Eligibility of a call for the "x6rs" family: more than one tap (at most 64: the live-tap mask), padded Cin % 32 == 0, no folded
-    input map / activation."""
-    return 1 < r * s <= 64 and cin % 32 == 0 and not copt
+    input map / activation -- unless config.x6_opts admits those (the `_opts` entry point)."""
+    return 1 < r * s <= 64 and cin % 32 == 0 and (not copt or _x6_opts())
 
 
 def _x6_fit(kp, cp):
@@ -340,7 +347,9 @@ def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, sta
                 and _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo)):
             tile, ratio = _wino_plan(hi, wi, doff[0])
             if tile >= 4:
-                return _Path("winograd_reflect", "opts", 0, "winograd", tile, ratio)
+                # (the mirror lives in the input transform only: under config.x6_opts the products behind it take _wino_x6's answer)
+                x6w = _x6_opts() and _wino_x6()
+                return _Path("winograd_reflect", "opts", 0, "winograd/x6" if x6w else "winograd", tile, ratio, x6w)
     elif stats != "chunks" and _winograd_ok(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo):
         tile, ratio = _wino_plan(hi, wi, abs(doff[0]))
         if stats is not None and (tile < 4 or epi or doff[0] < 0):
@@ -452,12 +461,13 @@ def _make_split(src, ld, rows, ch, triplet):
 # (family, variant) -> entry point.  The implicit-GEMM families share one argument layout (_conv_launch) up to: the leading operand
 # pointers (_operands), an input pitch (the two families that read fp32 activations through the ordinary loads), a bias slot (all
 # but `_epi`) and the one trailing pointer (statistics, or the variant's struct).  The Winograd entry points have their own layout
-# (_winograd_launch); with the products on bf16x6 one entry point serves every variant but "infer", which has its own.
+# (_winograd_launch); with the products on bf16x6 one entry point serves every variant but "infer" and "opts", which have their own.
+# ("x6rs", "opts") keeps the (null) statistics slot of its sibling in front of the options.
 _ENTRY = {
     ("x6ls", ""): "diga_conv2d_nhwc_bf16x6_f32in", ("x6ls", "epi"): "diga_conv2d_nhwc_bf16x6_f32in_epi",
     ("x6ls", "infer"): "diga_infer_conv2d_nhwc_bf16x6_f32in",
     ("x6rs", ""): "diga_conv_taps_bf16x6_f32in", ("x6rs", "epi"): "diga_conv_taps_bf16x6_f32in_epi",
-    ("x6rs", "infer"): "diga_infer_conv_taps_bf16x6_f32in",
+    ("x6rs", "infer"): "diga_infer_conv_taps_bf16x6_f32in", ("x6rs", "opts"): "diga_conv_taps_bf16x6_f32in_opts",
     ("x6", ""): "diga_conv2d_nhwc_bf16x6", ("x6", "epi"): "diga_conv2d_nhwc_bf16x6_epi", ("x6", "infer"): "diga_infer_conv2d_nhwc_bf16x6",
     ("twin", ""): "diga_conv2d_nhwc_twin", ("twin", "epi"): "diga_conv2d_nhwc_twin_epi", ("twin", "opts"): "diga_conv2d_nhwc_twin_opts",
     ("bf16x3", ""): "diga_conv2d_nhwc_bf16x3", ("bf16x3", "epi"): "diga_conv2d_nhwc_bf16x3_epi",
@@ -470,6 +480,7 @@ _ENTRY = {
 }
 _WINOGRAD_X6 = "diga_conv2d_winograd_bf16x6"
 _WINOGRAD_X6_INFER = "diga_infer_conv2d_winograd_bf16x6"
+_WINOGRAD_X6_OPTS = "diga_conv_winograd_bf16x6_opts"         # ("winograd_reflect", "opts") with x6w: the fp32 `_opts` form's argument list
 
 
 def _operands(path, x, w_krsc, twin_box):
@@ -521,8 +532,8 @@ def _winograd_launch(path, x, w_krsc, bias, out, d, flip, tag, stats, struct, ke
             variant = ""
     lead = [_lib.ptr(x), _lib.ptr(w_krsc)] + ([] if variant == "epi" and not path.x6w else [_lib.ptr(bias)]) + [_lib.ptr(out)]
     shape = (_lib.ptr(ws), ws.numel(), n, hi, wi, cin, x.stride(2), k, out.stride(2), d, tile)
-    if path.x6w and variant == "infer":
-        _lib.call(_WINOGRAD_X6_INFER, *lead, *shape, struct, _lib.ptr(tab), tag, _lib.stream())
+    if path.x6w and variant in ("infer", "opts"):
+        _lib.call(_WINOGRAD_X6_INFER if variant == "infer" else _WINOGRAD_X6_OPTS, *lead, *shape, struct, _lib.ptr(tab), tag, _lib.stream())
         return
     if path.x6w:
         # one entry point for the plain forward / backward-data, the forward with statistics, the forward that keeps V and
@@ -571,8 +582,9 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
     lead, held, split = _operands(path, x, w_krsc, twin_box)         # (`held`, `inf_held`: alive until the kernel is enqueued)
     _lib.call(_ENTRY[(path.family, path.variant)], *lead, *(() if path.variant == "epi" else (_lib.ptr(bias),)), _lib.ptr(out),
               n, hi, wi, cin, *((x.stride(2),) if path.family in ("bf16x3", "f32") else ()), ho, wo, k, out.stride(2), r, s,
-              stride[0], stride[1], off0[0], off0[1], doff[0], doff[1], struct if struct is not None else _lib.ptr(stats), tag,
-              _lib.stream())
+              stride[0], stride[1], off0[0], off0[1], doff[0], doff[1],
+              *((_lib.ptr(stats),) if (path.family, path.variant) == ("x6rs", "opts") else ()),
+              struct if struct is not None else _lib.ptr(stats), tag, _lib.stream())
     return split
 
 

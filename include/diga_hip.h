@@ -563,6 +563,19 @@ int diga_infer_conv_taps_bf16x6_f32in(const float* in, int64_t in_ld, const void
                                       int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
                                       int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
                                       int64_t off_dy, int64_t off_dx, const diga_infer_epilogue_t* infer, int prof_tag, void* stream);
+/* diga_conv_taps_bf16x6_f32in with a diga_conv_options_t (non-null, else DIGA_EINVAL; opt-in: StepConfig.x6_opts next to x6_taps):
+ * its argument list plus `opts` behind stats_partial.  `in` is the SOURCE tensor [N][Hi][Wi]; the loader waves map every tap's
+ * coordinate -- in the image upsampled by 2^upsample_shift -- to its source pixel: mirrored at both borders under reflect_pad, zeros
+ * outside without it; activation 1 is tanh on the output (the direct `_opts` kernels' drain).  Weight image, K-step order, MFMA
+ * sequence and drain are diga_conv_taps_bf16x6_f32in's: the result is, bit for bit, that entry point on the explicitly upsampled and
+ * padded image.  Inference-only: stats_partial must be null and there is no epilogue form; the options' rules are those of
+ * diga_conv2d_nhwc_f32_opts (reflect_pad 0/1, upsample_shift 0..2, activation 0/1); Hi << upsample_shift and Wi << upsample_shift
+ * stay below 2^30; every other check as above. */
+int diga_conv_taps_bf16x6_f32in_opts(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N,
+                                     int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
+                                     int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
+                                     int64_t off_dy, int64_t off_dx, float* stats_partial /* null */, const diga_conv_options_t* opts,
+                                     int prof_tag, void* stream);
 /* ... and their weight gradient dw [Cout][R][S][Cin]: diga_conv2d_wgrad_bf16x6_f32in's arguments with 1 <= R * S <= 64, Cin % 32 == 0
  * and Cout % 8 == 0; one block group per tap, split-K by the bf16x6 plan with the taps counted among the tiles.  The workspace query
  * returns 0 for a shape the entry point rejects (DIGA_EINVAL); a workspace smaller than it asks for: DIGA_EWORKSPACE. */
@@ -613,8 +626,11 @@ int diga_wgrad_bf16x6_tiled_f32in(const float* dy, int64_t dy_ld, const float* x
  *   v_keep (nullable, forward only) as in `_keep`, stats_partial (nullable, tile 4 / 6, forward) as in `_f32`, epi (nullable) as in
  *   `_epi`; same tile table, transforms, shape rules (Cin % 32 == 0, Cout % 4 == 0 and > 64, leading dimensions % 4 == 0, tiles 2 / 4
  *   / 6) and the GEMM's index limits above on (tile + 2)^2 batches of the padded tile count.  Workspace
- *   (diga_conv2d_winograd_bf16x6_workspace_bytes; 0 for a rejected shape) = the fp32 form's + the weight images.  No reflection
- *   padding: that form stays exact fp32.
+ *   (diga_conv2d_winograd_bf16x6_workspace_bytes; 0 for a rejected shape) = the fp32 form's + the weight images.
+ * diga_conv_winograd_bf16x6_opts: diga_conv2d_winograd_f32_opts (same arguments and rules: non-null options of which only reflect_pad
+ *   may be set, forward, no statistics, no epilogue, pad < H, W) on tiles of 4 or 6, with the products on the first GEMM and the
+ *   workspace of diga_conv2d_winograd_bf16x6_workspace_bytes (opt-in: StepConfig.x6_opts next to x6_winograd).  The mirror lives in the
+ *   input transform only; the GEMM and the output transform are diga_conv2d_winograd_bf16x6's.
  * diga_infer_conv2d_winograd_bf16x6: diga_conv2d_winograd_f32_infer (same arguments and rules: tile 4 or 6, forward, no statistics)
  *   with the products on the first GEMM and the workspace of diga_conv2d_winograd_bf16x6_workspace_bytes; bit-identical to
  *   diga_conv2d_winograd_bf16x6 followed by diga_bn_fwd(training = 0).
@@ -636,6 +652,10 @@ int diga_infer_conv2d_winograd_bf16x6(const float* in, const float* wgt, const f
                                       size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld, int64_t Cout,
                                       int64_t out_ld, int64_t dilation, int64_t tile, const diga_infer_epilogue_t* infer,
                                       const void* tile_table, int prof_tag, void* stream);
+int diga_conv_winograd_bf16x6_opts(const float* in, const float* wgt, const float* bias, float* out, void* workspace,
+                                   size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t in_ld, int64_t Cout,
+                                   int64_t out_ld, int64_t dilation, int64_t tile, const diga_conv_options_t* opts,
+                                   const void* tile_table, int prof_tag, void* stream);
 size_t diga_conv2d_wgrad_winograd_bf16x6_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t dilation,
                                                          int64_t tile, int v_kept);
 int diga_conv2d_wgrad_winograd_bf16x6(const float* dy, const float* x, const float* v_kept, float* dw, void* workspace,
