@@ -728,6 +728,233 @@ __global__ __launch_bounds__(512, 2 * wgrad_x6_tile_blocks(BM, BN)) void conv_wg
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// "window form" of the multi-tap forward (diga_conv_window_bf16x6_f32in): stride 1 in the logical image (`in` after nearest upsampling,
+// before padding), 2 <= R * S <= 64 taps.  conv_fwd_x6_kernel<..., TAPS> loads, splits and writes every input element once per tap; here a
+// block owns kWinTH x kWinTW = 8 x 16 output pixels of ONE image (128 rows = 8 sub-tiles of 16 consecutive pixels of one output row) and
+// splits that tile's input window -- WH x WW = (8 + (R - 1) dil_y) x (16 + (S - 1) dil_x) logical pixels of one 32-channel chunk --
+// into LDS once; all R * S taps are then walked from LDS.  Loader work and L2 traffic per output fall by about the tap count.
+//
+// Window.  Pixel wp = wy * WW + wx of the window is the logical pixel (ho0 + oy0 + wy, wo0 + ox0 + wx); it goes through map_tap (mirror,
+// clamp, shift back to the source pixel: no geometry forms an address outside the tensor; under up_shift neighbouring logical pixels
+// repeat a source pixel and are stored once each, as logical pixels).  A pixel of the zero padding issues no load and gets zero planes.
+// Per pixel and plane 64 bytes (32 channels), four 16-byte k-slots, slot s at s ^ lds_swz(wp); the three planes lie WH * WW * 64 bytes
+// apart.  All four waves fill it: an item is (pixel, k-slot), read as two float4 at in_ld (a wave instruction covers 16 pixels x 128
+// bytes), split3x4 -- the loader form's function, so the same planes -- and three ds_write_b128; four items are in flight per thread.
+//
+// K-steps.  One per (32-channel chunk, tap), CHUNK-major: one chunk's window is resident at a time, so the window costs
+// WH * WW * 192 bytes whatever Cin is (7 x 7: 14 x 22 pixels = 57.8 KB; 5 x 5: 12 x 20 = 45 KB).  At Cin = 32 chunk-major and tap-major are
+// the same sequence and a 16 x 16 sub-tile sees the fragments and the MFMA sequence of conv_fwd_x6_kernel<..., TAPS>: the same bits
+// (taps that kernel steps over add exact zeros to a +0 start here).  At Cin > 32 the sums are reassociated across chunks.
+// The A fragment of row (ty, tx) for tap (r, q) is window pixel (ty + r dil_y) * WW + tx + q dil_x = the row's own pixel + an offset that
+// is uniform per K-step; lane l reads k-slot (l >> 4) ^ lds_swz(pixel) of it with ds_read_b128 -- the key is the same function of the
+// window pixel index on both sides.  Bank behaviour: a ds_read_b128 is served in four groups of 16 lanes, 8 rows of one k-slot and 8 of
+// the next; 16 consecutive pixels x 64 bytes span four 256-byte bank lines.  Enumerated on the host over every alignment of a
+// sub-tile's first pixel (its own window pixel + the tap offset): where that index is a multiple of 8 the rows sit as in the M-tiled
+// kernel and lds_swz spreads each group over all 16 slots of a line (no conflict); at every other alignment the key pattern is shifted
+// against the lane groups and two lanes of a group meet on one slot (2-way, 8 instead of 4 LDS cycles per read), never more.  With six
+// (16 columns) or 24 (64 columns) MFMAs behind three reads per sub-tile that stays under the MFMA time of the wide form and about
+// level with it in the narrow one.  (Not measured with counters.)
+//
+// Weights.  The image of diga_split_bf16x6_image, unchanged; K-step (tap, chunk) sits at tap * Cin / 32 + chunk.  Two-stage ring by
+// LDS-DMA, one barrier per K-step (it says "this step's weights have landed" and "the other stage is free").  NC = 64: the 64 rows of the
+// column tile, 12 KB per K-step (column tile ct of a 128-row image = rows 64 (ct & 1) .. of image tile ct >> 1).  NC = 16 (Cout <= 16):
+// rows 0 .. 15 of each plane only, 1 KB per plane and K-step; rows past Cout repeat the last channel and are never stored.  Cout > 64
+// runs ceil(Cout / 64) column tiles, each of which loads and splits the window again.
+//
+// Products and drain.  a1 b1, a0 b2, a2 b0, a0 b1, a1 b0 chained from zero, a0 b0 into the running sum, one fold add per K-step.  Plain
+// drain only: the 128 x NC tile is staged over the (dead) window, then + bias, tanhf under a.act (drain_stage's expressions) and stores
+// at out_ld masked by column and by the tile's ragged right / bottom edge.  No statistics, no epilogues.
+//
+// Residency.  LDS = ring (2 x 3 x NC x 64) + max(window, 128 x (NC + 4) x 4): 7 x 7 narrow 63.8 KB, 5 x 5 wide 69 KB -- two blocks of four
+// waves per CU (2 waves per SIMD, 256 VGPRs each), so one block's window fill runs under the other's MFMAs.
+constexpr int kWinTH = 8, kWinTW = 16;
+
+template <int NC>
+__global__ __launch_bounds__(256, 2) void conv_win_x6_kernel(ConvArgs a) {
+    static_assert(NC == 16 || NC == 64, "16 output columns for Cout <= 16, 64 otherwise");
+    constexpr int NT = NC / 16, MT = 2, B_PLANE = NC * 64, RING = 3 * B_PLANE, LDS_LD = NC + 4;
+    extern __shared__ __align__(16) unsigned char smem_b[];
+    unsigned char* const win = smem_b + 2 * RING;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
+    const int tiles_x = (a.Wo + kWinTW - 1) / kWinTW, tiles_y = (a.Ho + kWinTH - 1) / kWinTH;
+    const int ct = wg % a.tiles_n;
+    wg /= a.tiles_n;
+    const int bx = wg % tiles_x;
+    wg /= tiles_x;
+    const int by = wg % tiles_y, img = wg / tiles_y;
+    const int ho0 = by * kWinTH, wo0 = bx * kWinTW;
+    const int WH = kWinTH + (a.R - 1) * a.ody, WW = kWinTW + (a.S - 1) * a.odx, WPLANE = WH * WW * 64;
+    const int RS = a.R * a.S, cchunks = a.Cin / 32, ksteps = RS * cchunks;
+    const int bn = a.Cout > 64 ? 128 : 64;                       // (image_bn: the weight image's tile)
+    const int img_tile = NC == 16 ? 0 : (bn == 128 ? ct >> 1 : ct), img_half = (NC == 64 && bn == 128) ? (ct & 1) : 0;
+    const unsigned char* wbase = a.wgt_img + (int64_t)img_tile * ksteps * (3 * bn * 64) + img_half * 4096 + lane * 16;
+
+    auto issue_w = [&](int tap, int cc, int buf) {               // LDS-DMA of K-step (tap, cc) into ring stage buf
+        const unsigned char* src = wbase + (int64_t)(tap * cchunks + cc) * (3 * bn * 64);
+        unsigned char* dst = smem_b + buf * RING;
+        if constexpr (NC == 16) {
+            if (wv < 3) DIGA_LDS_DMA16(src + wv * (bn * 64), dst + wv * 1024);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int pc = wv * 3 + c;                       // plane pc >> 2, 1 KB piece pc & 3
+                DIGA_LDS_DMA16(src + (pc >> 2) * (bn * 64) + (pc & 3) * 1024, dst + pc * 1024);
+            }
+        }
+    };
+    const int64_t pix0 = (int64_t)img * a.Hi * a.Wi;
+    const int items = WH * WW * 4;
+    auto load_window = [&](int cc) {                             // chunk cc of the tile's window: load, split, three planes
+        for (int base = 0; base < items; base += 1024) {
+            float4 v[4][2];
+            bool ok[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int idx = base + u * 256 + t;
+                const int wp = idx >> 2, wy = wp / WW, wx = wp - wy * WW;
+                int py, px;                                      // (always a pixel of the source image: map_tap clamps)
+                ok[u] = map_tap(a, ho0 + a.oy0 + wy, wo0 + a.ox0 + wx, py, px) && idx < items;
+                if (ok[u]) {
+                    const float* p = a.in + (pix0 + (int64_t)py * a.Wi + px) * a.in_ld + cc * 32 + (idx & 3) * 8;
+                    v[u][0] = *reinterpret_cast<const float4*>(p);
+                    v[u][1] = *reinterpret_cast<const float4*>(p + 4);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int idx = base + u * 256 + t;
+                if (idx < items) {
+                    uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // zero padding: zero planes
+                    if (ok[u]) {
+                        uint2 a0, a1, a2, b0, b1, b2;
+                        split3x4(v[u][0], a0, a1, a2);
+                        split3x4(v[u][1], b0, b1, b2);
+                        q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
+                        q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
+                        q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
+                    }
+                    const int wp = idx >> 2;
+                    unsigned char* dst = win + wp * 64 + (((idx & 3) ^ lds_swz(wp)) << 4);
+                    *reinterpret_cast<uint4*>(dst) = q0;
+                    *reinterpret_cast<uint4*>(dst + WPLANE) = q1;
+                    *reinterpret_cast<uint4*>(dst + 2 * WPLANE) = q2;
+                }
+            }
+        }
+    };
+
+    f32x4 acc[MT][NT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int frow = lane & 15, fk = lane >> 4;
+    const int boff = frow * 64 + ((fk ^ lds_swz(frow)) << 4);
+    int wp0[MT];                                                 // the rows' own window pixels: tile row wv * MT + i, column frow
+#pragma unroll
+    for (int i = 0; i < MT; ++i) wp0[i] = (wv * MT + i) * WW + frow;
+
+    issue_w(0, 0, 0);
+    int tap = 0, r = 0, q = 0, cc = 0;
+    for (int ks = 0; ks < ksteps; ++ks) {
+        if (tap == 0) {
+            if (cc > 0) __syncthreads();                         // everyone has left the previous chunk's window
+            load_window(cc);
+        }
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();                                         // step ks's weights (and a new window) have landed; stage ks + 1 is free
+        int ntap = tap + 1, ncc = cc;
+        if (ntap == RS) {
+            ntap = 0;
+            ++ncc;
+        }
+        if (ks + 1 < ksteps) issue_w(ntap, ncc, (ks + 1) & 1);
+        const unsigned char* B0 = smem_b + (ks & 1) * RING + boff;
+        bf16x8_t b0[NT], b1[NT], b2[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            b0[j] = *reinterpret_cast<const bf16x8_t*>(B0 + j * 1024);
+            b1[j] = *reinterpret_cast<const bf16x8_t*>(B0 + B_PLANE + j * 1024);
+            b2[j] = *reinterpret_cast<const bf16x8_t*>(B0 + 2 * B_PLANE + j * 1024);
+        }
+        const int toff = r * a.ody * WW + q * a.odx;             // uniform per K-step
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            const int wp = wp0[i] + toff;
+            const unsigned char* A0 = win + wp * 64 + ((fk ^ lds_swz(wp)) << 4);
+            const bf16x8_t a0 = *reinterpret_cast<const bf16x8_t*>(A0);
+            const bf16x8_t a1 = *reinterpret_cast<const bf16x8_t*>(A0 + WPLANE);
+            const bf16x8_t a2 = *reinterpret_cast<const bf16x8_t*>(A0 + 2 * WPLANE);
+            f32x4 tt[NT];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1[j], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2[j], tt[j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0[j], tt[j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1[j], tt[j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0[j], tt[j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[i][j] += tt[j];
+        }
+        if (++q == a.S) {
+            q = 0;
+            ++r;
+        }
+        if (++tap == RS) {
+            tap = r = q = 0;
+            ++cc;
+        }
+    }
+    __syncthreads();                                             // everyone is out of the window: it becomes the drain's stage
+
+    float* stage = reinterpret_cast<float*>(win);
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) stage[((wv * MT + i) * 16 + fk * 4 + e) * LDS_LD + j * 16 + frow] = acc[i][j][e];
+    __syncthreads();
+    constexpr int CQ = NC / 4, RG = 256 / CQ;                    // column quads per row, rows per pass
+    const int cq = t % CQ, rg = t / CQ;
+    const int n = ct * NC + cq * 4;
+    const bool vec_ok = (a.out_ld & 3) == 0 && n + 3 < a.Cout && ((uintptr_t)a.out & 15u) == 0;
+    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.bias != nullptr) {
+        bv.x = n + 0 < a.Cout ? a.bias[n + 0] : 0.f;
+        bv.y = n + 1 < a.Cout ? a.bias[n + 1] : 0.f;
+        bv.z = n + 2 < a.Cout ? a.bias[n + 2] : 0.f;
+        bv.w = n + 3 < a.Cout ? a.bias[n + 3] : 0.f;
+    }
+#pragma unroll
+    for (int p = rg; p < kWinTH * kWinTW; p += RG) {
+        const int ho = ho0 + (p >> 4), wo = wo0 + (p & 15);      // (kWinTW = 16)
+        if (ho < a.Ho && wo < a.Wo && n < a.Cout) {
+            float4 v = *reinterpret_cast<const float4*>(stage + p * LDS_LD + cq * 4);
+            v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
+            if (a.act == 1) {
+                v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w);
+            }
+            float* o = a.out + (((int64_t)img * a.Ho + ho) * a.Wo + wo) * a.out_ld + n;
+            if (vec_ok) {
+                store4_stream(o, v.x, v.y, v.z, v.w);
+            } else {
+                if (n + 0 < a.Cout) o[0] = v.x;
+                if (n + 1 < a.Cout) o[1] = v.y;
+                if (n + 2 < a.Cout) o[2] = v.z;
+                if (n + 3 < a.Cout) o[3] = v.w;
+            }
+        }
+    }
+}
+
 #undef DIGA_LDS_DMA16
 
 }  // namespace diga
@@ -956,6 +1183,96 @@ extern "C" int diga_conv_taps_bf16x6_f32in_opts(const float* in, int64_t in_ld, 
     c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
     c.stats = stats_partial; c.opts = opts; c.prof_tag = prof_tag;
     return conv2d_bf16x6(c);
+}
+
+// ---- the window form of the multi-tap forward (conv_win_x6_kernel)
+namespace {
+// THE window rule (diga_conv_window_bf16x6_plan answers it; the entry point, its LDS size and the Python planner read nothing else):
+// which calls the window form takes, on which tile and with how many output columns per block.  Stride 1 in the logical image is the
+// entry point's signature.  The tile is 8 x 16 for every class; 16 columns serve Cout <= 16, 64 columns everything else; the window of
+// one 32-channel chunk, the weight ring and the drain's staging must fit the CU's 160 KB.
+struct X6Window {
+    int th, tw, cols;
+    int64_t lds;
+};
+bool window_x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t R, int64_t S, int64_t dil_y, int64_t dil_x,
+                    int64_t up_shift, X6Window& w) {
+    if (Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin % 32 != 0 || Cout <= 0) return false;
+    if (R < 1 || S < 1 || R > 64 || S > 64 || R * S < 2 || R * S > 64) return false;
+    if (dil_y < 1 || dil_x < 1 || dil_y > 4096 || dil_x > 4096 || up_shift < 0 || up_shift > 2) return false;
+    w.th = kWinTH;
+    w.tw = kWinTW;
+    w.cols = Cout <= 16 ? 16 : 64;
+    const int64_t window = (kWinTH + (R - 1) * dil_y) * (kWinTW + (S - 1) * dil_x) * 3 * 64;
+    const int64_t stage = (int64_t)kWinTH * kWinTW * (w.cols + 4) * 4, ring = 2 * 3 * w.cols * 64;
+    w.lds = ring + (window > stage ? window : stage);
+    return w.lds <= 160 * 1024;
+}
+
+int conv_window_bf16x6(const ConvCall& c) {
+    DIGA_REQUIRE(c.in && c.wgt_img && c.out, DIGA_EINVAL, "conv_window_bf16x6: null pointer");
+    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0 && c.Cout > 0, DIGA_EINVAL, "conv_window_bf16x6: bad shape");
+    DIGA_REQUIRE(c.R >= 1 && c.S >= 1 && c.R <= 64 && c.S <= 64 && c.R * c.S >= 2 && c.R * c.S <= 64, DIGA_EINVAL,
+                 "conv_window_bf16x6: 2 <= R * S <= 64 taps");
+    DIGA_REQUIRE(c.Cin > 0 && c.Cin % 32 == 0 && c.out_ld >= c.Cout, DIGA_EINVAL, "conv_window_bf16x6: Cin must be a multiple of 32");
+    DIGA_REQUIRE(c.in_ld >= c.Cin && c.in_ld % 4 == 0 && c.in_ld < (1ll << 31) && c.out_ld < (1ll << 31), DIGA_EINVAL,
+                 "conv_window_bf16x6: in_ld must be at least Cin and a multiple of 4");
+    DIGA_REQUIRE(aligned16(c.in) && aligned16(c.wgt_img) && ((uintptr_t)c.out & 3u) == 0 && ((uintptr_t)c.bias & 3u) == 0, DIGA_EALIGN,
+                 "conv_window_bf16x6: alignment");
+    int rc = check_options(c.opts, "conv_window_bf16x6");
+    if (rc) return rc;
+    const int up = c.opts ? c.opts->upsample_shift : 0;
+    rc = check_tap_coordinates(c, "conv_window_bf16x6", up);
+    if (rc) return rc;
+    X6Window w;
+    DIGA_REQUIRE(window_x6_plan(c.Hi, c.Wi, c.Cin, c.Cout, c.R, c.S, c.off_dy, c.off_dx, up, w), DIGA_EINVAL,
+                 "conv_window_bf16x6: the window form does not take this call (diga_conv_window_bf16x6_plan)");
+    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv_window_bf16x6: too many pixels");
+    if (c.opts && c.opts->reflect_pad) {                          // a mirror reaches at most the far border (nn.ReflectionPad2d's rule)
+        const int64_t Hl = c.Hi << up, Wl = c.Wi << up;
+        const int64_t y_hi = c.Ho - 1 + c.off_y0 + (c.R - 1) * c.off_dy, x_hi = c.Wo - 1 + c.off_x0 + (c.S - 1) * c.off_dx;
+        DIGA_REQUIRE(-c.off_y0 < Hl && -c.off_x0 < Wl && y_hi - (Hl - 1) < Hl && x_hi - (Wl - 1) < Wl, DIGA_EINVAL,
+                     "conv_window_bf16x6: reflection padding must be smaller than the (upsampled) image");
+    }
+    const int64_t tiles_n = ceil_div(c.Cout, w.cols);
+    const int64_t grid = c.N * ceil_div(c.Ho, w.th) * ceil_div(c.Wo, w.tw) * tiles_n;
+    DIGA_REQUIRE(grid < (1ll << 31), DIGA_EINVAL, "conv_window_bf16x6: too many tiles for one launch");
+    ConvArgs a;
+    rc = fill_conv_args(a, c, "conv_window_bf16x6", "conv_window_bf16x6");
+    if (rc) return rc;
+    a.tiles_n = (int)tiles_n;
+    hipStream_t st = (hipStream_t)c.stream;
+    ProfScope prof(conv_prof_tag(c), st, conv_flops(c));
+    launch_k(w.cols == 16 ? conv_win_x6_kernel<16> : conv_win_x6_kernel<64>, (unsigned)grid, 256, (size_t)w.lds, st, a);
+    return launch_status("diga_conv_window_bf16x6_f32in");
+}
+}  // namespace
+
+// Returns 1 and the tile (th x tw output pixels, th * tw % 128 == 0) and the output columns per block (16 for Cout <= 16, else 64) where
+// the window form takes a stride-1 convolution of R x S taps at dilation (dil_y, dil_x) on the 2^upsample_shift upsampling of an
+// Hi x Wi x Cin image; 0 (and nothing written) where it does not.
+extern "C" int diga_conv_window_bf16x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t R, int64_t S, int64_t dil_y,
+                                            int64_t dil_x, int64_t upsample_shift, int* th, int* tw, int* cols) {
+    X6Window w;
+    if (!th || !tw || !cols || !window_x6_plan(Hi, Wi, Cin, Cout, R, S, dil_y, dil_x, upsample_shift, w)) return 0;
+    *th = w.th;
+    *tw = w.tw;
+    *cols = w.cols;
+    return 1;
+}
+
+// The multi-tap forward on the window form: stride 1, taps at (off_y0 + r * dil_y, off_x0 + q * dil_x) of the logical image; `opts`
+// (nullable) as in diga_conv_taps_bf16x6_f32in_opts.  Plain forward: bias, optional tanh, no statistics, no epilogue.
+extern "C" int diga_conv_window_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N,
+                                             int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
+                                             int64_t R, int64_t S, int64_t off_y0, int64_t off_x0, int64_t dil_y, int64_t dil_x,
+                                             const diga_conv_options_t* opts, int prof_tag, void* stream) {
+    const int64_t stride_y = 1, stride_x = 1, off_dy = dil_y, off_dx = dil_x;
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
+    c.opts = opts; c.prof_tag = prof_tag;
+    return conv_window_bf16x6(c);
 }
 
 namespace {

@@ -95,6 +95,18 @@ def _taps_ok(cin, r, s, copt):
     return 1 < r * s <= 64 and cin % 32 == 0 and (not copt or _x6_opts())
 
 
+def _x6_window(hi, wi, cin, k, r, s, doff, shift):
+    """True when config.x6_window is in force (conv_math = 2 with x6_taps; read per call) AND the library's window rule
+    (diga_conv_window_bf16x6_plan, the one place that decides) takes a stride-1 forward of r x s taps at dilation doff on the
+    2^shift upsampling of an hi x wi x cin image with k output channels: the call then runs on the window form ("x6win",
+    diga_conv_window_bf16x6_f32in).  Only _plan asks, for a forward without statistics and without an epilogue."""
+    if not (_x6_taps() and config.active().x6_window) or doff[0] < 1 or doff[1] < 1:
+        return False
+    th, tw, cols = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    return _lib.lib.diga_conv_window_bf16x6_plan(hi, wi, cin, k, r, s, doff[0], doff[1], shift, ctypes.byref(th), ctypes.byref(tw),
+                                                 ctypes.byref(cols)) == 1
+
+
 def _x6_fit(kp, cp):
     """True when config.x6_wgrad_tile = "fit" is in force (conv_math = 2; both read per call) AND the library's tile rule
     (diga_wgrad_bf16x6_tile, the one place that decides) gives a layer with kp (padded) output and cp input channels something other
@@ -295,7 +307,8 @@ class _Path(NamedTuple):
     """Which kernel ONE convolution call runs on.  _plan (forward / backward-data) and _wgrad_plan (weight gradient) decide it, once
     per call, from the call's geometry, the features it wants and the active configuration; everything else -- the launch, the
     statistics buffer DigaConv2d allocates, infer_kernel, winograd_stats_plan, what a forward saves for its backward -- reads it."""
-    family: str                # "x6ls" (bf16x6, operands split by the loader waves) / "x6" (bf16x6 on triplets) / "x6rs" (multi-tap bf16x6) / "twin" / "bf16x3" /
+    family: str                # "x6ls" (bf16x6, operands split by the loader waves) / "x6" (bf16x6 on triplets) / "x6rs" (multi-tap bf16x6) /
+    #                            "x6win" (multi-tap bf16x6 from an LDS window: config.x6_window) / "twin" / "bf16x3" /
     #                            "winograd" / "winograd_reflect" (reflection padding folded into the input transform) / "f32"
     variant: str               # "" / "epi" (backward-data epilogue) / "opts" / "infer" / "keep" (Winograd forward that keeps V)
     math: int                  # the layer's arithmetic (_layer_math): the `math` argument the library is given
@@ -366,6 +379,10 @@ def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, sta
         if infer and not fold_x6:
             raise RuntimeError("DigaConv2d: the multi-tap bf16x6 kernels' inference epilogue needs config.fold_eval_bn_x6 (check "
                                "infer_kernel / folds_eval_bn first)")
+        if (tag == _TAG_FWD and stats is None and not epi and not infer and tuple(stride) == (1, 1)
+                and _x6_window(hi, wi, cin, k, r, s, doff, opts[1] if copt else 0)):
+            # a stride-1 plain forward the window rule admits: the tile's input window split into LDS once (config.x6_window)
+            return _Path("x6win", variant, 2, "bf16x6/window")
         return _Path("x6rs", variant, 2, "bf16x6/taps+bn" if infer else "bf16x6/taps")
     return _Path("f32", variant, 0, "f32+bn" if infer else "f32")
 
@@ -468,6 +485,7 @@ _ENTRY = {
     ("x6ls", "infer"): "diga_infer_conv2d_nhwc_bf16x6_f32in",
     ("x6rs", ""): "diga_conv_taps_bf16x6_f32in", ("x6rs", "epi"): "diga_conv_taps_bf16x6_f32in_epi",
     ("x6rs", "infer"): "diga_infer_conv_taps_bf16x6_f32in", ("x6rs", "opts"): "diga_conv_taps_bf16x6_f32in_opts",
+    ("x6win", ""): "diga_conv_window_bf16x6_f32in", ("x6win", "opts"): "diga_conv_window_bf16x6_f32in",
     ("x6", ""): "diga_conv2d_nhwc_bf16x6", ("x6", "epi"): "diga_conv2d_nhwc_bf16x6_epi", ("x6", "infer"): "diga_infer_conv2d_nhwc_bf16x6",
     ("twin", ""): "diga_conv2d_nhwc_twin", ("twin", "epi"): "diga_conv2d_nhwc_twin_epi", ("twin", "opts"): "diga_conv2d_nhwc_twin_opts",
     ("bf16x3", ""): "diga_conv2d_nhwc_bf16x3", ("bf16x3", "epi"): "diga_conv2d_nhwc_bf16x3_epi",
@@ -488,7 +506,7 @@ def _operands(path, x, w_krsc, twin_box):
     behind them, the twin / triplet of x to hand back).  The weight image / split lives until the launch returns."""
     n, hi, wi, cin = x.shape
     k, r, s, _ = w_krsc.shape
-    if path.family in ("x6ls", "x6rs"):
+    if path.family in ("x6ls", "x6rs", "x6win"):
         # loader form: the activations are read as fp32 in place (contiguous or a channel slice) -- no triplet is built, returned or
         # looked for in the box
         split, ld = None, _nhwc_ld(x)
@@ -502,7 +520,7 @@ def _operands(path, x, w_krsc, twin_box):
             if twin_box is not None:
                 twin_box[0] = split
         act = [_lib.ptr(split)]
-    if path.family in ("x6ls", "x6rs", "x6", "twin"):
+    if path.family in ("x6ls", "x6rs", "x6win", "x6", "twin"):
         size, fill = ((_lib.lib.diga_split_bf16_image_bytes, "diga_split_bf16_image") if path.family == "twin" else
                       (_lib.lib.diga_split_bf16x6_image_bytes, "diga_split_bf16x6_image"))
         img = torch.empty(size(k, r * s, cin), dtype=torch.uint8, device=x.device)
@@ -580,6 +598,11 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
         _winograd_launch(path, x, w_krsc, bias, out, abs(doff[0]), 1 if doff[0] < 0 else 0, tag, stats, struct, keep_v)
         return None
     lead, held, split = _operands(path, x, w_krsc, twin_box)         # (`held`, `inf_held`: alive until the kernel is enqueued)
+    if path.family == "x6win":
+        # stride 1 is the entry point's signature; the options are nullable (variant "": a plain zero-padded convolution)
+        _lib.call(_ENTRY[(path.family, path.variant)], *lead, _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin, ho, wo, k, out.stride(2), r, s,
+                  off0[0], off0[1], doff[0], doff[1], struct, tag, _lib.stream())
+        return split
     _lib.call(_ENTRY[(path.family, path.variant)], *lead, *(() if path.variant == "epi" else (_lib.ptr(bias),)), _lib.ptr(out),
               n, hi, wi, cin, *((x.stride(2),) if path.family in ("bf16x3", "f32") else ()), ho, wo, k, out.stride(2), r, s,
               stride[0], stride[1], off0[0], off0[1], doff[0], doff[1],

@@ -576,6 +576,28 @@ int diga_conv_taps_bf16x6_f32in_opts(const float* in, int64_t in_ld, const void*
                                      int64_t R, int64_t S, int64_t stride_y, int64_t stride_x, int64_t off_y0, int64_t off_x0,
                                      int64_t off_dy, int64_t off_dx, float* stats_partial /* null */, const diga_conv_options_t* opts,
                                      int prof_tag, void* stream);
+/* The "window form" of the multi-tap forward (opt-in: StepConfig.x6_window next to x6_taps under conv_math = 2): for convolutions of
+ * stride 1 in the logical image (`in` upsampled by 2^upsample_shift, before padding) a block owns th x tw output pixels of one image
+ * and splits their input window -- (th + (R - 1) dil_y) x (tw + (S - 1) dil_x) logical pixels of one 32-channel chunk, every pixel
+ * through the `_opts` form's map (mirror, clamp, shift to the source pixel; zero planes and no load for zero padding) -- into LDS
+ * once; all R * S taps are walked from there.  K-steps run chunk-major: at Cin == 32 the result is, bit for bit,
+ * diga_conv_taps_bf16x6_f32in[_opts]'s; at Cin > 32 the same products are summed chunk by chunk (same error level).  Cout > 64 runs
+ * ceil(Cout / 64) column tiles, each splitting the window again.
+ *
+ * diga_conv_window_bf16x6_plan: a pure query, the one statement of the rule.  Returns 1 and *th, *tw (th * tw % 128 == 0; 8 x 16)
+ *   and *cols (16 for Cout <= 16, else 64) where the window form takes the call, 0 (nothing written) where it does not: Cin not a
+ *   positive multiple of 32, R * S outside 2 .. 64, a dilation below 1, upsample_shift outside 0 .. 2, null pointers, or a window
+ *   that does not fit: 2 * 3 * cols * 64 (weight ring) + max(window pixels * 192, th * tw * (cols + 4) * 4) > 160 KB.
+ * diga_conv_window_bf16x6_f32in: taps at (off_y0 + r * dil_y, off_x0 + q * dil_x), stride 1; `opts` nullable (its rules as above);
+ *   bias and tanh as in the `_opts` form, no statistics, no epilogue.  DIGA_EINVAL for everything the rule refuses, for in_ld < Cin
+ *   or in_ld % 4 != 0, out_ld < Cout, and for reflection padding not smaller than the logical extent; DIGA_EALIGN for `in` / `wgt_img`
+ *   off 16 bytes or `out` / `bias` off 4.  The weight image is diga_split_bf16x6_image's. */
+int diga_conv_window_bf16x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t R, int64_t S, int64_t dil_y, int64_t dil_x,
+                                 int64_t upsample_shift, int* th, int* tw, int* cols);
+int diga_conv_window_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N,
+                                  int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R,
+                                  int64_t S, int64_t off_y0, int64_t off_x0, int64_t dil_y, int64_t dil_x,
+                                  const diga_conv_options_t* opts /* nullable */, int prof_tag, void* stream);
 /* ... and their weight gradient dw [Cout][R][S][Cin]: diga_conv2d_wgrad_bf16x6_f32in's arguments with 1 <= R * S <= 64, Cin % 32 == 0
  * and Cout % 8 == 0; one block group per tap, split-K by the bf16x6 plan with the taps counted among the tiles.  The workspace query
  * returns 0 for a shape the entry point rejects (DIGA_EINVAL); a workspace smaller than it asks for: DIGA_EWORKSPACE. */

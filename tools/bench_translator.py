@@ -5,11 +5,13 @@ no_grad) under three settings, in alternated rounds on one box:
     mode0      conv_math 0 (exact fp32: the direct `_opts` kernels and fp32 Winograd with the mirror in the input transform)
     x6         conv_math 2, x6_split = "loader", x6_taps, x6_winograd            (x6_opts off: the 21 calls with options stay as in mode0)
     x6+opts    ... and x6_opts: those calls on the multi-tap bf16x6 kernels and on Winograd with bf16x6 products
+    x6+win     ... and x6_window (--x6-window only): the stride-1 multi-tap layers the window rule admits on the window form
 
-    python tools/bench_translator.py [--rounds 3] [--reps 3] [--batch 8] [--size 768] [--layers]
+    python tools/bench_translator.py [--rounds 3] [--reps 3] [--batch 8] [--size 768] [--layers] [--x6-window]
 
 Per setting: conv.path_log and the `_opts` entry points of one pass, then ms per pass of every round (device events around --reps
-passes), the median and the spread.  --layers adds the five distinct folded layer shapes one by one, x6 against x6+opts.  Needs the GPU."""
+passes), the median and the spread.  --layers adds the five distinct folded layer shapes one by one, x6 against x6+opts (and, with
+--x6-window, against x6+win; every round's time is printed, so the settings can be compared pair by pair).  Needs the GPU."""
 import argparse
 import os
 import statistics
@@ -68,7 +70,10 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--size", type=int, default=768)
     ap.add_argument("--layers", action="store_true")
+    ap.add_argument("--x6-window", action="store_true", help="add the setting x6+win: x6+opts with config.x6_window")
     a = ap.parse_args()
+    if a.x6_window:
+        SETTINGS.append(("x6+win", dict(X6, x6_opts=True, x6_window=True)))
     if not torch.cuda.is_available():
         sys.exit("bench_translator: needs the GPU")
     dev = "cuda"
@@ -96,16 +101,22 @@ def main():
             t = times[name]
             print(f"{name:8s} median {statistics.median(t):8.2f} ms per {a.batch} crops (min {min(t):.2f}, max {max(t):.2f})")
         if a.layers:
-            print("\nper layer (ms per call; count = calls per pass), x6 (the fp32 `_opts` kernel) against x6+opts:")
+            print("\nper layer (ms per call; count = calls per pass; median [path] (rounds)), x6 (the fp32 `_opts` kernel) against "
+                  + " and ".join(name for name, _ in SETTINGS[2:]) + ":")
             for lname, count, cin, cout, k, stride, pad, div, opts in LAYERS:
                 m = dc.DigaConv2d(cin, cout, k, stride, padding=pad, bias=True).to(dev).eval()
                 xs = torch.randn((a.batch, cin, a.size // div, a.size // div), device=dev).contiguous(memory_format=torch.channels_last)
-                row = []
+                row, logs, ts = [], {}, {name: [] for name, _ in SETTINGS[1:]}
                 for name, cfg in SETTINGS[1:]:
                     with config.override(**cfg):
-                        log, _ = logged(lambda: m(xs, opts=opts))
-                        ts = [timed(lambda: m(xs, opts=opts), a.reps) for _ in range(a.rounds)]
-                    row.append(f"{name} {statistics.median(ts):7.3f} ms [{', '.join(k2[1] for k2 in log)}]")
+                        logs[name], _ = logged(lambda: m(xs, opts=opts))
+                for _ in range(a.rounds):                # alternated: round r of every setting back to back
+                    for name, cfg in SETTINGS[1:]:
+                        with config.override(**cfg):
+                            ts[name].append(timed(lambda: m(xs, opts=opts), a.reps))
+                for name, _ in SETTINGS[1:]:
+                    row.append(f"{name} {statistics.median(ts[name]):7.3f} ms [{', '.join(k2[1] for k2 in logs[name])}] "
+                               f"({', '.join(f'{t:.3f}' for t in ts[name])})")
                 print(f"{lname:22s} x{count:<3d} " + "  |  ".join(row))
                 del m, xs
                 torch.cuda.empty_cache()
