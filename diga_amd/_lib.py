@@ -91,6 +91,9 @@ SIGNATURES = {
     "diga_conv_taps_bf16x6_f32in_opts": (INT, [P, I64, P, P, P] + [I64] * 16 + [P, P, INT, P]),
     "diga_conv_window_bf16x6_plan": (INT, [I64] * 9 + [P, P, P]),
     "diga_conv_window_bf16x6_f32in": (INT, [P, I64, P, P, P] + [I64] * 14 + [P, INT, P]),
+    "diga_conv_up2_bf16x6_plan": (INT, [I64] * 14 + [P, P]),
+    "diga_collapse_up2_weights": (INT, [P, P] + [I64] * 6 + [P]),
+    "diga_conv_up2_bf16x6_f32in": (INT, [P, I64, P, P, P, P] + [I64] * 12 + [P, INT, P]),
     "diga_conv_taps_wgrad_bf16x6_workspace_bytes": (SZ, [I64] * 7),
     "diga_conv_taps_wgrad_bf16x6_f32in": (INT, [P, I64, P, I64, P, P, SZ] + [I64] * 15 + [P]),
     "diga_wgrad_bf16x6_tile": (INT, [I64, I64, P, P]),

@@ -48,6 +48,7 @@ class StepConfig:
     x6_taps: bool = False                # conv_math 2 only: every multi-tap convolution that would run on the direct fp32 kernels (Cin % 32 == 0, no folded options), and the stem's im2col GEMM, on bf16x6 as well (loader form, whatever x6_split says)
     x6_opts: bool = False                # conv_math 2 only: lifts the "no folded options" exclusion of x6_taps and x6_winograd and nothing else -- a call with a diga_conv_options_t (reflection padding / nearest upsampling / tanh folded into the kernel: the frozen translator) is planned by the same rules as one without: multi-tap calls on the multi-tap bf16x6 kernels (with x6_taps), the products of the reflect-padded Winograd layers on bf16x6 (with x6_winograd); pointwise calls with options stay exact fp32
     x6_window: bool = False              # conv_math 2 with x6_taps only: a stride-1 multi-tap forward without statistics and without an epilogue that diga_conv_window_bf16x6_plan admits runs on the window form (diga_conv_window_bf16x6_f32in: the tile's input window split into LDS once, all taps walked from there); with folded options only next to x6_opts; everything else keeps its path; read per call
+    x6_up2: bool = False                 # conv_math 2 with x6_taps, x6_opts and x6_window only: a window-form forward of a 2x nearest-upsampled input that diga_conv_up2_bf16x6_plan admits runs its interior tiles on phase-collapsed weights (diga_conv_up2_bf16x6_f32in: four stride-1 convolutions of the SOURCE image, one per output parity, R' x S' summed taps instead of R x S) and only the ring of border tiles on the window walk; everything else keeps its path; read per call
     x6_wgrad_tile: str = "wide"          # conv_math 2 only: the loader-form bf16x6 weight gradient ("x6ls" / "x6rs") on "wide" = the one 256 x 128 tile, or "fit" = the tile diga_wgrad_bf16x6_tile picks for the layer (64x64 / 64x128 / 128x128 / 256x64 for the narrow layers, another split-K plan; 256 x 128 layers unchanged); read per call
     winograd: bool = True
     winograd_ratio: float = 0.62
@@ -96,6 +97,7 @@ class StepConfig:
         c.x6_taps = _flag("DIGA_X6_TAPS", c.x6_taps)
         c.x6_opts = _flag("DIGA_X6_OPTS", c.x6_opts)
         c.x6_window = _flag("DIGA_X6_WINDOW", c.x6_window)
+        c.x6_up2 = _flag("DIGA_X6_UP2", c.x6_up2)
         c.x6_wgrad_tile = e("DIGA_X6_WGRAD_TILE", c.x6_wgrad_tile)
         c.winograd = _flag("DIGA_CONV_WINOGRAD", c.winograd)
         c.winograd_ratio = float(e("DIGA_CONV_WINOGRAD_RATIO", c.winograd_ratio))
@@ -140,6 +142,8 @@ class StepConfig:
             raise ValueError(f"x6_opts must be a bool, not {self.x6_opts!r}")
         if not isinstance(self.x6_window, bool):
             raise ValueError(f"x6_window must be a bool, not {self.x6_window!r}")
+        if not isinstance(self.x6_up2, bool):
+            raise ValueError(f"x6_up2 must be a bool, not {self.x6_up2!r}")
         if self.x6_wgrad_tile not in ("wide", "fit"):
             raise ValueError(f"x6_wgrad_tile must be 'wide' or 'fit', not {self.x6_wgrad_tile!r}")
         if not isinstance(self.fold_eval_bn, bool):

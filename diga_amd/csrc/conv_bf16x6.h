@@ -768,32 +768,79 @@ __global__ __launch_bounds__(512, 2 * wgrad_x6_tile_blocks(BM, BN)) void conv_wg
 //
 // Residency.  LDS = ring (2 x 3 x NC x 64) + max(window, 128 x (NC + 4) x 4): 7 x 7 narrow 63.8 KB, 5 x 5 wide 69 KB -- two blocks of four
 // waves per CU (2 waves per SIMD, 256 VGPRs each), so one block's window fill runs under the other's MFMAs.
+//
+// The three forms of the one kernel (the fill, the K-steps, the weight ring, the products and the drain are written once):
+//   kWinAll   conv_win_x6_kernel<NC>: every tile of the output, as described above.
+//   kWinRing  conv_win_x6_kernel<64, RING>: the same walk on the BORDER tiles only (by in {0, tiles_y - 1} or bx in {0, tiles_x - 1}; a block
+//             index enumerates the top row, the bottom row, then the left / right tiles of the rows between).  Everything behind the block's
+//             (img, by, bx, ct) is kWinAll's, so a ring tile's bits are the window form's.
+//   kWinUp2   conv_up2_x6_kernel = conv_win_x6_kernel<64, false, UP2>: the INTERIOR tiles of a 2x nearest-upsampled input on phase-collapsed
+//             weights (diga_conv_up2_bf16x6_f32in; the rule up2_x6_plan admits only calls whose interior taps all lie inside the logical
+//             image; the ring form does the border tiles of the same call).  Output pixel (2 y + fy, 2 x + fx)
+//             reads source rows y + a(fy, r), a(f, r) = floor((f + oy0 + r) / 2): per output phase (fy, fx) a stride-1 convolution of the SOURCE
+//             image with R' x S' summed taps (diga_collapse_up2_weights) whose first tap sits at (a(fy, 0), a(fx, 0)).  A block does one phase
+//             of 8 x 16 SOURCE pixels (grid anchored at the first interior output pixel = source pixel (4, 8)); its window is
+//             (8 + R' - 1) x (16 + S' - 1) source pixels (5 x 5: 10 x 18 x 192 B = 34.6 KB), addresses clamped into the image (interior pixels
+//             never read a clamped value under a non-zero weight); its weights are the phase's image, images image_bytes(Cout, R' S', Cin)
+//             apart.  The launcher passes R', S' as a.R, a.S with unit dilation and leaves the call's own (oy0, ox0), Ho, Wo; stores are masked
+//             to the pixels of interior tiles.  Per output pixel: the window form's K-step and product sequence on the collapsed weights.
 constexpr int kWinTH = 8, kWinTW = 16;
+constexpr int kWinAll = 0, kWinRing = 1, kWinUp2 = 2;
 
-template <int NC>
+template <int NC, bool RING = false, bool UP2 = false>
 __global__ __launch_bounds__(256, 2) void conv_win_x6_kernel(ConvArgs a) {
+    constexpr int FORM = UP2 ? kWinUp2 : RING ? kWinRing : kWinAll;
+    static_assert(!(RING && UP2), "a block is a ring tile or an interior tile");
     static_assert(NC == 16 || NC == 64, "16 output columns for Cout <= 16, 64 otherwise");
-    constexpr int NT = NC / 16, MT = 2, B_PLANE = NC * 64, RING = 3 * B_PLANE, LDS_LD = NC + 4;
+    static_assert(FORM == kWinAll || NC == 64, "the ring and the collapsed interior come with 64 columns");
+    constexpr int NT = NC / 16, MT = 2, B_PLANE = NC * 64, WRING = 3 * B_PLANE, LDS_LD = NC + 4;
     extern __shared__ __align__(16) unsigned char smem_b[];
-    unsigned char* const win = smem_b + 2 * RING;
+    unsigned char* const win = smem_b + 2 * WRING;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int tiles_x = (a.Wo + kWinTW - 1) / kWinTW, tiles_y = (a.Ho + kWinTH - 1) / kWinTH;
     const int ct = wg % a.tiles_n;
     wg /= a.tiles_n;
-    const int bx = wg % tiles_x;
-    wg /= tiles_x;
-    const int by = wg % tiles_y, img = wg / tiles_y;
-    const int ho0 = by * kWinTH, wo0 = bx * kWinTW;
+    int bx, by, img, phy = 0, phx = 0;                           // (phy, phx): kWinUp2's output phase
+    if constexpr (FORM == kWinUp2) {                             // (by, bx): a tile of SOURCE pixels, the four phases of one tile adjacent
+        const int stx = (tiles_x - 1) >> 1, sty = (tiles_y - 1) >> 1;        // ceil(8 (tiles_x - 2) / 16), ceil(4 (tiles_y - 2) / 8)
+        phx = wg & 1;
+        phy = (wg >> 1) & 1;
+        wg >>= 2;
+        bx = wg % stx;
+        wg /= stx;
+        by = wg % sty;
+        img = wg / sty;
+    } else if constexpr (FORM == kWinRing) {
+        const int ring = 2 * tiles_x + 2 * (tiles_y - 2);        // (tiles_x, tiles_y >= 3: the rule)
+        const int i = wg % ring;
+        img = wg / ring;
+        if (i < 2 * tiles_x) {
+            by = i < tiles_x ? 0 : tiles_y - 1;
+            bx = i < tiles_x ? i : i - tiles_x;
+        } else {
+            by = 1 + ((i - 2 * tiles_x) >> 1);
+            bx = (i & 1) ? tiles_x - 1 : 0;
+        }
+    } else {
+        bx = wg % tiles_x;
+        wg /= tiles_x;
+        by = wg % tiles_y;
+        img = wg / tiles_y;
+    }
+    // the tile's first output pixel; kWinUp2: its first SOURCE pixel, and the phase's first tap there
+    const int ho0 = FORM == kWinUp2 ? 4 + by * kWinTH : by * kWinTH, wo0 = FORM == kWinUp2 ? 8 + bx * kWinTW : bx * kWinTW;
+    const int ay0 = (phy + a.oy0) >> 1, ax0 = (phx + a.ox0) >> 1;            // floor((f + off0) / 2); read by kWinUp2 only
     const int WH = kWinTH + (a.R - 1) * a.ody, WW = kWinTW + (a.S - 1) * a.odx, WPLANE = WH * WW * 64;
     const int RS = a.R * a.S, cchunks = a.Cin / 32, ksteps = RS * cchunks;
     const int bn = a.Cout > 64 ? 128 : 64;                       // (image_bn: the weight image's tile)
     const int img_tile = NC == 16 ? 0 : (bn == 128 ? ct >> 1 : ct), img_half = (NC == 64 && bn == 128) ? (ct & 1) : 0;
     const unsigned char* wbase = a.wgt_img + (int64_t)img_tile * ksteps * (3 * bn * 64) + img_half * 4096 + lane * 16;
+    if constexpr (FORM == kWinUp2) wbase += (int64_t)(phy * 2 + phx) * ((a.Cout + bn - 1) / bn) * ksteps * (3 * bn * 64);
 
     auto issue_w = [&](int tap, int cc, int buf) {               // LDS-DMA of K-step (tap, cc) into ring stage buf
         const unsigned char* src = wbase + (int64_t)(tap * cchunks + cc) * (3 * bn * 64);
-        unsigned char* dst = smem_b + buf * RING;
+        unsigned char* dst = smem_b + buf * WRING;
         if constexpr (NC == 16) {
             if (wv < 3) DIGA_LDS_DMA16(src + wv * (bn * 64), dst + wv * 1024);
         } else {
@@ -815,7 +862,13 @@ __global__ __launch_bounds__(256, 2) void conv_win_x6_kernel(ConvArgs a) {
                 const int idx = base + u * 256 + t;
                 const int wp = idx >> 2, wy = wp / WW, wx = wp - wy * WW;
                 int py, px;                                      // (always a pixel of the source image: map_tap clamps)
-                ok[u] = map_tap(a, ho0 + a.oy0 + wy, wo0 + a.ox0 + wx, py, px) && idx < items;
+                if constexpr (FORM == kWinUp2) {                 // a source pixel, clamped into the image
+                    py = min(max(ho0 + ay0 + wy, 0), a.Hi - 1);
+                    px = min(max(wo0 + ax0 + wx, 0), a.Wi - 1);
+                    ok[u] = idx < items;
+                } else {
+                    ok[u] = map_tap(a, ho0 + a.oy0 + wy, wo0 + a.ox0 + wx, py, px) && idx < items;
+                }
                 if (ok[u]) {
                     const float* p = a.in + (pix0 + (int64_t)py * a.Wi + px) * a.in_ld + cc * 32 + (idx & 3) * 8;
                     v[u][0] = *reinterpret_cast<const float4*>(p);
@@ -871,7 +924,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_x6_kernel(ConvArgs a) {
             ++ncc;
         }
         if (ks + 1 < ksteps) issue_w(ntap, ncc, (ks + 1) & 1);
-        const unsigned char* B0 = smem_b + (ks & 1) * RING + boff;
+        const unsigned char* B0 = smem_b + (ks & 1) * WRING + boff;
         bf16x8_t b0[NT], b1[NT], b2[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
@@ -935,8 +988,14 @@ __global__ __launch_bounds__(256, 2) void conv_win_x6_kernel(ConvArgs a) {
     }
 #pragma unroll
     for (int p = rg; p < kWinTH * kWinTW; p += RG) {
-        const int ho = ho0 + (p >> 4), wo = wo0 + (p & 15);      // (kWinTW = 16)
-        if (ho < a.Ho && wo < a.Wo && n < a.Cout) {
+        int ho = ho0 + (p >> 4), wo = wo0 + (p & 15);            // (kWinTW = 16)
+        bool inside = ho < a.Ho && wo < a.Wo;
+        if constexpr (FORM == kWinUp2) {                         // (ho, wo) is a source pixel: only pixels of interior tiles are this form's
+            inside = ho < 4 * (tiles_y - 1) && wo < 8 * (tiles_x - 1);
+            ho = 2 * ho + phy;
+            wo = 2 * wo + phx;
+        }
+        if (inside && n < a.Cout) {
             float4 v = *reinterpret_cast<const float4*>(stage + p * LDS_LD + cq * 4);
             v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
             if (a.act == 1) {
@@ -952,6 +1011,35 @@ __global__ __launch_bounds__(256, 2) void conv_win_x6_kernel(ConvArgs a) {
                 if (n + 3 < a.Cout) o[3] = v.w;
             }
         }
+    }
+}
+
+// (A body shared through a __device__ function gave the existing instantiations another register allocation; as one template they keep
+// their instruction streams, and the collapsed interior is its third form under a name of its own.)
+constexpr auto conv_up2_x6_kernel = conv_win_x6_kernel<64, false, true>;
+
+// Phase-collapsed weights of a convolution on a 2x nearest-upsampled input: w [K][R][S][C] -> wc [fy][fx][K][RC][SC][C], element
+// (r', s') = the sum of the taps (r, s) with a(fy, r) - a(fy, 0) == r' and a(fx, s) - a(fx, 0) == s', a(f, r) = floor((f + off0 + r) / 2):
+// taken in double, in ascending (r, s) order, rounded to fp32 once (a phase with fewer taps keeps zeros in the rest).
+__global__ __launch_bounds__(256) void collapse_up2_kernel(const float* __restrict__ w, float* __restrict__ wc, int K, int R, int S, int C,
+                                                           int oy0, int ox0, int RC, int SC, int64_t total) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        int64_t u = i / C;
+        const int sp = (int)(u % SC);
+        u /= SC;
+        const int rp = (int)(u % RC);
+        u /= RC;
+        const int k = (int)(u % K), ph = (int)(u / K);
+        const int fy = ph >> 1, fx = ph & 1;
+        const int ay0 = (fy + oy0) >> 1, ax0 = (fx + ox0) >> 1;
+        double sum = 0.0;
+        for (int r = 0; r < R; ++r) {
+            if (((fy + oy0 + r) >> 1) - ay0 != rp) continue;
+            for (int q = 0; q < S; ++q)
+                if (((fx + ox0 + q) >> 1) - ax0 == sp) sum += (double)w[(((int64_t)k * R + r) * S + q) * C + c];
+        }
+        wc[i] = (float)sum;
     }
 }
 
@@ -1273,6 +1361,139 @@ extern "C" int diga_conv_window_bf16x6_f32in(const float* in, int64_t in_ld, con
     c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
     c.opts = opts; c.prof_tag = prof_tag;
     return conv_window_bf16x6(c);
+}
+
+// ---- the window form of a 2x nearest-upsampled input on phase-collapsed weights (conv_up2_x6_kernel + the ring of conv_win_x6_kernel)
+namespace {
+inline int64_t up2_a(int64_t phase, int64_t off0, int64_t r) {        // floor((phase + off0 + r) / 2): the source row of tap r
+    const int64_t v = phase + off0 + r;
+    return v >= 0 ? v / 2 : -((-v + 1) / 2);
+}
+inline int up2_taps(int64_t R, int64_t off0) {                        // R': the widest phase's collapsed tap count
+    int64_t m = 0;
+    for (int64_t f = 0; f < 2; ++f) m = std::max(m, up2_a(f, off0, R - 1) - up2_a(f, off0, 0) + 1);
+    return (int)m;
+}
+
+// THE rule (diga_conv_up2_bf16x6_plan answers it; the entry point, its LDS size and the Python planner read nothing else): which window-form
+// calls run their interior tiles on phase-collapsed weights.  The window rule must admit the call with 64 output columns; one level of
+// upsampling, unit dilation, 2 .. 7 taps per axis, first tap at or before the pixel; an 8 x 16 tile grid with an interior (>= 3 x 3 tiles);
+// and every tap of every pixel of the interior tiles -- rows [8, 8 (tiles_y - 1)), columns [16, 16 (tiles_x - 1)) -- inside the logical
+// image [0, 2 Hi) x [0, 2 Wi): there the collapsed weights reproduce the layer, at the padding they cannot (logical -1 and -2 mirror to
+// source rows 0 and 1; zero padding zeroes half a group), so the ring keeps the border tiles.
+struct X6Up2 {
+    int rc, sc;
+    int64_t tiles_y, tiles_x, lds;
+};
+bool up2_x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t Ho, int64_t Wo, int64_t R, int64_t S, int64_t off_y0,
+                 int64_t off_x0, int64_t dil_y, int64_t dil_x, int64_t up_shift, int64_t reflect_pad, X6Up2& u) {
+    X6Window w;
+    if (!window_x6_plan(Hi, Wi, Cin, Cout, R, S, dil_y, dil_x, up_shift, w) || w.cols != 64) return false;
+    if (up_shift != 1 || dil_y != 1 || dil_x != 1 || R < 2 || S < 2 || R > 7 || S > 7 || off_y0 > 0 || off_x0 > 0) return false;
+    if (reflect_pad < 0 || reflect_pad > 1 || Ho <= 0 || Wo <= 0 || Hi >= (1ll << 29) || Wi >= (1ll << 29)) return false;
+    u.tiles_y = ceil_div(Ho, (int64_t)kWinTH);
+    u.tiles_x = ceil_div(Wo, (int64_t)kWinTW);
+    if (u.tiles_y < 3 || u.tiles_x < 3) return false;
+    if (kWinTH + off_y0 < 0 || kWinTH * (u.tiles_y - 1) - 1 + off_y0 + R - 1 > 2 * Hi - 1) return false;
+    if (kWinTW + off_x0 < 0 || kWinTW * (u.tiles_x - 1) - 1 + off_x0 + S - 1 > 2 * Wi - 1) return false;
+    u.rc = up2_taps(R, off_y0);
+    u.sc = up2_taps(S, off_x0);
+    const int64_t window = (int64_t)(kWinTH + u.rc - 1) * (kWinTW + u.sc - 1) * 3 * 64;
+    const int64_t stage = (int64_t)kWinTH * kWinTW * (64 + 4) * 4, ring = 2 * 3 * 64 * 64;
+    u.lds = ring + (window > stage ? window : stage);
+    return true;
+}
+
+int conv_up2_bf16x6(const ConvCall& c, const void* wgt_img_phases) {
+    DIGA_REQUIRE(c.in && c.wgt_img && wgt_img_phases && c.out && c.opts, DIGA_EINVAL, "conv_up2_bf16x6: null pointer");
+    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0 && c.Cout > 0, DIGA_EINVAL, "conv_up2_bf16x6: bad shape");
+    DIGA_REQUIRE(c.Cin > 0 && c.Cin % 32 == 0 && c.out_ld >= c.Cout, DIGA_EINVAL, "conv_up2_bf16x6: Cin must be a multiple of 32");
+    DIGA_REQUIRE(c.in_ld >= c.Cin && c.in_ld % 4 == 0 && c.in_ld < (1ll << 31) && c.out_ld < (1ll << 31), DIGA_EINVAL,
+                 "conv_up2_bf16x6: in_ld must be at least Cin and a multiple of 4");
+    DIGA_REQUIRE(aligned16(c.in) && aligned16(c.wgt_img) && aligned16(wgt_img_phases) && ((uintptr_t)c.out & 3u) == 0 &&
+                     ((uintptr_t)c.bias & 3u) == 0, DIGA_EALIGN, "conv_up2_bf16x6: alignment");
+    int rc = check_options(c.opts, "conv_up2_bf16x6");
+    if (rc) return rc;
+    const int up = c.opts->upsample_shift;
+    rc = check_tap_coordinates(c, "conv_up2_bf16x6", up);
+    if (rc) return rc;
+    X6Up2 u;
+    X6Window w;
+    DIGA_REQUIRE(up2_x6_plan(c.Hi, c.Wi, c.Cin, c.Cout, c.Ho, c.Wo, c.R, c.S, c.off_y0, c.off_x0, c.off_dy, c.off_dx, up, c.opts->reflect_pad, u) &&
+                     window_x6_plan(c.Hi, c.Wi, c.Cin, c.Cout, c.R, c.S, c.off_dy, c.off_dx, up, w),
+                 DIGA_EINVAL, "conv_up2_bf16x6: the collapsed form does not take this call (diga_conv_up2_bf16x6_plan)");
+    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv_up2_bf16x6: too many pixels");
+    if (c.opts->reflect_pad) {                                    // a mirror reaches at most the far border (nn.ReflectionPad2d's rule)
+        const int64_t Hl = c.Hi << up, Wl = c.Wi << up;
+        const int64_t y_hi = c.Ho - 1 + c.off_y0 + (c.R - 1) * c.off_dy, x_hi = c.Wo - 1 + c.off_x0 + (c.S - 1) * c.off_dx;
+        DIGA_REQUIRE(-c.off_y0 < Hl && -c.off_x0 < Wl && y_hi - (Hl - 1) < Hl && x_hi - (Wl - 1) < Wl, DIGA_EINVAL,
+                     "conv_up2_bf16x6: reflection padding must be smaller than the (upsampled) image");
+    }
+    const int64_t tiles_n = ceil_div(c.Cout, (int64_t)64);
+    // interior: one block per phase and 8 x 16 tile of the SOURCE pixels [4, 4 (tiles_y - 1)) x [8, 8 (tiles_x - 1)); ring: the border tiles
+    const int64_t grid_in = c.N * ((u.tiles_y - 1) / 2) * ((u.tiles_x - 1) / 2) * 4 * tiles_n;
+    const int64_t grid_ring = c.N * (u.tiles_x * u.tiles_y - (u.tiles_x - 2) * (u.tiles_y - 2)) * tiles_n;
+    DIGA_REQUIRE(grid_in < (1ll << 31) && grid_ring < (1ll << 31), DIGA_EINVAL, "conv_up2_bf16x6: too many tiles for one launch");
+    ConvArgs a;
+    rc = fill_conv_args(a, c, "conv_up2_bf16x6", "conv_up2_bf16x6");
+    if (rc) return rc;
+    a.tiles_n = (int)tiles_n;
+    ConvArgs in = a;                                             // the interior: R' x S' collapsed taps of the source image, the phases' images
+    in.R = u.rc;
+    in.S = u.sc;
+    in.wgt_img = static_cast<const unsigned char*>(wgt_img_phases);
+    hipStream_t st = (hipStream_t)c.stream;
+    ProfScope prof(conv_prof_tag(c), st, conv_flops(c));
+    launch_k(conv_up2_x6_kernel, (unsigned)grid_in, 256, (size_t)u.lds, st, in);
+    launch_k(conv_win_x6_kernel<64, true>, (unsigned)grid_ring, 256, (size_t)w.lds, st, a);
+    return launch_status("diga_conv_up2_bf16x6_f32in");
+}
+}  // namespace
+
+// Returns 1 and the collapsed tap counts R' x S' where the window form of a convolution on the 2x nearest upsampling of an Hi x Wi x Cin
+// image runs its interior tiles on phase-collapsed weights (diga_conv_up2_bf16x6_f32in); 0 (and nothing written) where it does not.
+extern "C" int diga_conv_up2_bf16x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t Ho, int64_t Wo, int64_t R, int64_t S,
+                                         int64_t off_y0, int64_t off_x0, int64_t dil_y, int64_t dil_x, int64_t upsample_shift,
+                                         int64_t reflect_pad, int* rc, int* sc) {
+    X6Up2 u;
+    if (!rc || !sc || !up2_x6_plan(Hi, Wi, Cin, Cout, Ho, Wo, R, S, off_y0, off_x0, dil_y, dil_x, upsample_shift, reflect_pad, u)) return 0;
+    *rc = u.rc;
+    *sc = u.sc;
+    return 1;
+}
+
+// w_krsc [K][R][S][C] -> wc [phase_y][phase_x][K][R'][S'][C] (fp32; R' x S' as diga_conv_up2_bf16x6_plan reports them for these taps
+// and offsets): each collapsed weight is the sum of its group of taps, taken in double in ascending (r, s) order and rounded once.
+extern "C" int diga_collapse_up2_weights(const float* w_krsc, float* wc, int64_t K, int64_t R, int64_t S, int64_t C, int64_t off_y0,
+                                         int64_t off_x0, void* stream) {
+    DIGA_REQUIRE(w_krsc && wc && K > 0 && C > 0 && R >= 2 && S >= 2 && R <= 7 && S <= 7 && off_y0 <= 0 && off_x0 <= 0 &&
+                     off_y0 > -(1ll << 30) && off_x0 > -(1ll << 30) && K * R * S * C < (1ll << 40), DIGA_EINVAL,
+                 "collapse_up2_weights: 2 <= R, S <= 7 taps, offsets <= 0");
+    DIGA_REQUIRE(aligned16(w_krsc) && aligned16(wc), DIGA_EALIGN, "collapse_up2_weights: pointers must be 16-byte aligned");
+    const int rc = up2_taps(R, off_y0), sc = up2_taps(S, off_x0);
+    const int64_t total = 4 * K * rc * sc * C;
+    int64_t blocks = ceil_div(total, (int64_t)256);
+    if (blocks > 8192) blocks = 8192;
+    ProfScope prof(DIGA_PROF_ELEMENTWISE, (hipStream_t)stream, (double)K * R * S * C * 4.0);
+    hipLaunchKernelGGL(collapse_up2_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w_krsc, wc, (int)K, (int)R, (int)S,
+                       (int)C, (int)off_y0, (int)off_x0, rc, sc, total);
+    return launch_status("diga_collapse_up2_weights");
+}
+
+// The window form of a convolution on the 2x nearest upsampling of `in` with the interior on phase-collapsed weights: stride 1, unit
+// dilation, taps at (off_y0 + r, off_x0 + q) of the logical image; opts non-null with upsample_shift = 1.  wgt_img: the layer's image
+// (the ring of border tiles); wgt_img_phases: diga_split_bf16x6_image of the four [K][R'][S'][C] tensors of diga_collapse_up2_weights,
+// consecutive (diga_split_bf16x6_image_bytes(Cout, R' * S', Cin) apart).  Two launches that write disjoint pixels.
+extern "C" int diga_conv_up2_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const void* wgt_img_phases, const float* bias,
+                                          float* out, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout,
+                                          int64_t out_ld, int64_t R, int64_t S, int64_t off_y0, int64_t off_x0,
+                                          const diga_conv_options_t* opts, int prof_tag, void* stream) {
+    const int64_t stride_y = 1, stride_x = 1, off_dy = 1, off_dx = 1;
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
+    c.opts = opts; c.prof_tag = prof_tag;
+    return conv_up2_bf16x6(c, wgt_img_phases);
 }
 
 namespace {

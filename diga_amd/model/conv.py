@@ -107,6 +107,18 @@ def _x6_window(hi, wi, cin, k, r, s, doff, shift):
                                                  ctypes.byref(cols)) == 1
 
 
+def _x6_up2(hi, wi, cin, k, ho, wo, r, s, off0, doff, opts):
+    """True when config.x6_up2 is in force (conv_math = 2 with x6_taps, x6_opts and x6_window; read per call) AND the library's rule
+    (diga_conv_up2_bf16x6_plan, the one place that decides) takes the call: a window-form forward of the 2x nearest upsampling of an
+    hi x wi x cin image whose interior tiles then run on phase-collapsed weights ("x6up2", diga_conv_up2_bf16x6_f32in).  Only _plan
+    asks, for a call it would otherwise answer "x6win" with options."""
+    if not (_x6_opts() and config.active().x6_up2):
+        return False
+    rc, sc = ctypes.c_int(0), ctypes.c_int(0)
+    return _lib.lib.diga_conv_up2_bf16x6_plan(hi, wi, cin, k, ho, wo, r, s, off0[0], off0[1], doff[0], doff[1], int(opts[1]),
+                                              int(opts[0]), ctypes.byref(rc), ctypes.byref(sc)) == 1
+
+
 def _x6_fit(kp, cp):
     """True when config.x6_wgrad_tile = "fit" is in force (conv_math = 2; both read per call) AND the library's tile rule
     (diga_wgrad_bf16x6_tile, the one place that decides) gives a layer with kp (padded) output and cp input channels something other
@@ -308,7 +320,8 @@ class _Path(NamedTuple):
     per call, from the call's geometry, the features it wants and the active configuration; everything else -- the launch, the
     statistics buffer DigaConv2d allocates, infer_kernel, winograd_stats_plan, what a forward saves for its backward -- reads it."""
     family: str                # "x6ls" (bf16x6, operands split by the loader waves) / "x6" (bf16x6 on triplets) / "x6rs" (multi-tap bf16x6) /
-    #                            "x6win" (multi-tap bf16x6 from an LDS window: config.x6_window) / "twin" / "bf16x3" /
+    #                            "x6win" (multi-tap bf16x6 from an LDS window: config.x6_window) / "x6up2" (... of a 2x upsampled input, the
+    #                            interior on phase-collapsed weights: config.x6_up2) / "twin" / "bf16x3" /
     #                            "winograd" / "winograd_reflect" (reflection padding folded into the input transform) / "f32"
     variant: str               # "" / "epi" (backward-data epilogue) / "opts" / "infer" / "keep" (Winograd forward that keeps V)
     math: int                  # the layer's arithmetic (_layer_math): the `math` argument the library is given
@@ -382,6 +395,9 @@ def _plan(n, hi, wi, cin, k, r, s, stride, off0, doff, ho, wo, tag=_TAG_FWD, sta
         if (tag == _TAG_FWD and stats is None and not epi and not infer and tuple(stride) == (1, 1)
                 and _x6_window(hi, wi, cin, k, r, s, doff, opts[1] if copt else 0)):
             # a stride-1 plain forward the window rule admits: the tile's input window split into LDS once (config.x6_window)
+            if copt and _x6_up2(hi, wi, cin, k, ho, wo, r, s, off0, doff, opts):
+                # ... of a 2x upsampled input: the interior tiles on phase-collapsed weights, the border ring as "x6win" (config.x6_up2)
+                return _Path("x6up2", variant, 2, "bf16x6/up2")
             return _Path("x6win", variant, 2, "bf16x6/window")
         return _Path("x6rs", variant, 2, "bf16x6/taps+bn" if infer else "bf16x6/taps")
     return _Path("f32", variant, 0, "f32+bn" if infer else "f32")
@@ -486,6 +502,7 @@ _ENTRY = {
     ("x6rs", ""): "diga_conv_taps_bf16x6_f32in", ("x6rs", "epi"): "diga_conv_taps_bf16x6_f32in_epi",
     ("x6rs", "infer"): "diga_infer_conv_taps_bf16x6_f32in", ("x6rs", "opts"): "diga_conv_taps_bf16x6_f32in_opts",
     ("x6win", ""): "diga_conv_window_bf16x6_f32in", ("x6win", "opts"): "diga_conv_window_bf16x6_f32in",
+    ("x6up2", "opts"): "diga_conv_up2_bf16x6_f32in",
     ("x6", ""): "diga_conv2d_nhwc_bf16x6", ("x6", "epi"): "diga_conv2d_nhwc_bf16x6_epi", ("x6", "infer"): "diga_infer_conv2d_nhwc_bf16x6",
     ("twin", ""): "diga_conv2d_nhwc_twin", ("twin", "epi"): "diga_conv2d_nhwc_twin_epi", ("twin", "opts"): "diga_conv2d_nhwc_twin_opts",
     ("bf16x3", ""): "diga_conv2d_nhwc_bf16x3", ("bf16x3", "epi"): "diga_conv2d_nhwc_bf16x3_epi",
@@ -501,12 +518,31 @@ _WINOGRAD_X6_INFER = "diga_infer_conv2d_winograd_bf16x6"
 _WINOGRAD_X6_OPTS = "diga_conv_winograd_bf16x6_opts"         # ("winograd_reflect", "opts") with x6w: the fp32 `_opts` form's argument list
 
 
-def _operands(path, x, w_krsc, twin_box):
+def _up2_phase_images(w_krsc, hi, wi, ho, wo, off0, opts):
+    """The four phase images of "x6up2": the collapsed weights [phi_y][phi_x][K][R'][S'][C] (diga_collapse_up2_weights; R' x S' is the
+    rule's answer) and diga_split_bf16x6_image of each, consecutive in one buffer."""
+    k, r, s, cin = w_krsc.shape
+    rc, sc = ctypes.c_int(0), ctypes.c_int(0)
+    if _lib.lib.diga_conv_up2_bf16x6_plan(hi, wi, cin, k, ho, wo, r, s, off0[0], off0[1], 1, 1, int(opts[1]), int(opts[0]),
+                                          ctypes.byref(rc), ctypes.byref(sc)) != 1:
+        raise RuntimeError("DigaConv2d: diga_conv_up2_bf16x6_plan does not take a call planned as 'x6up2'")
+    rs = rc.value * sc.value
+    wc = torch.empty((4, k, rc.value, sc.value, cin), dtype=torch.float32, device=w_krsc.device)
+    _lib.call("diga_collapse_up2_weights", _lib.ptr(w_krsc), _lib.ptr(wc), k, r, s, cin, off0[0], off0[1], _lib.stream())
+    size = _lib.lib.diga_split_bf16x6_image_bytes(k, rs, cin)
+    imgs = torch.empty(4 * size, dtype=torch.uint8, device=w_krsc.device)
+    for ph in range(4):
+        _lib.call("diga_split_bf16x6_image", _lib.ptr(wc[ph]), _lib.ptr(imgs[ph * size:]), k, rs, cin, _lib.stream())
+    return wc, imgs
+
+
+def _operands(path, x, w_krsc, twin_box, up2=None):
     """The operands of an implicit-GEMM call in the form its family reads -> (the leading arguments up to the weights, the tensors
-    behind them, the twin / triplet of x to hand back).  The weight image / split lives until the launch returns."""
+    behind them, the twin / triplet of x to hand back).  The weight image / split lives until the launch returns.  up2: (ho, wo, off0,
+    opts) of the call ("x6up2" alone reads them: its phase images depend on the first tap's offsets)."""
     n, hi, wi, cin = x.shape
     k, r, s, _ = w_krsc.shape
-    if path.family in ("x6ls", "x6rs", "x6win"):
+    if path.family in ("x6ls", "x6rs", "x6win", "x6up2"):
         # loader form: the activations are read as fp32 in place (contiguous or a channel slice) -- no triplet is built, returned or
         # looked for in the box
         split, ld = None, _nhwc_ld(x)
@@ -520,11 +556,14 @@ def _operands(path, x, w_krsc, twin_box):
             if twin_box is not None:
                 twin_box[0] = split
         act = [_lib.ptr(split)]
-    if path.family in ("x6ls", "x6rs", "x6win", "x6", "twin"):
+    if path.family in ("x6ls", "x6rs", "x6win", "x6up2", "x6", "twin"):
         size, fill = ((_lib.lib.diga_split_bf16_image_bytes, "diga_split_bf16_image") if path.family == "twin" else
                       (_lib.lib.diga_split_bf16x6_image_bytes, "diga_split_bf16x6_image"))
         img = torch.empty(size(k, r * s, cin), dtype=torch.uint8, device=x.device)
         _lib.call(fill, _lib.ptr(w_krsc), _lib.ptr(img), k, r * s, cin, _lib.stream())
+        if path.family == "x6up2":                     # the full image for the ring of border tiles + one image per output phase
+            wc, imgs = _up2_phase_images(w_krsc, hi, wi, *up2)
+            return act + [_lib.ptr(img), _lib.ptr(imgs)], (x, split, img, wc, imgs), split
         return act + [_lib.ptr(img)], (x, split, img), split
     if path.family == "bf16x3":
         nel = w_krsc.numel()
@@ -597,7 +636,12 @@ def _conv_launch(x, w_krsc, bias, out, stride, off0, doff, tag, stats=None, twin
     if path.family in ("winograd", "winograd_reflect"):
         _winograd_launch(path, x, w_krsc, bias, out, abs(doff[0]), 1 if doff[0] < 0 else 0, tag, stats, struct, keep_v)
         return None
-    lead, held, split = _operands(path, x, w_krsc, twin_box)         # (`held`, `inf_held`: alive until the kernel is enqueued)
+    lead, held, split = _operands(path, x, w_krsc, twin_box, (ho, wo, off0, opts))      # (`held`, `inf_held`: alive until the kernel is enqueued)
+    if path.family == "x6up2":
+        # stride 1, dilation 1 and the options (upsample_shift = 1) are the entry point's signature
+        _lib.call(_ENTRY[(path.family, path.variant)], *lead, _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin, ho, wo, k, out.stride(2), r, s,
+                  off0[0], off0[1], struct, tag, _lib.stream())
+        return split
     if path.family == "x6win":
         # stride 1 is the entry point's signature; the options are nullable (variant "": a plain zero-padded convolution)
         _lib.call(_ENTRY[(path.family, path.variant)], *lead, _lib.ptr(bias), _lib.ptr(out), n, hi, wi, cin, ho, wo, k, out.stride(2), r, s,

@@ -598,6 +598,36 @@ int diga_conv_window_bf16x6_f32in(const float* in, int64_t in_ld, const void* wg
                                   int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld, int64_t R,
                                   int64_t S, int64_t off_y0, int64_t off_x0, int64_t dil_y, int64_t dil_x,
                                   const diga_conv_options_t* opts /* nullable */, int prof_tag, void* stream);
+/* The window form of a 2x nearest-upsampled input on PHASE-COLLAPSED weights (opt-in: StepConfig.x6_up2 next to x6_taps, x6_opts and
+ * x6_window under conv_math = 2).  After nearest x2 upsampling output pixel (2 y + fy, 2 x + fx) reads, for tap r, source row
+ * y + a(fy, r) with a(f, r) = floor((f + off_y0 + r) / 2) (columns alike): away from the padding the layer is four stride-1
+ * convolutions of the SOURCE image, one per output phase (fy, fx), each with R' x S' taps that are sums of the layer's -- collapsed tap
+ * index a(f, r) - a(f, 0), R' = max over f of a(f, R - 1) - a(f, 0) + 1 (5 x 5 at pad 2: 3 x 3).  At the padding no collapsed weight
+ * reproduces the layer, so the 8 x 16 tiles of the window form are split: the INTERIOR tiles (1 <= by <= tiles_y - 2,
+ * 1 <= bx <= tiles_x - 2) run on the collapsed weights (conv_up2_x6_kernel), the ring of border tiles on the window walk with the
+ * layer's own image -- bit for bit what diga_conv_window_bf16x6_f32in gives those tiles.  An interior pixel is, bit for bit, the window
+ * form's result for its phase's collapsed weights on the source image.
+ *
+ * diga_conv_up2_bf16x6_plan: a pure query, the one statement of the rule.  Returns 1 and *rc = R', *sc = S' where the form takes the
+ *   call, 0 (nothing written) where it does not: whatever diga_conv_window_bf16x6_plan refuses or gives 16 columns (Cout <= 16),
+ *   upsample_shift != 1, a dilation other than 1, R or S outside 2 .. 7, off_y0 or off_x0 > 0, reflect_pad outside 0 / 1, fewer than
+ *   3 x 3 tiles, an interior tap outside the logical image [0, 2 Hi) x [0, 2 Wi), null pointers.
+ * diga_collapse_up2_weights: w_krsc [K][R][S][C] -> wc [fy][fx][K][R'][S'][C] fp32; each element the sum of its group taken in double in
+ *   ascending (r, s) order and rounded once; a phase with fewer taps keeps zeros in the rest.  DIGA_EINVAL for R, S outside 2 .. 7 or
+ *   positive offsets, DIGA_EALIGN for pointers off 16 bytes.
+ * diga_conv_up2_bf16x6_f32in: diga_conv_window_bf16x6_f32in's arguments at unit dilation with a non-null `opts` (upsample_shift = 1) and
+ *   wgt_img_phases = diga_split_bf16x6_image of the four [K][R'][S'][C] tensors, consecutive
+ *   (diga_split_bf16x6_image_bytes(Cout, R' * S', Cin) apart); wgt_img stays the layer's own image.  Two launches on the stream that
+ *   write disjoint pixels.  Refusals as diga_conv_window_bf16x6_f32in's, plus everything the rule refuses. */
+int diga_conv_up2_bf16x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t Ho, int64_t Wo, int64_t R, int64_t S,
+                              int64_t off_y0, int64_t off_x0, int64_t dil_y, int64_t dil_x, int64_t upsample_shift, int64_t reflect_pad,
+                              int* rc, int* sc);
+int diga_collapse_up2_weights(const float* w_krsc, float* wc, int64_t K, int64_t R, int64_t S, int64_t C, int64_t off_y0, int64_t off_x0,
+                              void* stream);
+int diga_conv_up2_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const void* wgt_img_phases, const float* bias,
+                               float* out, int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout,
+                               int64_t out_ld, int64_t R, int64_t S, int64_t off_y0, int64_t off_x0, const diga_conv_options_t* opts,
+                               int prof_tag, void* stream);
 /* ... and their weight gradient dw [Cout][R][S][Cin]: diga_conv2d_wgrad_bf16x6_f32in's arguments with 1 <= R * S <= 64, Cin % 32 == 0
  * and Cout % 8 == 0; one block group per tap, split-K by the bf16x6 plan with the taps counted among the tiles.  The workspace query
  * returns 0 for a shape the entry point rejects (DIGA_EINVAL); a workspace smaller than it asks for: DIGA_EWORKSPACE. */

@@ -6,12 +6,13 @@ no_grad) under three settings, in alternated rounds on one box:
     x6         conv_math 2, x6_split = "loader", x6_taps, x6_winograd            (x6_opts off: the 21 calls with options stay as in mode0)
     x6+opts    ... and x6_opts: those calls on the multi-tap bf16x6 kernels and on Winograd with bf16x6 products
     x6+win     ... and x6_window (--x6-window only): the stride-1 multi-tap layers the window rule admits on the window form
+    x6+up2     ... and x6_up2 (--x6-up2 only): the upsampled layers diga_conv_up2_bf16x6_plan admits on phase-collapsed weights
 
-    python tools/bench_translator.py [--rounds 3] [--reps 3] [--batch 8] [--size 768] [--layers] [--x6-window]
+    python tools/bench_translator.py [--rounds 3] [--reps 3] [--batch 8] [--size 768] [--layers] [--x6-window] [--x6-up2]
 
 Per setting: conv.path_log and the `_opts` entry points of one pass, then ms per pass of every round (device events around --reps
 passes), the median and the spread.  --layers adds the five distinct folded layer shapes one by one, x6 against x6+opts (and, with
---x6-window, against x6+win; every round's time is printed, so the settings can be compared pair by pair).  Needs the GPU."""
+--x6-window / --x6-up2, against x6+win / x6+up2; every round's time is printed, so the settings can be compared pair by pair).  Needs the GPU."""
 import argparse
 import os
 import statistics
@@ -71,9 +72,12 @@ def main():
     ap.add_argument("--size", type=int, default=768)
     ap.add_argument("--layers", action="store_true")
     ap.add_argument("--x6-window", action="store_true", help="add the setting x6+win: x6+opts with config.x6_window")
+    ap.add_argument("--x6-up2", action="store_true", help="add the setting x6+up2: x6+win with config.x6_up2")
     a = ap.parse_args()
     if a.x6_window:
         SETTINGS.append(("x6+win", dict(X6, x6_opts=True, x6_window=True)))
+    if a.x6_up2:
+        SETTINGS.append(("x6+up2", dict(X6, x6_opts=True, x6_window=True, x6_up2=True)))
     if not torch.cuda.is_available():
         sys.exit("bench_translator: needs the GPU")
     dev = "cuda"

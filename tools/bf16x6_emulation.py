@@ -49,6 +49,58 @@ def product_chain(a, b):
     return chain
 
 
+# ---- phase-collapsed weights of a convolution behind a 2x nearest upsampling (config.x6_up2; diga_collapse_up2_weights and
+# diga_conv_up2_bf16x6_plan restated; tests/test_bf16x6_up2_cpu.py, tests/test_gpu_conv_bf16x6_up2.py)
+def up2_rows(R, off0, phase):
+    """a(phase, r) = floor((phase + off0 + r) / 2) for r = 0 .. R - 1: the SOURCE row, relative to y, that tap r of output row
+    2 y + phase reads after nearest x2 upsampling (away from the padding)."""
+    return [(phase + off0 + r) // 2 for r in range(R)]
+
+
+def up2_taps(R, off0):
+    """R': the collapsed tap count of the wider phase."""
+    return max(a[-1] - a[0] + 1 for a in (up2_rows(R, off0, 0), up2_rows(R, off0, 1)))
+
+
+def collapse_up2(w_krsc, off_y0, off_x0):
+    """w [K, R, S, C] -> (wc [2, 2, K, R', S', C], first [2][2] = (a_y(fy, 0), a_x(fx, 0))): element (r', s') of phase (fy, fx) is the sum
+    of the taps (r, s) with a_y(fy, r) - a_y(fy, 0) == r' and a_x(fx, s) - a_x(fx, 0) == s', taken in float64 in ascending (r, s) order
+    and rounded to w's dtype once; a phase with fewer taps keeps zeros in the rest."""
+    K, R, S, C = w_krsc.shape
+    rc, sc = up2_taps(R, off_y0), up2_taps(S, off_x0)
+    wc = torch.zeros(2, 2, K, rc, sc, C, dtype=torch.float64)
+    first = [[None, None], [None, None]]
+    wd = w_krsc.double()
+    for fy in (0, 1):
+        ay = up2_rows(R, off_y0, fy)
+        for fx in (0, 1):
+            ax = up2_rows(S, off_x0, fx)
+            first[fy][fx] = (ay[0], ax[0])
+            for r in range(R):
+                for s in range(S):
+                    wc[fy, fx, :, ay[r] - ay[0], ax[s] - ax[0], :] += wd[:, r, s, :]
+    return wc.to(w_krsc.dtype), first
+
+
+def up2_rule(Hi, Wi, Cin, Cout, Ho, Wo, R, S, off_y0, off_x0, dil_y=1, dil_x=1, shift=1, reflect=1):
+    """diga_conv_up2_bf16x6_plan restated: (R', S') where the collapsed form takes the call, else None."""
+    TH, TW, LDS = 8, 16, 160 * 1024
+    if min(Hi, Wi, Cin, Cout, Ho, Wo) <= 0 or Cin % 32 != 0 or Cout <= 16:
+        return None
+    if shift != 1 or dil_y != 1 or dil_x != 1 or not (2 <= R <= 7 and 2 <= S <= 7) or off_y0 > 0 or off_x0 > 0 or reflect not in (0, 1):
+        return None
+    if 2 * 3 * 64 * 64 + max((TH + R - 1) * (TW + S - 1) * 192, TH * TW * 68 * 4) > LDS:     # the window rule (never binds at R, S <= 7)
+        return None
+    ty, tx = -(-Ho // TH), -(-Wo // TW)
+    if ty < 3 or tx < 3:
+        return None
+    if TH + off_y0 < 0 or TH * (ty - 1) - 1 + off_y0 + R - 1 > 2 * Hi - 1:
+        return None
+    if TW + off_x0 < 0 or TW * (tx - 1) - 1 + off_x0 + S - 1 > 2 * Wi - 1:
+        return None
+    return up2_taps(R, off_y0), up2_taps(S, off_x0)
+
+
 def operands(M, K, N, seed):
     torch.manual_seed(seed)
     a = torch.randn(M, K)
