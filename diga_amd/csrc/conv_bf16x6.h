@@ -53,6 +53,42 @@ __device__ __forceinline__ void split3x4(const float4 v, uint2& p0, uint2& p1, u
     p2.y = pack_bf16(s2, s3);
 }
 
+// 8 consecutive fp32 channels (two float4) -> the three 16-byte plane words q0, q1, q2 (8 bf16 each, channel order).  Every kernel
+// that makes planes -- the triplet pass, the weight images, the loader waves, the window fill -- makes them here: the same bits.
+__device__ __forceinline__ void split3x8(const float4 lo, const float4 hi, uint4& q0, uint4& q1, uint4& q2) {
+    uint2 a0, a1, a2, b0, b1, b2;
+    split3x4(lo, a0, a1, a2);
+    split3x4(hi, b0, b1, b2);
+    q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
+    q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
+    q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
+}
+
+// THE product chain of bf16x6: per 16 x 16 sub-tile j and 32-deep K-step, a1 b1, a0 b2, a2 b0, a0 b1, a1 b0 chained from a ZERO
+// accumulator (smallest first), a0 b0 into the running sum acc[j], then one fold add -- two roundings of the running sum per K-step.
+// This order IS the bits of bf16x6 (tools/bf16x6_emulation.py restates it on the host); the forward, window and weight-gradient
+// kernels differ in how the fragments reach the registers and in nothing here.  Each product runs over the NT column sub-tiles before
+// the next starts, so an MFMA never waits for the one before it.
+template <int NT>
+__device__ __forceinline__ void x6_products(const bf16x8_t& a0, const bf16x8_t& a1, const bf16x8_t& a2, const bf16x8_t (&b0)[NT],
+                                            const bf16x8_t (&b1)[NT], const bf16x8_t (&b2)[NT], f32x4 (&acc)[NT]) {
+    f32x4 t[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1[j], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2[j], t[j], 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0[j], t[j], 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1[j], t[j], 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0[j], t[j], 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0[j], acc[j], 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] += t[j];
+}
+
 // x [M][ld] fp32 (C channels) -> triplet [M][C/8][plane0 x 8 | plane1 x 8 | plane2 x 8]
 __global__ __launch_bounds__(256) void make_triplet_kernel(const float* __restrict__ x, int64_t ld, unsigned char* __restrict__ trip,
                                                            int64_t M, int C8) {
@@ -61,13 +97,8 @@ __global__ __launch_bounds__(256) void make_triplet_kernel(const float* __restri
         const int64_t m = i / C8;
         const int g = (int)(i - m * C8);
         const float* src = x + m * ld + g * 8;
-        uint2 a0, a1, a2, b0, b1, b2;
-        split3x4(*reinterpret_cast<const float4*>(src), a0, a1, a2);
-        split3x4(*reinterpret_cast<const float4*>(src + 4), b0, b1, b2);
         uint4* dst = reinterpret_cast<uint4*>(trip + i * 48);
-        dst[0] = make_uint4(a0.x, a0.y, b0.x, b0.y);
-        dst[1] = make_uint4(a1.x, a1.y, b1.x, b1.y);
-        dst[2] = make_uint4(a2.x, a2.y, b2.x, b2.y);
+        split3x8(*reinterpret_cast<const float4*>(src), *reinterpret_cast<const float4*>(src + 4), dst[0], dst[1], dst[2]);
     }
 }
 
@@ -85,14 +116,10 @@ __global__ __launch_bounds__(256) void split_image3_kernel(const float* __restri
         const int tap = ks / cchunks, cc = ks - tap * cchunks;
         const int n = min(tile * bn + r, K - 1);
         const float* src = w + ((int64_t)n * RS + tap) * C + cc * 32 + 8 * s;
-        uint2 a0, a1, a2, b0, b1, b2;
-        split3x4(*reinterpret_cast<const float4*>(src), a0, a1, a2);
-        split3x4(*reinterpret_cast<const float4*>(src + 4), b0, b1, b2);
         const int64_t plane = (int64_t)bn * 64;
         unsigned char* dst = img + tk * (3 * plane) + r * 64 + ((s ^ lds_swz(r)) << 4);
-        *reinterpret_cast<uint4*>(dst) = make_uint4(a0.x, a0.y, b0.x, b0.y);
-        *reinterpret_cast<uint4*>(dst + plane) = make_uint4(a1.x, a1.y, b1.x, b1.y);
-        *reinterpret_cast<uint4*>(dst + 2 * plane) = make_uint4(a2.x, a2.y, b2.x, b2.y);
+        split3x8(*reinterpret_cast<const float4*>(src), *reinterpret_cast<const float4*>(src + 4), *reinterpret_cast<uint4*>(dst),
+                 *reinterpret_cast<uint4*>(dst + plane), *reinterpret_cast<uint4*>(dst + 2 * plane));
     }
 }
 
@@ -111,14 +138,10 @@ __global__ __launch_bounds__(256) void split_image3_batched_kernel(const float* 
         const int ks = (int)(tk % ksteps), tile = (int)(tk / ksteps);
         const int n = min(tile * bn + r, K - 1);
         const float* src = w + (int64_t)n * C + ks * 32 + 8 * s;
-        uint2 a0, a1, a2, b0, b1, b2;
-        split3x4(*reinterpret_cast<const float4*>(src), a0, a1, a2);
-        split3x4(*reinterpret_cast<const float4*>(src + 4), b0, b1, b2);
         const int64_t plane = (int64_t)bn * 64;
         unsigned char* dst = img + tk * (3 * plane) + r * 64 + ((s ^ lds_swz(r)) << 4);
-        *reinterpret_cast<uint4*>(dst) = make_uint4(a0.x, a0.y, b0.x, b0.y);
-        *reinterpret_cast<uint4*>(dst + plane) = make_uint4(a1.x, a1.y, b1.x, b1.y);
-        *reinterpret_cast<uint4*>(dst + 2 * plane) = make_uint4(a2.x, a2.y, b2.x, b2.y);
+        split3x8(*reinterpret_cast<const float4*>(src), *reinterpret_cast<const float4*>(src + 4), *reinterpret_cast<uint4*>(dst),
+                 *reinterpret_cast<uint4*>(dst + plane), *reinterpret_cast<uint4*>(dst + 2 * plane));
     }
 }
 
@@ -134,9 +157,9 @@ __global__ __launch_bounds__(256) void split_image3_batched_kernel(const float* 
 //
 // LS ("loader split", the `_f32in` entry points): a.in is the fp32 tensor itself ([pixel][in_ld], a channel slice of a wider
 // NHWC buffer included).  The loader lanes keep their rows, their k-slot and their 16-byte LDS slot; per row a lane reads its 8
-// channels as two float4 (a wave instruction covers 16 rows x 128 contiguous bytes), runs split3x4 -- the pass form's function, so
-// the planes are the same bits -- and writes the three planes with ds_write_b128 where the DMA form lands them.  The LDS image is
-// byte-identical: MFMA waves, fold accumulator and drain_stage are shared.  Weights stay pre-split images staged by LDS-DMA.
+// channels as two float4 (a wave instruction covers 16 rows x 128 contiguous bytes), splits them (split3x8) and writes the three
+// planes with ds_write_b128 where the DMA form lands them.  The LDS image is byte-identical: MFMA waves, fold accumulator and
+// drain_stage are shared.  Weights stay pre-split images staged by LDS-DMA.
 // Schedule per K-step: loads of step k + 1 into registers + the weight DMA, vmcnt(0), split, ds_write, lgkmcnt(0), barrier (the
 // stage written was last read in step k - 1, behind the previous barrier).  No triplet pass and 4 instead of 6 B per element
 // through L2; the price is ~6 VALU instructions per element in the loader waves.
@@ -155,10 +178,12 @@ __global__ __launch_bounds__(256) void split_image3_batched_kernel(const float* 
 // split_image3_kernel's image (ks = tap * cchunks + cc), so an R x S layer runs the K-step sequence of the pointwise kernel on the
 // tap-major im2col rows [M][RS * Cin] of its input: same weight image bytes, same LDS bytes, same bits.  Taps that lie outside the
 // image for every row of the block's tile (live_taps: uniform over the block) are stepped over in the weight image: they would add
-// exact zeros.  The loader lanes keep rows, k-slot, swizzle, LDS slot and the issue / vmcnt(0) / split3x4 / ds_write_b128 /
-// lgkmcnt(0) / barrier schedule; per row they keep the image's first pixel and (y0, x0) = (ho * sy + oy0, wo * sx + ox0), per tap they
-// derive (y0 + r * ody, x0 + q * odx) and the pointer -- null outside the image: no load is issued, the planes written are zero.  The
-// MFMA waves learn the new K-step count and nothing else; drain_stage, the fold accumulator and the ring are untouched.
+// exact zeros.  It is the LS loader, written once: rows (x6_row), k-slot, swizzle, LDS slot, `issue`, `write` and the issue / vmcnt(0) /
+// split / ds_write_b128 / lgkmcnt(0) / barrier ring are the same text; the pointwise form points its rows once and walks the chunks of
+// its one tap, the tap walk derives (y0 + r * ody, x0 + q * odx) and the pointers per live tap (next_tap) -- null outside the image: no
+// load is issued, the planes written are zero -- and steps K-step -> (tap, chunk).  R = S = 1 through the tap walk is the pointwise
+// kernel's K-step sequence.  The MFMA waves learn the new K-step count and nothing else; drain_stage, the fold accumulator and the ring
+// are untouched.
 //
 // OPT (diga_conv_taps_bf16x6_f32in_opts; TAPS, plain variant only): the input map of diga_conv_options_t folded into the tap walk.  A
 // row's (y0, x0) are then coordinates in the LOGICAL image -- `in` upsampled by 2^up_shift, (Hi << up_shift) x (Wi << up_shift) -- and
@@ -166,6 +191,17 @@ __global__ __launch_bounds__(256) void split_image3_batched_kernel(const float* 
 // form an address outside the tensor), shifted back to the source pixel; pix0 stays the SOURCE image's first pixel.  A tap that reads
 // zero padding keeps the null pointer and the zero planes.  live_taps already counts in the logical extent and keeps every tap under
 // pad_reflect; drain_stage already applies tanh under a.act.  An instantiation of its own: the others keep their instruction streams.
+// Output row m of the tile (clamped to the last row) -> the first pixel of its image in `in` and the input coordinates of its tap (0, 0).
+__device__ __forceinline__ void x6_row(const ConvArgs& a, int m, int& pix0, int& y0, int& x0) {
+    m = min(m, a.M - 1);
+    const int HoWo = a.Ho * a.Wo;
+    const int img = m / HoWo, rem = m - img * HoWo;
+    const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
+    pix0 = img * a.Hi * a.Wi;
+    y0 = ho * a.sy + a.oy0;
+    x0 = wo * a.sx + a.ox0;
+}
+
 template <int TN, bool EPI = false, bool LS = false, bool WB = false, bool INF = false, bool TAPS = false, bool OPT = false>
 __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
     static_assert(!(INF && (EPI || WB)), "the inference epilogue comes with the plain pointwise forward");
@@ -187,30 +223,17 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
     }
     const int ksteps = ksteps_all;
 
-    if constexpr (TAPS) {
+    if constexpr (LS) {
       if (loader) {
         const int lw = wv - 8;                                   // 0..3: A rows lw*64 + 16 j + (lane >> 2)
         const int lrow = lane >> 2;
         const int kslot = (lane & 3) ^ lds_swz(lrow);
-        const int HoWo = a.Ho * a.Wo, cchunks = a.Cin / 32;
+        const int cchunks = a.Cin / 32;
         int pix0[4], y0[4], x0[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int m = min(m0 + lw * 64 + 16 * j + lrow, a.M - 1);
-            const int img = m / HoWo, rem = m - img * HoWo;
-            const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-            pix0[j] = img * a.Hi * a.Wi;
-            y0[j] = ho * a.sy + a.oy0;
-            x0[j] = wo * a.sx + a.ox0;
-        }
+        for (int j = 0; j < 4; ++j) x6_row(a, m0 + lw * 64 + 16 * j + lrow, pix0[j], y0[j], x0[j]);
         const float* pa[4];
-        uint64_t todo = live;
-        int l_tap = 0, l_cc = 0, issued = 0;
-        auto next_tap = [&]() {                                  // -> l_tap = the next live tap, pa = its pixels
-            l_tap = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const int r = l_tap / a.S, q = l_tap - r * a.S;
-            const int dy = r * a.ody, dx = q * a.odx;
+        auto point = [&](int dy, int dx) {                       // pa = the rows' pixels at tap offset (dy, dx); null outside the image
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int iy = y0[j] + dy, ix = x0[j] + dx;
@@ -224,7 +247,20 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
                 }
             }
         };
-        const unsigned char* bimg = a.wgt_img + (int64_t)tile_n * ((int64_t)a.R * a.S * cchunks) * (3 * B_PLANE) + (lw * 3 * TN) * 1024 + lane * 16;
+        // the K-step in flight is chunk l_cc of tap l_tap.  Pointwise: one tap, whose chunks are the K-steps (l_cc = ks)
+        [[maybe_unused]] uint64_t todo = live;
+        [[maybe_unused]] int l_tap = 0, issued = 0;
+        int l_cc = 0;
+        auto next_tap = [&]() {                                  // -> l_tap = the next live tap, pa = its pixels
+            l_tap = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int r = l_tap / a.S, q = l_tap - r * a.S;
+            point(r * a.ody, q * a.odx);
+        };
+        const unsigned char* wimg = a.wgt_img;                   // the column tile's image: every tap's K-steps, live or not
+        if constexpr (WB) wimg += (int64_t)(tile_m / a.wb_tiles) * a.wb_stride;
+        const int64_t img_steps = TAPS ? (int64_t)a.R * a.S * cchunks : ksteps;
+        const unsigned char* bimg = wimg + (int64_t)tile_n * img_steps * (3 * B_PLANE) + (lw * 3 * TN) * 1024 + lane * 16;
         float4 v[4][2];
         auto issue = [&](int buf) {                              // global loads of the next K-step into registers + its weight DMA
 #pragma unroll
@@ -234,7 +270,7 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
                     v[j][1] = *reinterpret_cast<const float4*>(pa[j] + l_cc * 32 + 4);
                 }
             }
-            const unsigned char* bsrc = bimg + (int64_t)(l_tap * cchunks + l_cc) * (3 * B_PLANE);
+            const unsigned char* bsrc = bimg + (int64_t)(TAPS ? l_tap * cchunks + l_cc : l_cc) * (3 * B_PLANE);
             unsigned char* bdst = smem_b + buf * STAGE + 3 * A_PLANE + (lw * 3 * TN) * 1024;
 #pragma unroll
             for (int c = 0; c < 3 * TN; ++c) DIGA_LDS_DMA16(bsrc + c * 1024, bdst + c * 1024);
@@ -244,27 +280,24 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // a pixel outside the image: zero planes
-                if (pa[j] != nullptr) {
-                    uint2 a0, a1, a2, b0, b1, b2;
-                    split3x4(v[j][0], a0, a1, a2);
-                    split3x4(v[j][1], b0, b1, b2);
-                    q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
-                    q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
-                    q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
-                }
+                if (pa[j] != nullptr) split3x8(v[j][0], v[j][1], q0, q1, q2);
                 unsigned char* dst = stage + (lw * 64 + 16 * j) * 64 + lane * 16;
                 *reinterpret_cast<uint4*>(dst) = q0;
                 *reinterpret_cast<uint4*>(dst + A_PLANE) = q1;
                 *reinterpret_cast<uint4*>(dst + 2 * A_PLANE) = q2;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            ++issued;
-            if (++l_cc == cchunks) {                             // (pa changes only here, behind the writes that read it)
-                l_cc = 0;
-                if (issued < ksteps) next_tap();
+            ++l_cc;
+            if constexpr (TAPS) {
+                ++issued;
+                if (l_cc == cchunks) {                           // (pa changes only here, behind the writes that read it)
+                    l_cc = 0;
+                    if (issued < ksteps) next_tap();
+                }
             }
         };
-        next_tap();
+        if constexpr (TAPS) next_tap();
+        else point(0, 0);
         issue(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         write(0);
@@ -279,89 +312,19 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
         }
         return;
       }
-    } else if constexpr (LS) {
-      if (loader) {
-        const int lw = wv - 8;                                   // 0..3: A rows lw*64 + 16 j + (lane >> 2)
-        const int lrow = lane >> 2;
-        const int kslot = (lane & 3) ^ lds_swz(lrow);
-        const int HoWo = a.Ho * a.Wo;
-        const float* pa[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int m = min(m0 + lw * 64 + 16 * j + lrow, a.M - 1);
-            const int img = m / HoWo, rem = m - img * HoWo;
-            const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-            const int iy = ho * a.sy + a.oy0, ix = wo * a.sx + a.ox0;
-            const bool ok = (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
-            pa[j] = ok ? a.in + ((int64_t)img * a.Hi * a.Wi + (int64_t)iy * a.Wi + ix) * a.in_ld + kslot * 8 : nullptr;
-        }
-        const unsigned char* wimg = a.wgt_img;
-        if constexpr (WB) wimg += (int64_t)(tile_m / a.wb_tiles) * a.wb_stride;
-        const unsigned char* bimg = wimg + (int64_t)tile_n * ksteps * (3 * B_PLANE) + (lw * 3 * TN) * 1024 + lane * 16;
-        float4 v[4][2];
-        auto issue = [&](int ks, int buf) {                      // global loads of step ks into registers + its weight DMA
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (pa[j] != nullptr) {
-                    v[j][0] = *reinterpret_cast<const float4*>(pa[j] + ks * 32);
-                    v[j][1] = *reinterpret_cast<const float4*>(pa[j] + ks * 32 + 4);
-                }
-            }
-            const unsigned char* bsrc = bimg + (int64_t)ks * (3 * B_PLANE);
-            unsigned char* bdst = smem_b + buf * STAGE + 3 * A_PLANE + (lw * 3 * TN) * 1024;
-#pragma unroll
-            for (int c = 0; c < 3 * TN; ++c) DIGA_LDS_DMA16(bsrc + c * 1024, bdst + c * 1024);
-        };
-        auto write = [&](int buf) {                              // split + three ds_write_b128 per row, then wait for them
-            unsigned char* stage = smem_b + buf * STAGE;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // a pixel outside the image: zero planes
-                if (pa[j] != nullptr) {
-                    uint2 a0, a1, a2, b0, b1, b2;
-                    split3x4(v[j][0], a0, a1, a2);
-                    split3x4(v[j][1], b0, b1, b2);
-                    q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
-                    q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
-                    q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
-                }
-                unsigned char* dst = stage + (lw * 64 + 16 * j) * 64 + lane * 16;
-                *reinterpret_cast<uint4*>(dst) = q0;
-                *reinterpret_cast<uint4*>(dst + A_PLANE) = q1;
-                *reinterpret_cast<uint4*>(dst + 2 * A_PLANE) = q2;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        };
-        issue(0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        write(0);
-        __builtin_amdgcn_s_barrier();                            // stage 0 has landed
-        for (int ks = 0; ks < ksteps; ++ks) {
-            if (ks + 1 < ksteps) {                               // (its stage was read by step ks - 1: behind the last barrier)
-                issue(ks + 1, (ks + 1) & 1);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                write((ks + 1) & 1);
-            }
-            __builtin_amdgcn_s_barrier();
-        }
-        return;
-      }
     } else if (loader) {
         const int lw = wv - 8;                                   // 0..3: A rows lw*64 + 16 j + (lane >> 2)
         const unsigned char* trip = reinterpret_cast<const unsigned char*>(a.in);
         const int lrow = lane >> 2;
         const int kslot = (lane & 3) ^ lds_swz(lrow);
         const int64_t rowb = (int64_t)a.Cin * 6;
-        const int HoWo = a.Ho * a.Wo;
         const unsigned char* pa[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int m = min(m0 + lw * 64 + 16 * j + lrow, a.M - 1);
-            const int img = m / HoWo, rem = m - img * HoWo;
-            const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-            const int iy = ho * a.sy + a.oy0, ix = wo * a.sx + a.ox0;
+            int pix0, iy, ix;
+            x6_row(a, m0 + lw * 64 + 16 * j + lrow, pix0, iy, ix);
             const bool ok = (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
-            pa[j] = ok ? trip + ((int64_t)img * a.Hi * a.Wi + (int64_t)iy * a.Wi + ix) * rowb + kslot * 48 : nullptr;
+            pa[j] = ok ? trip + ((int64_t)pix0 + (int64_t)iy * a.Wi + ix) * rowb + kslot * 48 : nullptr;
         }
         const unsigned char* bimg = a.wgt_img + (int64_t)tile_n * ksteps * (3 * B_PLANE) + (lw * 3 * TN) * 1024 + lane * 16;
         auto issue = [&](int ks, int buf) {
@@ -418,21 +381,7 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
             const bf16x8_t a0 = *reinterpret_cast<const bf16x8_t*>(A0 + i * 1024);
             const bf16x8_t a1 = *reinterpret_cast<const bf16x8_t*>(A0 + A_PLANE + i * 1024);
             const bf16x8_t a2 = *reinterpret_cast<const bf16x8_t*>(A0 + 2 * A_PLANE + i * 1024);
-            f32x4 t[NT];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1[j], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2[j], t[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0[j], t[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1[j], t[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) t[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0[j], t[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] += t[j];
+            x6_products<NT>(a0, a1, a2, b0, b1, b2, acc[i]);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -456,10 +405,9 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// backward-weight: conv_wgrad_x3t_kernel with a third plane, six products in the order above with the fold accumulator, and a
-// two-stage ring.  One BM (Cout) x BN (Cin) tile per pixel range, tap and split: four MFMA waves as 2 x 2 (wave tile BM/2 x BN/2 =
-// MT x NT sub-tiles of 16 x 16, MT = BM / 32, NT = BN / 32) + four loader waves; fragments through the transposing LDS reads; the
-// zero-started correction chain folded in with one `acc += tt` per 32-pixel K-step; the pixel clamp on dy; zero planes for x outside
+// backward-weight: conv_wgrad_x3t_kernel with a third plane, the product chain of x6_products and a two-stage ring.  One BM (Cout) x BN (Cin) tile per pixel range, tap and split: four MFMA waves as 2 x 2 (wave tile BM/2 x BN/2 =
+// MT x NT sub-tiles of 16 x 16, MT = BM / 32, NT = BN / 32) + four loader waves; fragments through the transposing LDS reads; one
+// x6_products per row of sub-tiles and 32-pixel K-step; the pixel clamp on dy; zero planes for x outside
 // the image or past the pixel range; the channel-chunk clamp (kmax / cmax) with masked stores; the tap walk over a.ptab + tap *
 // a.M_pad; the slab layout [split][Cout][RS][Cin].  Seven instantiations: 256 x 128 in the three forms below (238 of 256 VGPRs), and
 // the loader form on 64 x 64, 64 x 128, 128 x 128, 256 x 64 for the layers that fill an eighth to a half of 256 x 128 and would pay
@@ -470,7 +418,7 @@ __global__ __launch_bounds__(768, 3) void conv_fwd_x6_kernel(ConvArgs a) {
 // LS = false (the pass form, diga_conv2d_wgrad_bf16x6; 256 x 128 only): dy and x are triplet images, staged by LDS-DMA.
 //
 // LS (the `_f32in` entry points): dy and x are the fp32 tensors ([pixel][dy_ld] / [pixel][x_ld]); the loader lanes keep row,
-// destination chunk, source-side swizzle and clamps, read their chunk's 8 channels as two float4, split (split3x4) and write the
+// destination chunk, source-side swizzle and clamps, read their chunk's 8 channels as two float4, split (split3x8) and write the
 // three planes into the lane-linear LDS slots of the DMA form -- the same LDS bytes, so the same dw bits.
 // Loader split.  A plane is 32 pixel rows x CH / 8 chunks of 16 bytes (CH = BM or BN channels); the 256 loader lanes take
 // 64 * 8 / CH rows per wave instruction, CH / 32 instructions per wave (4 / 2 / 1 at 256 / 128 / 64 channels): instruction j of wave
@@ -577,25 +525,17 @@ __global__ __launch_bounds__(512, 2 * wgrad_x6_tile_blocks(BM, BN)) void conv_wg
             unsigned char* stage = smem_b + stg * STAGE;
 #pragma unroll
             for (int j = 0; j < A_NI; ++j) {
-                uint2 a0, a1, a2, b0, b1, b2;
-                split3x4(va[j][0], a0, a1, a2);
-                split3x4(va[j][1], b0, b1, b2);
+                uint4 q0, q1, q2;
+                split3x8(va[j][0], va[j][1], q0, q1, q2);
                 unsigned char* dst = stage + (8 * wv + A_RPI * j) * A_ROW + lane * 16;
-                *reinterpret_cast<uint4*>(dst) = make_uint4(a0.x, a0.y, b0.x, b0.y);
-                *reinterpret_cast<uint4*>(dst + A_PLANE) = make_uint4(a1.x, a1.y, b1.x, b1.y);
-                *reinterpret_cast<uint4*>(dst + 2 * A_PLANE) = make_uint4(a2.x, a2.y, b2.x, b2.y);
+                *reinterpret_cast<uint4*>(dst) = q0;
+                *reinterpret_cast<uint4*>(dst + A_PLANE) = q1;
+                *reinterpret_cast<uint4*>(dst + 2 * A_PLANE) = q2;
             }
 #pragma unroll
             for (int j = 0; j < B_NI; ++j) {
                 uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // outside the image / past the pixel range: zero planes
-                if (okb[j]) {
-                    uint2 a0, a1, a2, b0, b1, b2;
-                    split3x4(vb[j][0], a0, a1, a2);
-                    split3x4(vb[j][1], b0, b1, b2);
-                    q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
-                    q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
-                    q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
-                }
+                if (okb[j]) split3x8(vb[j][0], vb[j][1], q0, q1, q2);
                 unsigned char* dst = stage + 3 * A_PLANE + (8 * wv + B_RPI * j) * B_ROW + lane * 16;
                 *reinterpret_cast<uint4*>(dst) = q0;
                 *reinterpret_cast<uint4*>(dst + B_PLANE) = q1;
@@ -693,21 +633,7 @@ __global__ __launch_bounds__(512, 2 * wgrad_x6_tile_blocks(BM, BN)) void conv_wg
             const bf16x8_t a0 = tr_frag(Ap + a_off(i, row0), Ap + a_off(i, row1));
             const bf16x8_t a1 = tr_frag(Ap + A_PLANE + a_off(i, row0), Ap + A_PLANE + a_off(i, row1));
             const bf16x8_t a2 = tr_frag(Ap + 2 * A_PLANE + a_off(i, row0), Ap + 2 * A_PLANE + a_off(i, row1));
-            f32x4 tt[NT];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1[j], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] += tt[j];
+            x6_products<NT>(a0, a1, a2, b0, b1, b2, acc[i]);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -740,7 +666,7 @@ __global__ __launch_bounds__(512, 2 * wgrad_x6_tile_blocks(BM, BN)) void conv_wg
 // repeat a source pixel and are stored once each, as logical pixels).  A pixel of the zero padding issues no load and gets zero planes.
 // Per pixel and plane 64 bytes (32 channels), four 16-byte k-slots, slot s at s ^ lds_swz(wp); the three planes lie WH * WW * 64 bytes
 // apart.  All four waves fill it: an item is (pixel, k-slot), read as two float4 at in_ld (a wave instruction covers 16 pixels x 128
-// bytes), split3x4 -- the loader form's function, so the same planes -- and three ds_write_b128; four items are in flight per thread.
+// bytes), split3x8 and three ds_write_b128; four items are in flight per thread.
 //
 // K-steps.  One per (32-channel chunk, tap), CHUNK-major: one chunk's window is resident at a time, so the window costs
 // WH * WW * 192 bytes whatever Cin is (7 x 7: 14 x 22 pixels = 57.8 KB; 5 x 5: 12 x 20 = 45 KB).  At Cin = 32 chunk-major and tap-major are
@@ -762,8 +688,7 @@ __global__ __launch_bounds__(512, 2 * wgrad_x6_tile_blocks(BM, BN)) void conv_wg
 // rows 0 .. 15 of each plane only, 1 KB per plane and K-step; rows past Cout repeat the last channel and are never stored.  Cout > 64
 // runs ceil(Cout / 64) column tiles, each of which loads and splits the window again.
 //
-// Products and drain.  a1 b1, a0 b2, a2 b0, a0 b1, a1 b0 chained from zero, a0 b0 into the running sum, one fold add per K-step.  Plain
-// drain only: the 128 x NC tile is staged over the (dead) window, then + bias, tanhf under a.act (drain_stage's expressions) and stores
+// Products and drain.  x6_products per row of sub-tiles and K-step.  Plain drain only: the 128 x NC tile is staged over the (dead) window, then + bias, tanhf under a.act (drain_stage's expressions) and stores
 // at out_ld masked by column and by the tile's ragged right / bottom edge.  No statistics, no epilogues.
 //
 // Residency.  LDS = ring (2 x 3 x NC x 64) + max(window, 128 x (NC + 4) x 4): 7 x 7 narrow 63.8 KB, 5 x 5 wide 69 KB -- two blocks of four
@@ -880,14 +805,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_x6_kernel(ConvArgs a) {
                 const int idx = base + u * 256 + t;
                 if (idx < items) {
                     uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;     // zero padding: zero planes
-                    if (ok[u]) {
-                        uint2 a0, a1, a2, b0, b1, b2;
-                        split3x4(v[u][0], a0, a1, a2);
-                        split3x4(v[u][1], b0, b1, b2);
-                        q0 = make_uint4(a0.x, a0.y, b0.x, b0.y);
-                        q1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
-                        q2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
-                    }
+                    if (ok[u]) split3x8(v[u][0], v[u][1], q0, q1, q2);
                     const int wp = idx >> 2;
                     unsigned char* dst = win + wp * 64 + (((idx & 3) ^ lds_swz(wp)) << 4);
                     *reinterpret_cast<uint4*>(dst) = q0;
@@ -940,21 +858,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_x6_kernel(ConvArgs a) {
             const bf16x8_t a0 = *reinterpret_cast<const bf16x8_t*>(A0);
             const bf16x8_t a1 = *reinterpret_cast<const bf16x8_t*>(A0 + WPLANE);
             const bf16x8_t a2 = *reinterpret_cast<const bf16x8_t*>(A0 + 2 * WPLANE);
-            f32x4 tt[NT];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1[j], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) tt[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0[j], tt[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] += tt[j];
+            x6_products<NT>(a0, a1, a2, b0, b1, b2, acc[i]);
         }
         if (++q == a.S) {
             q = 0;
@@ -1273,8 +1177,16 @@ extern "C" int diga_conv_taps_bf16x6_f32in_opts(const float* in, int64_t in_ld, 
     return conv2d_bf16x6(c);
 }
 
-// ---- the window form of the multi-tap forward (conv_win_x6_kernel)
+// ---- the window forms of the multi-tap forward (conv_win_x6_kernel): every tile from the layer's weights (diga_conv_window_bf16x6_f32in), or
+// the interior of a 2x nearest-upsampled input on phase-collapsed weights inside a ring of border tiles (diga_conv_up2_bf16x6_f32in)
 namespace {
+// The LDS of a block whose window is wh x ww pixels of one 32-channel chunk: the weight ring + the larger of the window's three planes
+// and the drain's staging of the 8 x 16 x cols tile.
+inline int64_t x6_window_lds(int64_t wh, int64_t ww, int64_t cols) {
+    const int64_t window = wh * ww * 3 * 64, stage = (int64_t)kWinTH * kWinTW * (cols + 4) * 4, ring = 2 * 3 * cols * 64;
+    return ring + (window > stage ? window : stage);
+}
+
 // THE window rule (diga_conv_window_bf16x6_plan answers it; the entry point, its LDS size and the Python planner read nothing else):
 // which calls the window form takes, on which tile and with how many output columns per block.  Stride 1 in the logical image is the
 // entry point's signature.  The tile is 8 x 16 for every class; 16 columns serve Cout <= 16, 64 columns everything else; the window of
@@ -1291,80 +1203,10 @@ bool window_x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t R
     w.th = kWinTH;
     w.tw = kWinTW;
     w.cols = Cout <= 16 ? 16 : 64;
-    const int64_t window = (kWinTH + (R - 1) * dil_y) * (kWinTW + (S - 1) * dil_x) * 3 * 64;
-    const int64_t stage = (int64_t)kWinTH * kWinTW * (w.cols + 4) * 4, ring = 2 * 3 * w.cols * 64;
-    w.lds = ring + (window > stage ? window : stage);
+    w.lds = x6_window_lds(kWinTH + (R - 1) * dil_y, kWinTW + (S - 1) * dil_x, w.cols);
     return w.lds <= 160 * 1024;
 }
 
-int conv_window_bf16x6(const ConvCall& c) {
-    DIGA_REQUIRE(c.in && c.wgt_img && c.out, DIGA_EINVAL, "conv_window_bf16x6: null pointer");
-    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0 && c.Cout > 0, DIGA_EINVAL, "conv_window_bf16x6: bad shape");
-    DIGA_REQUIRE(c.R >= 1 && c.S >= 1 && c.R <= 64 && c.S <= 64 && c.R * c.S >= 2 && c.R * c.S <= 64, DIGA_EINVAL,
-                 "conv_window_bf16x6: 2 <= R * S <= 64 taps");
-    DIGA_REQUIRE(c.Cin > 0 && c.Cin % 32 == 0 && c.out_ld >= c.Cout, DIGA_EINVAL, "conv_window_bf16x6: Cin must be a multiple of 32");
-    DIGA_REQUIRE(c.in_ld >= c.Cin && c.in_ld % 4 == 0 && c.in_ld < (1ll << 31) && c.out_ld < (1ll << 31), DIGA_EINVAL,
-                 "conv_window_bf16x6: in_ld must be at least Cin and a multiple of 4");
-    DIGA_REQUIRE(aligned16(c.in) && aligned16(c.wgt_img) && ((uintptr_t)c.out & 3u) == 0 && ((uintptr_t)c.bias & 3u) == 0, DIGA_EALIGN,
-                 "conv_window_bf16x6: alignment");
-    int rc = check_options(c.opts, "conv_window_bf16x6");
-    if (rc) return rc;
-    const int up = c.opts ? c.opts->upsample_shift : 0;
-    rc = check_tap_coordinates(c, "conv_window_bf16x6", up);
-    if (rc) return rc;
-    X6Window w;
-    DIGA_REQUIRE(window_x6_plan(c.Hi, c.Wi, c.Cin, c.Cout, c.R, c.S, c.off_dy, c.off_dx, up, w), DIGA_EINVAL,
-                 "conv_window_bf16x6: the window form does not take this call (diga_conv_window_bf16x6_plan)");
-    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv_window_bf16x6: too many pixels");
-    if (c.opts && c.opts->reflect_pad) {                          // a mirror reaches at most the far border (nn.ReflectionPad2d's rule)
-        const int64_t Hl = c.Hi << up, Wl = c.Wi << up;
-        const int64_t y_hi = c.Ho - 1 + c.off_y0 + (c.R - 1) * c.off_dy, x_hi = c.Wo - 1 + c.off_x0 + (c.S - 1) * c.off_dx;
-        DIGA_REQUIRE(-c.off_y0 < Hl && -c.off_x0 < Wl && y_hi - (Hl - 1) < Hl && x_hi - (Wl - 1) < Wl, DIGA_EINVAL,
-                     "conv_window_bf16x6: reflection padding must be smaller than the (upsampled) image");
-    }
-    const int64_t tiles_n = ceil_div(c.Cout, w.cols);
-    const int64_t grid = c.N * ceil_div(c.Ho, w.th) * ceil_div(c.Wo, w.tw) * tiles_n;
-    DIGA_REQUIRE(grid < (1ll << 31), DIGA_EINVAL, "conv_window_bf16x6: too many tiles for one launch");
-    ConvArgs a;
-    rc = fill_conv_args(a, c, "conv_window_bf16x6", "conv_window_bf16x6");
-    if (rc) return rc;
-    a.tiles_n = (int)tiles_n;
-    hipStream_t st = (hipStream_t)c.stream;
-    ProfScope prof(conv_prof_tag(c), st, conv_flops(c));
-    launch_k(w.cols == 16 ? conv_win_x6_kernel<16> : conv_win_x6_kernel<64>, (unsigned)grid, 256, (size_t)w.lds, st, a);
-    return launch_status("diga_conv_window_bf16x6_f32in");
-}
-}  // namespace
-
-// Returns 1 and the tile (th x tw output pixels, th * tw % 128 == 0) and the output columns per block (16 for Cout <= 16, else 64) where
-// the window form takes a stride-1 convolution of R x S taps at dilation (dil_y, dil_x) on the 2^upsample_shift upsampling of an
-// Hi x Wi x Cin image; 0 (and nothing written) where it does not.
-extern "C" int diga_conv_window_bf16x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t R, int64_t S, int64_t dil_y,
-                                            int64_t dil_x, int64_t upsample_shift, int* th, int* tw, int* cols) {
-    X6Window w;
-    if (!th || !tw || !cols || !window_x6_plan(Hi, Wi, Cin, Cout, R, S, dil_y, dil_x, upsample_shift, w)) return 0;
-    *th = w.th;
-    *tw = w.tw;
-    *cols = w.cols;
-    return 1;
-}
-
-// The multi-tap forward on the window form: stride 1, taps at (off_y0 + r * dil_y, off_x0 + q * dil_x) of the logical image; `opts`
-// (nullable) as in diga_conv_taps_bf16x6_f32in_opts.  Plain forward: bias, optional tanh, no statistics, no epilogue.
-extern "C" int diga_conv_window_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N,
-                                             int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
-                                             int64_t R, int64_t S, int64_t off_y0, int64_t off_x0, int64_t dil_y, int64_t dil_x,
-                                             const diga_conv_options_t* opts, int prof_tag, void* stream) {
-    const int64_t stride_y = 1, stride_x = 1, off_dy = dil_y, off_dx = dil_x;
-    ConvCall c;
-    DIGA_FILL_GEOMETRY(c);
-    c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
-    c.opts = opts; c.prof_tag = prof_tag;
-    return conv_window_bf16x6(c);
-}
-
-// ---- the window form of a 2x nearest-upsampled input on phase-collapsed weights (conv_up2_x6_kernel + the ring of conv_win_x6_kernel)
-namespace {
 inline int64_t up2_a(int64_t phase, int64_t off0, int64_t r) {        // floor((phase + off0 + r) / 2): the source row of tap r
     const int64_t v = phase + off0 + r;
     return v >= 0 ? v / 2 : -((-v + 1) / 2);
@@ -1398,37 +1240,70 @@ bool up2_x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t Ho, 
     if (kWinTW + off_x0 < 0 || kWinTW * (u.tiles_x - 1) - 1 + off_x0 + S - 1 > 2 * Wi - 1) return false;
     u.rc = up2_taps(R, off_y0);
     u.sc = up2_taps(S, off_x0);
-    const int64_t window = (int64_t)(kWinTH + u.rc - 1) * (kWinTW + u.sc - 1) * 3 * 64;
-    const int64_t stage = (int64_t)kWinTH * kWinTW * (64 + 4) * 4, ring = 2 * 3 * 64 * 64;
-    u.lds = ring + (window > stage ? window : stage);
+    u.lds = x6_window_lds(kWinTH + u.rc - 1, kWinTW + u.sc - 1, 64);
     return true;
 }
 
-int conv_up2_bf16x6(const ConvCall& c, const void* wgt_img_phases) {
-    DIGA_REQUIRE(c.in && c.wgt_img && wgt_img_phases && c.out && c.opts, DIGA_EINVAL, "conv_up2_bf16x6: null pointer");
-    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0 && c.Cout > 0, DIGA_EINVAL, "conv_up2_bf16x6: bad shape");
-    DIGA_REQUIRE(c.Cin > 0 && c.Cin % 32 == 0 && c.out_ld >= c.Cout, DIGA_EINVAL, "conv_up2_bf16x6: Cin must be a multiple of 32");
+// The argument rules of the two entry points, in the order they answer, each under the entry point's own name.  u == nullptr:
+// diga_conv_window_bf16x6_f32in.  u != nullptr: diga_conv_up2_bf16x6_f32in -- the phases' images and the options are operands of their
+// own, the tap count is the collapsed rule's to judge, and that rule (which holds the window rule) decides whether the call is taken.
+// On success w (and *u) hold the plans.
+struct X6WindowNames {
+    const char *who, *form, *plan;
+};
+const X6WindowNames kX6WindowNames[2] = {{"conv_window_bf16x6", "window", "diga_conv_window_bf16x6_plan"},
+                                         {"conv_up2_bf16x6", "collapsed", "diga_conv_up2_bf16x6_plan"}};
+int check_window_call(const ConvCall& c, const void* wgt_img_phases, X6Window& w, X6Up2* u) {
+    const X6WindowNames& n = kX6WindowNames[u != nullptr];
+    DIGA_REQUIRE(c.in && c.wgt_img && c.out && (!u || (wgt_img_phases && c.opts)), DIGA_EINVAL, "%s: null pointer", n.who);
+    DIGA_REQUIRE(c.N > 0 && c.Hi > 0 && c.Wi > 0 && c.Ho > 0 && c.Wo > 0 && c.Cout > 0, DIGA_EINVAL, "%s: bad shape", n.who);
+    DIGA_REQUIRE(u || (c.R >= 1 && c.S >= 1 && c.R <= 64 && c.S <= 64 && c.R * c.S >= 2 && c.R * c.S <= 64), DIGA_EINVAL,
+                 "%s: 2 <= R * S <= 64 taps", n.who);
+    DIGA_REQUIRE(c.Cin > 0 && c.Cin % 32 == 0 && c.out_ld >= c.Cout, DIGA_EINVAL, "%s: Cin must be a multiple of 32", n.who);
     DIGA_REQUIRE(c.in_ld >= c.Cin && c.in_ld % 4 == 0 && c.in_ld < (1ll << 31) && c.out_ld < (1ll << 31), DIGA_EINVAL,
-                 "conv_up2_bf16x6: in_ld must be at least Cin and a multiple of 4");
+                 "%s: in_ld must be at least Cin and a multiple of 4", n.who);
     DIGA_REQUIRE(aligned16(c.in) && aligned16(c.wgt_img) && aligned16(wgt_img_phases) && ((uintptr_t)c.out & 3u) == 0 &&
-                     ((uintptr_t)c.bias & 3u) == 0, DIGA_EALIGN, "conv_up2_bf16x6: alignment");
-    int rc = check_options(c.opts, "conv_up2_bf16x6");
+                     ((uintptr_t)c.bias & 3u) == 0, DIGA_EALIGN, "%s: alignment", n.who);
+    int rc = check_options(c.opts, n.who);
     if (rc) return rc;
-    const int up = c.opts->upsample_shift;
-    rc = check_tap_coordinates(c, "conv_up2_bf16x6", up);
+    const int up = c.opts ? c.opts->upsample_shift : 0;
+    rc = check_tap_coordinates(c, n.who, up);
     if (rc) return rc;
-    X6Up2 u;
-    X6Window w;
-    DIGA_REQUIRE(up2_x6_plan(c.Hi, c.Wi, c.Cin, c.Cout, c.Ho, c.Wo, c.R, c.S, c.off_y0, c.off_x0, c.off_dy, c.off_dx, up, c.opts->reflect_pad, u) &&
-                     window_x6_plan(c.Hi, c.Wi, c.Cin, c.Cout, c.R, c.S, c.off_dy, c.off_dx, up, w),
-                 DIGA_EINVAL, "conv_up2_bf16x6: the collapsed form does not take this call (diga_conv_up2_bf16x6_plan)");
-    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "conv_up2_bf16x6: too many pixels");
-    if (c.opts->reflect_pad) {                                    // a mirror reaches at most the far border (nn.ReflectionPad2d's rule)
+    DIGA_REQUIRE(window_x6_plan(c.Hi, c.Wi, c.Cin, c.Cout, c.R, c.S, c.off_dy, c.off_dx, up, w) &&
+                     (!u || up2_x6_plan(c.Hi, c.Wi, c.Cin, c.Cout, c.Ho, c.Wo, c.R, c.S, c.off_y0, c.off_x0, c.off_dy, c.off_dx, up, c.opts->reflect_pad, *u)),
+                 DIGA_EINVAL, "%s: the %s form does not take this call (%s)", n.who, n.form, n.plan);
+    DIGA_REQUIRE(c.N * c.Hi * c.Wi < (1ll << 31) && c.N * c.Ho * c.Wo < (1ll << 31), DIGA_EINVAL, "%s: too many pixels", n.who);
+    if (c.opts && c.opts->reflect_pad) {                          // a mirror reaches at most the far border (nn.ReflectionPad2d's rule)
         const int64_t Hl = c.Hi << up, Wl = c.Wi << up;
         const int64_t y_hi = c.Ho - 1 + c.off_y0 + (c.R - 1) * c.off_dy, x_hi = c.Wo - 1 + c.off_x0 + (c.S - 1) * c.off_dx;
         DIGA_REQUIRE(-c.off_y0 < Hl && -c.off_x0 < Wl && y_hi - (Hl - 1) < Hl && x_hi - (Wl - 1) < Wl, DIGA_EINVAL,
-                     "conv_up2_bf16x6: reflection padding must be smaller than the (upsampled) image");
+                     "%s: reflection padding must be smaller than the (upsampled) image", n.who);
     }
+    return DIGA_OK;
+}
+
+int conv_window_bf16x6(const ConvCall& c) {
+    X6Window w;
+    int rc = check_window_call(c, nullptr, w, nullptr);
+    if (rc) return rc;
+    const int64_t tiles_n = ceil_div(c.Cout, w.cols);
+    const int64_t grid = c.N * ceil_div(c.Ho, w.th) * ceil_div(c.Wo, w.tw) * tiles_n;
+    DIGA_REQUIRE(grid < (1ll << 31), DIGA_EINVAL, "conv_window_bf16x6: too many tiles for one launch");
+    ConvArgs a;
+    rc = fill_conv_args(a, c, "conv_window_bf16x6", "conv_window_bf16x6");
+    if (rc) return rc;
+    a.tiles_n = (int)tiles_n;
+    hipStream_t st = (hipStream_t)c.stream;
+    ProfScope prof(conv_prof_tag(c), st, conv_flops(c));
+    launch_k(w.cols == 16 ? conv_win_x6_kernel<16> : conv_win_x6_kernel<64>, (unsigned)grid, 256, (size_t)w.lds, st, a);
+    return launch_status("diga_conv_window_bf16x6_f32in");
+}
+
+int conv_up2_bf16x6(const ConvCall& c, const void* wgt_img_phases) {
+    X6Window w;
+    X6Up2 u;
+    int rc = check_window_call(c, wgt_img_phases, w, &u);
+    if (rc) return rc;
     const int64_t tiles_n = ceil_div(c.Cout, (int64_t)64);
     // interior: one block per phase and 8 x 16 tile of the SOURCE pixels [4, 4 (tiles_y - 1)) x [8, 8 (tiles_x - 1)); ring: the border tiles
     const int64_t grid_in = c.N * ((u.tiles_y - 1) / 2) * ((u.tiles_x - 1) / 2) * 4 * tiles_n;
@@ -1449,6 +1324,33 @@ int conv_up2_bf16x6(const ConvCall& c, const void* wgt_img_phases) {
     return launch_status("diga_conv_up2_bf16x6_f32in");
 }
 }  // namespace
+
+// Returns 1 and the tile (th x tw output pixels, th * tw % 128 == 0) and the output columns per block (16 for Cout <= 16, else 64) where
+// the window form takes a stride-1 convolution of R x S taps at dilation (dil_y, dil_x) on the 2^upsample_shift upsampling of an
+// Hi x Wi x Cin image; 0 (and nothing written) where it does not.
+extern "C" int diga_conv_window_bf16x6_plan(int64_t Hi, int64_t Wi, int64_t Cin, int64_t Cout, int64_t R, int64_t S, int64_t dil_y,
+                                            int64_t dil_x, int64_t upsample_shift, int* th, int* tw, int* cols) {
+    X6Window w;
+    if (!th || !tw || !cols || !window_x6_plan(Hi, Wi, Cin, Cout, R, S, dil_y, dil_x, upsample_shift, w)) return 0;
+    *th = w.th;
+    *tw = w.tw;
+    *cols = w.cols;
+    return 1;
+}
+
+// The multi-tap forward on the window form: stride 1, taps at (off_y0 + r * dil_y, off_x0 + q * dil_x) of the logical image; `opts`
+// (nullable) as in diga_conv_taps_bf16x6_f32in_opts.  Plain forward: bias, optional tanh, no statistics, no epilogue.
+extern "C" int diga_conv_window_bf16x6_f32in(const float* in, int64_t in_ld, const void* wgt_img, const float* bias, float* out, int64_t N,
+                                             int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t out_ld,
+                                             int64_t R, int64_t S, int64_t off_y0, int64_t off_x0, int64_t dil_y, int64_t dil_x,
+                                             const diga_conv_options_t* opts, int prof_tag, void* stream) {
+    const int64_t stride_y = 1, stride_x = 1, off_dy = dil_y, off_dx = dil_x;
+    ConvCall c;
+    DIGA_FILL_GEOMETRY(c);
+    c.in = in; c.in_ld = in_ld; c.f32in = c.taps = true; c.wgt_img = wgt_img; c.bias = bias; c.out = out; c.out_ld = out_ld;
+    c.opts = opts; c.prof_tag = prof_tag;
+    return conv_window_bf16x6(c);
+}
 
 // Returns 1 and the collapsed tap counts R' x S' where the window form of a convolution on the 2x nearest upsampling of an Hi x Wi x Cin
 // image runs its interior tiles on phase-collapsed weights (diga_conv_up2_bf16x6_f32in); 0 (and nothing written) where it does not.

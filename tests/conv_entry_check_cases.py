@@ -7,7 +7,7 @@ EWORKSPACE) before anything is launched; the fixture keeps (return code, message
 shapes.  Only `_lib.SIGNATURES`, `_lib.lib` and the descriptor structures are used, so the same file records from any revision:
 
     DIGA_LIB=<library of the revision to record> python tests/conv_entry_check_cases.py --record [--relist-valid]
-    DIGA_LIB=<...> python tests/conv_entry_check_cases.py --merge <name prefix>       (adds entry points, keeps every recorded entry)
+    DIGA_LIB=<...> python tests/conv_entry_check_cases.py --merge <name prefix> ...   (adds entry points, keeps every recorded entry)
 """
 import ctypes
 import itertools
@@ -28,6 +28,7 @@ G17 = "n hi wi cin in_ld ho wo cout out_ld r s sy sx oy ox dy dx"
 G16 = "n hi wi cin ho wo cout out_ld r s sy sx oy ox dy dx"
 W17 = "n hi wi cin x_ld ho wo cout dy_ld r s sy sx oy ox dy dx"
 W15 = "n hi wi cin ho wo cout r s sy sx oy ox dy dx"
+GW = "n hi wi cin ho wo cout out_ld r s oy ox"          # the window forms: stride 1
 WF = "n h w cin in_ld cout out_ld dil tile"
 WB = "n h w cin x_ld cout dy_ld dil tile"
 SPECS = {
@@ -69,8 +70,15 @@ SPECS = {
     "diga_wgrad_batched_bf16x6_f32in": "dyp xp dw ws ws_bytes rows batches cout cin stream",
     "diga_wgrad_bf16x6_tiled_f32in": f"dyp dy_ld xp x_ld dw ws ws_bytes {W15} stream",
     "diga_wgrad_bf16x6_tile": "cout cin bm bn",
+    "diga_conv_taps_bf16x6_f32in_opts": f"in in_ld img bias? out {G16} stats? opts tag stream",
+    "diga_conv_window_bf16x6_f32in": f"in in_ld img bias? out {GW} dy dx opts? tag stream",
+    "diga_conv_up2_bf16x6_f32in": f"in in_ld img img_ph bias? out {GW} opts tag stream",
+    "diga_collapse_up2_weights": "wgt wc cout r s cin oy ox stream",
 }
-POINTERS = ("in", "wgt", "wgt_hi", "wgt_lo", "img", "bias", "out", "stats", "dyp", "xp", "dw", "ws", "table", "tile_table", "v_keep", "v_kept")
+# the plan functions answer through int* results: recorded as queries, [value returned, the integers written (-7: not written)]
+PLANS = {"diga_conv_window_bf16x6_plan": 3, "diga_conv_up2_bf16x6_plan": 2}
+POINTERS = ("in", "wgt", "wgt_hi", "wgt_lo", "img", "bias", "out", "stats", "dyp", "xp", "dw", "ws", "table", "tile_table", "v_keep", "v_kept",
+            "img_ph", "wc")
 DESCRIPTORS = ("epi", "infer", "opts")
 OUT_INTS = ("bm", "bn")          # results written through an int*: a real int unless the case passes null (0)
 
@@ -89,11 +97,15 @@ def is_winograd(name):
 
 def has_taps(name):
     """The entry point takes more than one tap (R, S are not pinned to 1)."""
-    return "r" in params(name) and not ("bf16x6" in name and "taps" not in name and "tiled" not in name)
+    return "r" in params(name) and not ("bf16x6" in name and not any(k in name for k in ("taps", "tiled", "window", "up2")))
 
 
 def multi_tap_form(name):
-    return "conv_taps" in name or "tiled" in name
+    return "conv_taps" in name or "tiled" in name or is_window(name)
+
+
+def is_window(name):
+    return "conv_window" in name or "conv_up2" in name
 
 
 def base(name):
@@ -113,6 +125,8 @@ def base(name):
     for d in DESCRIPTORS:
         if d in ps:
             v[d] = None if d in optional(name) else dict(BASE_DESCRIPTOR[d])
+    if "conv_up2" in name:       # 3 x 3 tiles of 8 x 16 output pixels on the 2x upsampling of 10 x 18: one interior tile, every tap of it inside
+        v.update(hi=10, wi=18, ho=20, wo=36, r=5, s=5, oy=-2, ox=-2, opts=dict(upsample_shift=1))
     return v
 
 
@@ -276,6 +290,37 @@ def cases(valid=False):
             first = "in" if "in" in ps else "dyp"
             two = [{first: 0, "n": 0}, {first: 0, "cin": 48}, {first: A + 4, "cin": 48}, {first: A + 4, "n": 1 << 12, "ho": 1 << 10, "wo": 1 << 9},
                    {"cin": 48, "r": 65, "s": 1}, {"sy": 0, "r": 0}, {"oy": 1 << 31, "cin": 48}, {"n": 0, "r": 65}]
+            if is_window(name):
+                up2 = "conv_up2" in name
+                refl = dict(BASE_DESCRIPTOR["opts"], upsample_shift=int(up2), reflect_pad=1)
+                out += [one("rs=1", r=1, s=1), one("out_ld=2^31", out_ld=1 << 31), one("hi=2^30", hi=1 << 30), one("dy=4097", dy=4097),
+                        one("window_too_large", r=7, s=7, dy=8, dx=8),
+                        # a mirror reaches at most the far border (the collapsed form's own rule refuses these calls first)
+                        one("reflect_oy", opts=refl, oy=-12), one("reflect_ox", opts=refl, ox=-12), one("reflect_far_y", opts=refl, dy=7),
+                        one("reflect_far_x", opts=refl, dx=7), one("reflect_up1_oy", opts=dict(refl, upsample_shift=1), oy=-24),
+                        one("reflect_far_y_ho", opts=refl, ho=40), one("reflect_far_x_wo", opts=refl, wo=72),
+                        one("too_many_tiles", n=1 << 12, hi=1 << 8, wi=1 << 8, ho=1 << 9, wo=1 << 9, cout=1 << 16, out_ld=1 << 16)]
+                if up2:          # what the collapsed form does not take (diga_conv_up2_bf16x6_plan), one reason each
+                    out += [one("up_shift=0", opts={}), one("up_shift=2", opts=dict(upsample_shift=2)), one("cout=16", cout=16),
+                            one("two_tile_rows", ho=16), one("two_tile_columns", wo=32), one("r=8", r=8), one("r=1", r=1), one("oy=1", oy=1),
+                            one("interior_tap_outside", ho=28), one("oy=-9", oy=-9), one("img_ph+4+bad_opts", img_ph=A + 4, opts=dict(activation=2))]
+                # two faults, rule by rule in the order of the checks
+                taken = dict(cout=16) if up2 else dict(r=7, s=7, dy=8, dx=8)
+                chain = [{"in": 0}, {"n": 0}] + ([] if up2 else [{"r": 65, "s": 1}]) + \
+                    [{"cin": 48}, {"in_ld": 66}, {"in": A + 4}, {"opts": dict(activation=2)}, {"oy": 1 << 31}, taken, {"n": 1 << 12, "hi": 1 << 10, "wi": 1 << 9}]
+                two += [{**a, **b} for a, b in zip(chain, chain[1:])]
+                two += [{"opts": refl, "oy": -12, "n": 1 << 12, "hi": 1 << 10, "wi": 1 << 9}, {"opts": refl, "oy": -12, "in": A + 4},
+                        {"opts": refl, "oy": -12, "cout": 1 << 16, "out_ld": 1 << 16, "n": 1 << 12, "hi": 1 << 8, "wi": 1 << 8, "ho": 1 << 9, "wo": 1 << 9}]
+            if "opts" in ps and "stats" in ps:                   # a folded input map comes without statistics
+                chain = [{"in": 0}, {"n": 0}, {"in_ld": -1}, {"r": 65, "s": 1}, {"sy": 0}, {"stats": A}, {"opts": dict(activation=2)},
+                         {"oy": 1 << 31}, {"cin": 48}, {"in": A + 4}, {"n": 1 << 12, "ho": 1 << 10, "wo": 1 << 9}]
+                out += [one("stats", stats=A), one("stats+4", stats=A + 4), one("hi=2^30", hi=1 << 30), one("hi=2^29_up_shift=1", hi=1 << 29, opts=dict(upsample_shift=1)),
+                        one("too_many_tiles", n=1 << 10, ho=1 << 10, wo=1 << 10, cout=1 << 16, out_ld=1 << 16)]
+                two += [{**a, **b} for a, b in zip(chain, chain[1:]) if not set(a) & set(b)]
+            if name == "diga_collapse_up2_weights":
+                out += [one("r=1", r=1), one("r=8", r=8), one("s=1", s=1), one("s=8", s=8), one("oy=1", oy=1), one("ox=1", ox=1),
+                        one("oy=-2^30", oy=-(1 << 30)), one("ox=-2^30", ox=-(1 << 30)), one("2^40_elements", cout=1 << 31)]
+                two += [{"wgt": A + 4, "r": 1}, {"wc": A + 4, "oy": 1}, {"wgt": 0, "wc": A + 4}]
             if "tiled" in name:
                 # Cin % 8 is the rule at 1x1, Cin % 32 with taps; the tap coordinates answer before pitch, alignment, pixel count, workspace
                 out += [one("cin=72+ld+ws_bytes=64", cin=72, x_ld=72, ws_bytes=64), one("cin=44+ld", cin=44, x_ld=44)]
@@ -286,7 +331,8 @@ def cases(valid=False):
             if "ws_bytes" in ps:
                 two += [{"ws_bytes": 0, first: A + 4}, {"ws_bytes": 0, "n": 1 << 12, "ho": 1 << 10, "wo": 1 << 9}, {"ws_bytes": 0, "cin": 48},
                         {"ws_bytes": 0, "math": 2}, {"ws": 0, "n": 0}]
-        out += [one("+".join(f"{k}={v}" for k, v in kw.items()), **kw) for kw in two]
+        out += [one("+".join(f"{k}={v}" if not isinstance(v, dict) else k + ":" + ",".join(f"{f}={x}" for f, x in v.items()) for k, v in kw.items()), **kw)
+                for kw in two]
         seen = set()
         for c in out:
             if c is not None and c[0] not in seen and (valid or c[0] not in VALID_CALLS):
@@ -353,14 +399,28 @@ def call(_lib, name, vals):
 
 # ------------------------------------------------------------------------------------------------------------------ queries
 def is_query(name):
-    return name.endswith(("_workspace_bytes", "_stats_floats", "_stats_records", "_v_floats", "_tile_table_bytes", "_image_bytes")) or \
+    return name in PLANS or name.endswith(("_workspace_bytes", "_stats_floats", "_stats_records", "_v_floats", "_tile_table_bytes", "_image_bytes")) or \
         name in ("diga_conv2d_stats_chunk_rows", "diga_conv2d_epi_chunk_rows")
 
 
+ENTRY_PREFIXES = ("diga_conv2d_", "diga_conv_taps_", "diga_conv_window_", "diga_conv_up2_", "diga_collapse_up2_", "diga_infer_conv",
+                  "diga_wgrad_bf16x6_")
+QUERY_PREFIXES = ENTRY_PREFIXES + ("diga_split_bf16",)           # (of the weight-image functions only the size queries)
+
+
 def in_scope(name, restype_is_int):
-    conv = name.startswith(("diga_conv2d_", "diga_conv_taps_", "diga_infer_conv", "diga_split_bf16", "diga_wgrad_bf16x6_")) or \
-        "batched_bf16x6" in name
-    return conv and (is_query(name) or (restype_is_int and name in SPECS))
+    """By name alone: an entry point or query that joins `_lib.SIGNATURES` under one of these names is in scope whether or not a case
+    was written for it (the coverage test then fails until one is)."""
+    if is_query(name):
+        return name.startswith(QUERY_PREFIXES) or "batched_bf16x6" in name
+    return restype_is_int and (name.startswith(ENTRY_PREFIXES) or "batched_bf16x6" in name)
+
+
+def query(_lib, name, args):
+    """The answer of one query: the value returned; for a plan function [value returned, the integers written]."""
+    outs = [ctypes.c_int(-7) for _ in range(PLANS.get(name, 0))]
+    got = getattr(_lib.lib, name)(*args, *[ctypes.byref(o) for o in outs])
+    return [got] + [o.value for o in outs] if outs else got
 
 
 def queries():
@@ -401,6 +461,22 @@ def queries():
             for m in (0, 1, 2, 3)]
     grids["diga_conv2d_stats_chunk_rows"] = rows
     grids["diga_conv2d_epi_chunk_rows"] = rows
+    # (Hi, Wi, Cin, Cout, R, S, dil_y, dil_x, upsample_shift)
+    grids["diga_conv_window_bf16x6_plan"] = [(h, w, ci, co, r, s, dy, dx, up) for h, w in ((12, 12), (97, 33), (0, 12), (12, -1))
+                                             for ci, co in ((64, 64), (32, 3), (64, 16), (64, 17), (48, 64), (0, 64), (64, 0))
+                                             for r, s, dy, dx in ((3, 3, 1, 1), (5, 5, 1, 1), (7, 7, 1, 1), (3, 3, 2, 2), (3, 3, 14, 14), (7, 7, 4, 4),
+                                                                  (7, 7, 8, 8), (9, 9, 1, 1), (1, 1, 1, 1), (1, 2, 1, 1), (65, 1, 1, 1), (8, 8, 1, 1),
+                                                                  (3, 3, 0, 1), (3, 3, 1, 4097), (3, 1, 4096, 1))
+                                             for up in (0, 1, 2, 3, -1)]
+    # (Hi, Wi, Cin, Cout, Ho, Wo, R, S, off_y0, off_x0, dil_y, dil_x, upsample_shift, reflect_pad)
+    grids["diga_conv_up2_bf16x6_plan"] = [(h, w, ci, co, ho, wo, r, s, oy, ox, dy, dx, up, refl)
+                                          for h, w, ho, wo in ((10, 18, 20, 36), (12, 24, 24, 48), (96, 96, 192, 192), (8, 16, 16, 32), (10, 18, 20, 32),
+                                                               (10, 18, 24, 36), (10, 18, 20, 52), (0, 18, 20, 36), (1 << 29, 18, 20, 36), (10, 18, 0, 36))
+                                          for ci, co in ((32, 72), (64, 64), (64, 16), (48, 72))
+                                          for r, s, oy, ox in ((5, 5, -2, -2), (3, 3, -1, -1), (7, 7, -3, -3), (4, 4, -1, -2), (2, 2, 0, 0), (5, 5, -3, -2),
+                                                               (8, 8, -3, -3), (1, 3, 0, -1), (3, 3, 1, -1), (5, 5, -2, -9), (5, 5, -9, -2))
+                                          for dy, dx, up, refl in ((1, 1, 1, 0), (1, 1, 1, 1), (2, 1, 1, 0), (1, 2, 1, 0), (1, 1, 0, 0), (1, 1, 2, 0),
+                                                                   (1, 1, 1, 2), (1, 1, 1, -1))]
     for name, grid in grids.items():
         for g in grid:
             yield f"{name}{tuple(g)}", name, tuple(g)
@@ -424,7 +500,7 @@ def record(_lib, relist, only=""):
             accepted.append(cid)
     if accepted and not relist:
         raise SystemExit("calls that no argument check rejects and that are not listed as valid calls:\n" + "\n".join(accepted))
-    q = {qid: getattr(_lib.lib, name)(*args) for qid, name, args in queries() if name.startswith(only)}
+    q = {qid: query(_lib, name, args) for qid, name, args in queries() if name.startswith(only)}
     return {"calls": got, "queries": q, "valid_calls": sorted(accepted) if relist else sorted(VALID_CALLS)}
 
 
@@ -433,12 +509,15 @@ if __name__ == "__main__":
     from diga_amd import _lib
     if "--merge" in sys.argv:
         # entry points that join the fixture later: their answers are recorded (valid calls relisted), every other entry is kept as it is
-        data, new = load_fixture(), record(_lib, True, sys.argv[sys.argv.index("--merge") + 1])
-        data["calls"].update(new["calls"])
-        data["queries"].update(new["queries"])
-        data["valid_calls"] = sorted(set(data["valid_calls"]) | set(new["valid_calls"]))
+        data = load_fixture()
+        for only in sys.argv[sys.argv.index("--merge") + 1:]:
+            new = record(_lib, True, only)
+            assert not (set(new["calls"]) | set(new["queries"])) & (set(data["calls"]) | set(data["queries"])), "already recorded: " + only
+            data["calls"].update(new["calls"])
+            data["queries"].update(new["queries"])
+            data["valid_calls"] = sorted(set(data["valid_calls"]) | set(new["valid_calls"]))
+            print(f"{only}: {len(new['calls'])} calls, {len(new['queries'])} queries, {len(new['valid_calls'])} valid calls merged into {FIXTURE}")
         dump_fixture(data)
-        print(f"{len(new['calls'])} calls, {len(new['queries'])} queries, {len(new['valid_calls'])} valid calls merged into {FIXTURE}")
     elif "--record" in sys.argv:
         data = record(_lib, "--relist-valid" in sys.argv)
         dump_fixture(data)
