@@ -1,21 +1,36 @@
-// Winograd F(2x2, 3x3) in fp32 for the stride-1 "same" 3x3 convolutions of the trunk and the ASPP head (dilation d,
-// padding d): layer3/layer4 conv2 (d = 2, 4), the ASPP branches (d = 6, 12, 18) and the ASPP bottleneck (d = 1) -- 64 %
-// of the model's convolution FLOPs.  Reference: the nn.Conv2d(3x3) layers of G5/model/seg_model_noaux.py:66-70,
-// 143-150,166-170, which the reference runs through cuDNN (whose fp32 algorithm choice for these shapes is Winograd too).
+// Winograd F(m x m, 3x3) in fp32, m = 2, 4 or 6, for the stride-1 "same" 3x3 convolutions of the trunk and the ASPP head (dilation d,
+// padding d): layer3/layer4 conv2 (d = 2, 4), the ASPP branches (d = 6, 12, 18) and the ASPP bottleneck (d = 1) -- 64 % of the model's
+// convolution FLOPs.  Reference: the nn.Conv2d(3x3) layers of G5/model/seg_model_noaux.py:66-70, 143-150,166-170, which the reference
+// runs through cuDNN (whose fp32 algorithm choice for these shapes is Winograd too).
 //
 // A dilated 3x3 convolution with padding = dilation is d*d independent dense 3x3 convolutions on the sub-images
-// {(a + d*i, b + d*j)} (phase (a, b)).  Each sub-image is cut into 2x2 output tiles; per tile and input channel the 4x4
-// input patch becomes V = B^T d B (wino_input_kernel), per (output, input) channel the 3x3 filter becomes U = G g G^T
-// (wino_weight_kernel), the 16 element-wise products summed over the input channels are 16 independent GEMMs
-//   M_k [tiles x Cout] = V_k [tiles x Cin] * U_k^T [Cin x Cout]         (16 multiplications per 2x2 outputs instead of 36)
-// run as ONE launch of conv_fwd_dma_kernel (exact-fp32 MFMA, LDS-DMA operands; the weight panel is picked per 256-row
-// tile), and y = A^T M A (+ bias) (wino_output_kernel).  B, G, A hold 0, +-1, +-1/2 only: the result differs from the
-// direct convolution by rounding alone (Lavin & Gray 2016 measure F(2x2,3x3) fp32 error BELOW direct convolution's);
-// tests hold both against a float64 convolution with the same bound.
+// {(a + d*i, b + d*j)} (phase (a, b)).  Each sub-image is cut into m x m output tiles; with A = m + 2, per tile and input channel the
+// A x A input patch becomes V = B^T d B (winoM_input_kernel; wino_input_kernel for m = 2), per (output, input) channel the 3x3 filter becomes U = G g G^T
+// (winoM_weight_kernel), the A * A element-wise products summed over the input channels are A * A independent GEMMs
+//   M_k [tiles x Cout] = V_k [tiles x Cin] * U_k^T [Cin x Cout]
+// run as ONE launch of conv_fwd_dma_kernel (exact-fp32 MFMA, LDS-DMA operands; the weight panel is picked per 256-row tile), and
+// y = A^T M A (+ bias) (winoM_output_kernel and its siblings with statistics, the inference epilogue or the backward-data epilogue).
+// The weight gradient runs the transposed chain (winoM_dy_kernel, a batched GEMM over the tiles, winoM_dw_kernel).
 //
-// Workspace: [tile table int4 x Tp][U 16 x Cout x Cin][V 16 x Tp x Cin][M 16 x Tp x Cout], Tp = tiles rounded up to
-// 256 (rows of padding tiles are zero).  HBM traffic on top of the GEMM: V is written and read once (4x the input
-// tensor), M likewise (4x the output) -- both transforms are plain bandwidth passes.
+// One set of kernel templates serves every tile edge M; what differs per M is the five 1-D transforms (Xf<M>) and the vector width of
+// each pass (Vec<M>):
+//   F(2,3): 16 products per 4 outputs (4 multiplications per output instead of 9 direct; V is 4x the input, M 4x the output).  B, G, A
+//           hold 0, +-1, +-1/2 only and are written out by hand: the result differs from the direct convolution by rounding alone
+//           (Lavin & Gray 2016 measure F(2x2,3x3) fp32 error BELOW direct convolution's; here 7.5e-7 of the output scale against float64
+//           on a 512-channel layer, the direct fmaf chain 3e-7).  The tile of set_conv_math(0, exact=True).
+//   F(4,3): 36 products per 16 outputs (2.25 per output; V and M 2.25x); points 0, 1, -1, 2, -1/2, inf -- max 4.9e-6 of the output scale
+//           (Lavin & Gray's 0, +-1, +-2: 1.2e-5);
+//   F(6,3): 64 products per 36 outputs (1.78 per output; V and M 1.78x); points 0, +-1, +-2, +-1/2, inf -- max 2.7e-5, rms 2.0e-6.
+// The transforms of F(4,3) and F(6,3) are generated (tools/gen_winograd_xforms.py -> winograd_xforms.h) from the exact Toom-Cook
+// matrices.  The caller picks the tile per layer (diga_amd/model/conv.py::_wino_plan: fewest multiplications); tests hold every tile
+// size to its own bound against float64, the full-size captures to north_star's 1e-3, and F(2,3) to recorded bits
+// (tests/test_gpu_winograd_f2_bits.py).
+//
+// Workspace: [tile table int4 x Tp][U A*A x Cout x Cin][V A*A x Tp x Cin][M A*A x Tp x Cout], Tp = tiles rounded up to 256 (rows of
+// padding tiles are zero).  HBM traffic on top of the GEMM: V is written and read once, M likewise -- both transforms are plain
+// bandwidth passes.
+#include <type_traits>
+
 #include "common.h"
 #include "conv_call.h"
 
@@ -40,7 +55,7 @@ namespace wino {
 
 struct WinoGeom {
     int N, H, W, d;
-    int m;                 // output tile edge: 2 = F(2x2,3x3) (16 products), 4 = F(4x4,3x3) (36 products)
+    int m;                 // output tile edge: 2 = F(2x2,3x3) (16 products), 4 = F(4x4,3x3) (36), 6 = F(6x6,3x3) (64)
     int tys, txs;          // tile rows / columns summed over the d phases
     int64_t T, Tp;
 };
@@ -115,323 +130,6 @@ __device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4
 __device__ __forceinline__ float4 f4sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float4 f4half(float4 a) { return make_float4(0.5f * a.x, 0.5f * a.y, 0.5f * a.z, 0.5f * a.w); }
 
-// U[k = 4 i + j][co][c] = (G g G^T)[i][j], g = w[co][.][.][c] (flip: g[r][s] = w[co][2 - r][2 - s][c], backward-data)
-__global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restrict__ w, float* __restrict__ U, int Cout, int Cin,
-                                                          int flip) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c4n = Cin / 4;
-    if (idx >= (int64_t)Cout * c4n) return;
-    const int co = (int)(idx / c4n), c = (int)(idx - (int64_t)co * c4n) * 4;
-    float4 g[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            const int rr = flip ? 2 - r : r, ss = flip ? 2 - s : s;
-            g[r][s] = *reinterpret_cast<const float4*>(w + ((int64_t)co * 9 + rr * 3 + ss) * Cin + c);
-        }
-    float4 t[4][3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        const float4 sum = f4add(g[0][s], g[2][s]);
-        t[0][s] = g[0][s];
-        t[1][s] = f4half(f4add(sum, g[1][s]));
-        t[2][s] = f4half(f4sub(sum, g[1][s]));
-        t[3][s] = g[2][s];
-    }
-    const int64_t plane = (int64_t)Cout * Cin;
-    float* o = U + (int64_t)co * Cin + c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float4 sum = f4add(t[i][0], t[i][2]);
-        *reinterpret_cast<float4*>(o + (4 * i + 0) * plane) = t[i][0];
-        *reinterpret_cast<float4*>(o + (4 * i + 1) * plane) = f4half(f4add(sum, t[i][1]));
-        *reinterpret_cast<float4*>(o + (4 * i + 2) * plane) = f4half(f4sub(sum, t[i][1]));
-        *reinterpret_cast<float4*>(o + (4 * i + 3) * plane) = t[i][2];
-    }
-}
-
-// V[k][t][c] = (B^T d B)[i][j] of the 4x4 patch of tile t, channel c (zero outside the image / for padding tiles)
-__global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ x, int64_t ld, const int4* __restrict__ tab,
-                                                         float* __restrict__ V, int64_t Tp, int C, int H, int W, int d) {
-    const int c4n = C / 4;
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= Tp * c4n) return;
-    const int64_t t = idx / c4n;
-    const int c = (int)(idx - t * c4n) * 4;
-    const int4 e = tab[t];
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    // branch-free: every tap is loaded from a clamped (valid) address and zeroed afterwards when it lies outside the image, so the
-    // 16 loads of a thread issue back to back (measured on the 4x4-tile twin of this kernel: 151 -> 109 us)
-    const int img = max(e.x, 0);
-    float4 p[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int y = e.y + (i - 1) * d;
-        const bool yok = e.x >= 0 && (unsigned)y < (unsigned)H;
-        const int yc = min(max(y, 0), H - 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int xx = e.z + (j - 1) * d;
-            const bool ok = yok && (unsigned)xx < (unsigned)W;
-            const float4 v = *reinterpret_cast<const float4*>(x + ((int64_t)(img * H + yc) * W + min(max(xx, 0), W - 1)) * ld + c);
-            p[i][j] = ok ? v : z;
-        }
-    }
-    float4 m[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        m[0][j] = f4sub(p[0][j], p[2][j]);
-        m[1][j] = f4add(p[1][j], p[2][j]);
-        m[2][j] = f4sub(p[2][j], p[1][j]);
-        m[3][j] = f4sub(p[1][j], p[3][j]);
-    }
-    float* o = V + t * C + c;
-    const int64_t plane = Tp * C;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        nt_store4(o + (4 * i + 0) * plane, f4sub(m[i][0], m[i][2]));
-        nt_store4(o + (4 * i + 1) * plane, f4add(m[i][1], m[i][2]));
-        nt_store4(o + (4 * i + 2) * plane, f4sub(m[i][2], m[i][1]));
-        nt_store4(o + (4 * i + 3) * plane, f4sub(m[i][1], m[i][3]));
-    }
-}
-
-// y[2x2 of tile t][co] = A^T M A + bias
-__global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ Mb, const int4* __restrict__ tab,
-                                                          const float* __restrict__ bias, float* __restrict__ y, int64_t ld,
-                                                          int64_t T, int64_t Tp, int K, int H, int W, int d) {
-    const int k4n = K / 4;
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= T * k4n) return;
-    const int64_t t = idx / k4n;
-    const int k = (int)(idx - t * k4n) * 4;
-    const int4 e = tab[t];
-    const int64_t plane = Tp * K;
-    const float* src = Mb + t * K + k;
-    float4 m[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) m[i][j] = nt_load4(src + (4 * i + j) * plane);
-    float4 s[2][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        s[0][j] = f4add(f4add(m[0][j], m[1][j]), m[2][j]);
-        s[1][j] = f4sub(f4sub(m[1][j], m[2][j]), m[3][j]);
-    }
-    const float4 b = bias != nullptr ? *reinterpret_cast<const float4*>(bias + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int yy = e.y + i * d;
-        if (yy >= H) continue;
-        const float4 o0 = f4add(f4add(f4add(s[i][0], s[i][1]), s[i][2]), b);
-        const float4 o1 = f4add(f4sub(f4sub(s[i][1], s[i][2]), s[i][3]), b);
-        float* row = y + ((int64_t)(e.x * H + yy) * W) * ld + k;
-        *reinterpret_cast<float4*>(row + (int64_t)e.z * ld) = o0;
-        if (e.z + d < W) *reinterpret_cast<float4*>(row + (int64_t)(e.z + d) * ld) = o1;
-    }
-}
-
-// wino_output_kernel for a backward-data convolution with the fused epilogue of diga_bwd_epilogue_t (same arithmetic, element
-// by element, as drain_stage<EPI> in conv.hip): out = mask(A^T M A + addend) and the BatchNorm-backward column sums
-// { sum g, sum g * xhat }.  Block (g, s): tiles [g * tpb, (g + 1) * tpb) x channels [256 s, 256 s + 256), 64 channel quads x 4
-// tile lanes; its sums go to row g of `partials` ([G][2][K], G = ceil(N H W / 128) rows as the direct kernel fills them --
-// the finaliser only adds the rows up), reduced over the tile lanes in fixed order.
-struct WinoEpi {
-    const float* add;
-    const float* masky;
-    const unsigned char* maskbits;
-    const float* x;
-    const float* relu_ab;
-    const float* mean;
-    const float* invstd;
-    float* partials;
-    int64_t add_ld, masky_ld, x_ld, maskbits_ld;
-};
-
-__global__ __launch_bounds__(256) void wino_output_epi_kernel(const float* __restrict__ Mb, const int4* __restrict__ tab,
-                                                              float* __restrict__ y, int64_t ld, int64_t T, int64_t Tp, int K,
-                                                              int H, int W, int d, int tpb, WinoEpi ep) {
-    __shared__ float red[2][4][256];
-    const int q = threadIdx.x & 63, tl = threadIdx.x >> 6;
-    const int k = (blockIdx.y * 64 + q) * 4;
-    const bool kok = k < K;
-    const int64_t t0 = (int64_t)blockIdx.x * tpb;
-    int64_t t1 = t0 + tpb;
-    if (t1 > T) t1 = T;
-    const int64_t plane = Tp * K;
-    float ra[4] = {0.f, 0.f, 0.f, 0.f}, rb[4] = {0.f, 0.f, 0.f, 0.f}, mu[4] = {0.f, 0.f, 0.f, 0.f}, is[4] = {0.f, 0.f, 0.f, 0.f};
-    if (kok && ep.relu_ab != nullptr) {
-        const float4 a0 = *reinterpret_cast<const float4*>(ep.relu_ab + k), a1 = *reinterpret_cast<const float4*>(ep.relu_ab + K + k);
-        ra[0] = a0.x; ra[1] = a0.y; ra[2] = a0.z; ra[3] = a0.w;
-        rb[0] = a1.x; rb[1] = a1.y; rb[2] = a1.z; rb[3] = a1.w;
-    }
-    if (kok && ep.partials != nullptr) {
-        const float4 a0 = *reinterpret_cast<const float4*>(ep.mean + k), a1 = *reinterpret_cast<const float4*>(ep.invstd + k);
-        mu[0] = a0.x; mu[1] = a0.y; mu[2] = a0.z; mu[3] = a0.w;
-        is[0] = a1.x; is[1] = a1.y; is[2] = a1.z; is[3] = a1.w;
-    }
-    float sd[4] = {0.f, 0.f, 0.f, 0.f}, sd2[4] = {0.f, 0.f, 0.f, 0.f};
-    if (kok) {
-        for (int64_t t = t0 + tl; t < t1; t += 4) {
-            const int4 e = tab[t];
-            const float* src = Mb + t * K + k;
-            float4 m[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) m[i][j] = nt_load4(src + (4 * i + j) * plane);
-            float4 s[2][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                s[0][j] = f4add(f4add(m[0][j], m[1][j]), m[2][j]);
-                s[1][j] = f4sub(f4sub(m[1][j], m[2][j]), m[3][j]);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int yy = e.y + i * d;
-                if (yy >= H) continue;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int xx = e.z + j * d;
-                    if (xx >= W) continue;
-                    const float4 o = j == 0 ? f4add(f4add(s[i][0], s[i][1]), s[i][2]) : f4sub(f4sub(s[i][1], s[i][2]), s[i][3]);
-                    const int64_t row = (int64_t)(e.x * H + yy) * W + xx;
-                    float v[4] = {o.x, o.y, o.z, o.w};
-                    float xv[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (ep.add != nullptr) {
-                        const float4 a4 = *reinterpret_cast<const float4*>(ep.add + row * ep.add_ld + k);
-                        v[0] += a4.x; v[1] += a4.y; v[2] += a4.z; v[3] += a4.w;
-                    }
-                    if (ep.x != nullptr) {
-                        const float4 x4 = *reinterpret_cast<const float4*>(ep.x + row * ep.x_ld + k);
-                        xv[0] = x4.x; xv[1] = x4.y; xv[2] = x4.z; xv[3] = x4.w;
-                    }
-                    if (ep.masky != nullptr) {
-                        const float4 y4 = *reinterpret_cast<const float4*>(ep.masky + row * ep.masky_ld + k);
-                        v[0] = y4.x > 0.f ? v[0] : 0.f; v[1] = y4.y > 0.f ? v[1] : 0.f;
-                        v[2] = y4.z > 0.f ? v[2] : 0.f; v[3] = y4.w > 0.f ? v[3] : 0.f;
-                    } else if (ep.maskbits != nullptr) {
-                        const unsigned b = ep.maskbits[row * ep.maskbits_ld + (k >> 3)] >> (k & 4);
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) v[c] = ((b >> c) & 1u) ? v[c] : 0.f;
-                    } else if (ep.relu_ab != nullptr) {
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) v[c] = __builtin_fmaf(xv[c], ra[c], rb[c]) > 0.f ? v[c] : 0.f;
-                    }
-                    *reinterpret_cast<float4*>(y + row * ld + k) = make_float4(v[0], v[1], v[2], v[3]);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        sd[c] += v[c];
-                        sd2[c] += v[c] * ((xv[c] - mu[c]) * is[c]);
-                    }
-                }
-            }
-        }
-    }
-    if (ep.partials == nullptr) return;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        red[0][tl][q * 4 + c] = sd[c];
-        red[1][tl][q * 4 + c] = sd2[c];
-    }
-    __syncthreads();
-    const int ch = blockIdx.y * 256 + threadIdx.x;
-    if (ch < K) {
-        float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            a0 += red[0][l][threadIdx.x];
-            a1 += red[1][l][threadIdx.x];
-        }
-        float* sp = ep.partials + (int64_t)blockIdx.x * 2 * K + ch;
-        sp[0] = a0;
-        sp[K] = a1;
-    }
-}
-
-// ---- backward-weight: dL/dg = G^T [ sum over tiles (A dY A^T) (.) (B^T d B) ] G  (the transpose of the forward chain).
-// Z[k][t][co] = (A dY A^T)[i][j] of the 2x2 output-gradient tile t (zero outside the image / for padding tiles)
-__global__ __launch_bounds__(256) void wino_dy_kernel(const float* __restrict__ dy, int64_t ld, const int4* __restrict__ tab,
-                                                      float* __restrict__ Z, int64_t Tp, int K, int H, int W, int d) {
-    const int k4n = K / 4;
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= Tp * k4n) return;
-    const int64_t t = idx / k4n;
-    const int k = (int)(idx - t * k4n) * 4;
-    const int4 e = tab[t];
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 g[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int yy = e.y + i * d, xx = e.z + j * d;
-            const bool ok = e.x >= 0 && yy < H && xx < W;
-            const float4 v = *reinterpret_cast<const float4*>(dy + ((int64_t)(max(e.x, 0) * H + min(yy, H - 1)) * W + min(xx, W - 1)) * ld + k);
-            g[i][j] = ok ? v : z;
-        }
-    // rows of A = [1 0; 1 1; 1 -1; 0 -1]
-    float4 r[4][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        r[0][j] = g[0][j];
-        r[1][j] = f4add(g[0][j], g[1][j]);
-        r[2][j] = f4sub(g[0][j], g[1][j]);
-        r[3][j] = f4sub(z, g[1][j]);
-    }
-    float* o = Z + t * K + k;
-    const int64_t plane = Tp * K;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        nt_store4(o + (4 * i + 0) * plane, r[i][0]);
-        nt_store4(o + (4 * i + 1) * plane, f4add(r[i][0], r[i][1]));
-        nt_store4(o + (4 * i + 2) * plane, f4sub(r[i][0], r[i][1]));
-        nt_store4(o + (4 * i + 3) * plane, f4sub(z, r[i][1]));
-    }
-}
-
-// dw[co][r][s][c] = (G^T dU G)[r][s], dU [co][16][c]
-__global__ __launch_bounds__(256) void wino_dw_kernel(const float* __restrict__ dU, float* __restrict__ dw, int Cout, int Cin) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c4n = Cin / 4;
-    if (idx >= (int64_t)Cout * c4n) return;
-    const int co = (int)(idx / c4n), c = (int)(idx - (int64_t)co * c4n) * 4;
-    const float* src = dU + (int64_t)co * 16 * Cin + c;
-    float4 u[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) u[i][j] = *reinterpret_cast<const float4*>(src + (int64_t)(4 * i + j) * Cin);
-    // G^T = [1 .5 .5 0; 0 .5 -.5 0; 0 .5 .5 1]
-    float4 t[3][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float4 hs = f4half(f4add(u[1][j], u[2][j])), hd = f4half(f4sub(u[1][j], u[2][j]));
-        t[0][j] = f4add(u[0][j], hs);
-        t[1][j] = hd;
-        t[2][j] = f4add(hs, u[3][j]);
-    }
-    float* o = dw + (int64_t)co * 9 * Cin + c;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const float4 hs = f4half(f4add(t[r][1], t[r][2])), hd = f4half(f4sub(t[r][1], t[r][2]));
-        *reinterpret_cast<float4*>(o + (int64_t)(3 * r + 0) * Cin) = f4add(t[r][0], hs);
-        *reinterpret_cast<float4*>(o + (int64_t)(3 * r + 1) * Cin) = hd;
-        *reinterpret_cast<float4*>(o + (int64_t)(3 * r + 2) * Cin) = f4add(hs, t[r][3]);
-    }
-}
-
-// ======================================================================================================================
-// Larger tiles: F(m x m, 3x3) with m = 4 (36 products per 16 outputs: 2.25 multiplications per output instead of 9 direct / 4 with
-// F(2x2); V is 2.25x the input, M 2.25x the output) and m = 6 (64 products per 36 outputs: 1.78 per output; V and M 1.78x).  The
-// 1-D transforms are generated (tools/gen_winograd_xforms.py -> winograd_xforms.h) from the exact Toom-Cook matrices:
-//   F(4,3): points 0, 1, -1, 2, -1/2, inf -- fp32 error of a 512-channel layer against float64: max 4.9e-6 of the output scale
-//           (Lavin & Gray's 0, +-1, +-2: 1.2e-5; F(2x2): 7.5e-7; the direct fmaf chain 3e-7);
-//   F(6,3): points 0, +-1, +-2, +-1/2, inf -- max 2.7e-5, rms 2.0e-6.
-// The caller picks the tile per layer (diga_amd/model/conv.py::_wino_plan: fewest multiplications); tests hold every tile size
-// to its own bound against float64 and the full-size captures to north_star's 1e-3.
 __device__ __forceinline__ float4 f4fma(float s, float4 a, float4 b) {
     return make_float4(__builtin_fmaf(s, a.x, b.x), __builtin_fmaf(s, a.y, b.y), __builtin_fmaf(s, a.z, b.z), __builtin_fmaf(s, a.w, b.w));
 }
@@ -466,6 +164,39 @@ template <> __device__ __forceinline__ float2 vzero<float2>() { return make_floa
 #include "winograd_xforms.h"      // (inside namespace diga::wino: the generated transforms use the helpers above)
 
 template <int M> struct Xf;
+// F(2,3) by hand: sums, differences and halves only (NOT generated: the generator's FMA chains round differently, and these bits are
+// recorded -- tests/golden/wino_f2_bits.json)
+template <> struct Xf<2> {
+    template <typename V> static __device__ __forceinline__ void bt(const V* x, V* r) {          // B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
+        r[0] = f4sub(x[0], x[2]);
+        r[1] = f4add(x[1], x[2]);
+        r[2] = f4sub(x[2], x[1]);
+        r[3] = f4sub(x[1], x[3]);
+    }
+    template <typename V> static __device__ __forceinline__ void g(const V* x, V* r) {           // G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]
+        const V sum = f4add(x[0], x[2]);
+        r[0] = x[0];
+        r[1] = f4half(f4add(sum, x[1]));
+        r[2] = f4half(f4sub(sum, x[1]));
+        r[3] = x[2];
+    }
+    template <typename V> static __device__ __forceinline__ void at(const V* x, V* r) {          // A^T = [1 1 1 0; 0 1 -1 -1]
+        r[0] = f4add(f4add(x[0], x[1]), x[2]);
+        r[1] = f4sub(f4sub(x[1], x[2]), x[3]);
+    }
+    template <typename V> static __device__ __forceinline__ void a(const V* x, V* r) {           // A = [1 0; 1 1; 1 -1; 0 -1]
+        r[0] = x[0];
+        r[1] = f4add(x[0], x[1]);
+        r[2] = f4sub(x[0], x[1]);
+        r[3] = f4sub(vzero<V>(), x[1]);                                                          // (0 - x, not -x: they differ on +0)
+    }
+    template <typename V> static __device__ __forceinline__ void gt(const V* x, V* r) {          // G^T = [1 .5 .5 0; 0 .5 -.5 0; 0 .5 .5 1]
+        const V hs = f4half(f4add(x[1], x[2])), hd = f4half(f4sub(x[1], x[2]));
+        r[0] = f4add(x[0], hs);
+        r[1] = hd;
+        r[2] = f4add(hs, x[3]);
+    }
+};
 template <> struct Xf<4> {
     template <typename V> static __device__ __forceinline__ void bt(const V* x, V* r) { wino4_bt(x, r); }
     template <typename V> static __device__ __forceinline__ void g(const V* x, V* r) { wino4_g(x, r); }
@@ -482,13 +213,19 @@ template <> struct Xf<6> {
 };
 // vector width of each pass (measured on l3.conv2, 16 images, 4x4 tiles: output 82 us with float2 vs 94 us with float4 -- 113
 // instead of 215 VGPRs; input / dy: no difference; the 8x8-patch passes of 6x6 tiles hold 64 vectors per thread: pairs throughout)
+// and EpiLanes, the tile lanes of the backward-data output transform (round 4, 4x4 / 6x6 tiles: 11.5 / 10.1 / 9.8 ms per step with
+// 4 / 2 / 1).  The partial sums are added per lane in tile order, then over the lanes: the lane count is part of the result's bits.
 template <int M> struct Vec;
-template <> struct Vec<4> { using In = float4; using Out = float2; using Dy = float4; };
+// EpiBlocks: that transform's blocks per CU (__launch_bounds__): 4 = a 128-VGPR cap; on quads the fullest operand combinations (addend,
+// mask and sums) need 131-140 and would spill under it, 3 (168) leaves them three waves per SIMD and the other 13 four or five.
+// 4x4 patches: 16 vectors per thread, quads throughout; 4 tile lanes (the widths and the lane count F(2x2) has always run with)
+template <> struct Vec<2> { using In = float4; using Out = float4; using Dy = float4; using Dw = float4; static constexpr int EpiLanes = 4, EpiBlocks = 3; };
+template <> struct Vec<4> { using In = float4; using Out = float2; using Dy = float4; using Dw = float2; static constexpr int EpiLanes = 2, EpiBlocks = 4; };
 // round 5 re-measured the 6x6 input transform on float4: 108 vs 163 us per launch in a warm micro-benchmark (tools/bench_conv.py), but
 // INSIDE the step (cold operands, serialised: tools/diag/r05_regress.sh) 195 vs 177 us per launch, and the two-stream step 427.7 vs
 // 424.7 ms (three interleaved runs each on one box) -- the float4 form needs the whole register file (one wave per SIMD) and
 // co-resides with nothing.  Pairs stay; dy on pairs as well (84 vs 88 us).
-template <> struct Vec<6> { using In = float2; using Out = float; using Dy = float2; };
+template <> struct Vec<6> { using In = float2; using Out = float; using Dy = float2; using Dw = float2; static constexpr int EpiLanes = 2, EpiBlocks = 4; };
 
 // U[k = A i + j][co][c] = (G g G^T)[i][j], A = M + 2
 template <int M>
@@ -589,6 +326,56 @@ __global__ __launch_bounds__(256) void winoM_input_kernel(const float* __restric
         Xf<M>::bt(m[i], row);
 #pragma unroll
         for (int j = 0; j < A; ++j) wino_in_store<V>(o + (A * i + j) * plane, row[j]);
+    }
+}
+
+// winoM_input_kernel<2, float4, false> written out: the 4x4 patch loaded row by row, all sixteen taps before the first transform.  Same
+// bits, and the one F(2x2) pass the template does not run as fast: 611 -> 617 us per launch over the seven layers of
+// tools/bench_conv.py --winograd-only --winograd-max-tile 2 (+1.0 %, the parent's run-to-run spread is 1.2 us), +2 % on l3.conv2, +3 %
+// on l2.conv2 (profiles/r22_winograd_f2_speed.txt) at the same vector width and launch bounds.  The template's loop order is what the
+// 6x6 and 8x8 patches were tuned with, so this kernel stays; zero padding only.
+__global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ x, int64_t ld, const int4* __restrict__ tab,
+                                                         float* __restrict__ V, int64_t Tp, int C, int H, int W, int d) {
+    const int c4n = C / 4;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= Tp * c4n) return;
+    const int64_t t = idx / c4n;
+    const int c = (int)(idx - t * c4n) * 4;
+    const int4 e = tab[t];
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    // branch-free: every tap is loaded from a clamped (valid) address and zeroed afterwards when it lies outside the image, so the
+    // 16 loads of a thread issue back to back (measured on the 4x4-tile twin of this kernel: 151 -> 109 us)
+    const int img = max(e.x, 0);
+    float4 p[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int y = e.y + (i - 1) * d;
+        const bool yok = e.x >= 0 && (unsigned)y < (unsigned)H;
+        const int yc = min(max(y, 0), H - 1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int xx = e.z + (j - 1) * d;
+            const bool ok = yok && (unsigned)xx < (unsigned)W;
+            const float4 v = *reinterpret_cast<const float4*>(x + ((int64_t)(img * H + yc) * W + min(max(xx, 0), W - 1)) * ld + c);
+            p[i][j] = ok ? v : z;
+        }
+    }
+    float4 m[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        m[0][j] = f4sub(p[0][j], p[2][j]);
+        m[1][j] = f4add(p[1][j], p[2][j]);
+        m[2][j] = f4sub(p[2][j], p[1][j]);
+        m[3][j] = f4sub(p[1][j], p[3][j]);
+    }
+    float* o = V + t * C + c;
+    const int64_t plane = Tp * C;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        nt_store4(o + (4 * i + 0) * plane, f4sub(m[i][0], m[i][2]));
+        nt_store4(o + (4 * i + 1) * plane, f4add(m[i][1], m[i][2]));
+        nt_store4(o + (4 * i + 2) * plane, f4sub(m[i][2], m[i][1]));
+        nt_store4(o + (4 * i + 3) * plane, f4sub(m[i][1], m[i][3]));
     }
 }
 
@@ -768,7 +555,24 @@ __global__ __launch_bounds__(256, 4) void winoM_output_stats_kernel(const float*
     if (q == 0 && blockIdx.y == 0) counts[r] = n;
 }
 
-// Round 5: winoM_output_epi_kernel again, built for OCCUPANCY.  The kernel above it holds a tile's A * A products and the M * M pixels'
+// winoM_output_kernel for a backward-data convolution with the fused epilogue of diga_bwd_epilogue_t (same arithmetic, element by
+// element, as drain_stage<EPI> in conv.hip): out = mask(A^T M A + addend) and the BatchNorm-backward column sums { sum g, sum g * xhat }.
+// Block (g, s): tiles [g * tpb, (g + 1) * tpb) x one slab of CG * VW channels, CG channel groups x TL tile lanes; its sums go to row g
+// of `partials` ([G][2][K], G = ceil(N H W / 128) rows as the direct kernel fills them -- the finaliser only adds the rows up), reduced
+// over the tile lanes in fixed order.
+struct WinoEpi {
+    const float* add;
+    const float* masky;
+    const unsigned char* maskbits;
+    const float* x;
+    const float* relu_ab;
+    const float* mean;
+    const float* invstd;
+    float* partials;
+    int64_t add_ld, masky_ld, x_ld, maskbits_ld;
+};
+
+// Round 5 rebuilt this kernel for OCCUPANCY.  Round 4's form held a tile's A * A products and the M * M pixels'
 // epilogue operands (addend, x, mask: up to 3 * 36 values) in registers at once -- 256 VGPRs, one wave per SIMD, 2.0 TB/s on l3.conv2
 // (626 MB in 316 us) where the plain output transform (95 VGPRs, five waves per SIMD) moves its bytes at 5.7 TB/s.  Here a thread
 // column-transforms the products as they arrive (A * M values stay), then walks the tile's rows: the epilogue operands of ONE row are
@@ -777,7 +581,7 @@ __global__ __launch_bounds__(256, 4) void winoM_output_stats_kernel(const float*
 // tests.  Same arithmetic per element, same partial-row layout (block (g, s) = tile group x channel slab, TL tile lanes reduced
 // through LDS in lane order): bit-identical results.
 template <int M, typename V, int TL, bool ADD, int MASK /* 0 none, 1 y > 0, 2 bits, 3 fma(x, a, b) > 0 */, bool SUMS>
-__global__ __launch_bounds__(256, 4) void winoM_output_epi2_kernel(const float* __restrict__ Mb, const int4* __restrict__ tab,
+__global__ __launch_bounds__(256, Vec<M>::EpiBlocks) void winoM_output_epi2_kernel(const float* __restrict__ Mb, const int4* __restrict__ tab,
                                                                 float* __restrict__ y, int64_t ld, int64_t T, int64_t Tp, int K,
                                                                 int H, int W, int d, int tpb, WinoEpi ep) {
     constexpr int A = M + 2;
@@ -956,25 +760,33 @@ __global__ __launch_bounds__(256) void winoM_dw_kernel(const float* __restrict__
     }
 }
 
-// ---- launches by tile size (2: the hand-written F(2x2) kernels above)
-template <int M>
+// ---- launches by tile size.  with_tile turns the run-time tile (tile_ok: 2, 4 or 6) into a compile-time M: f(TileC<M>{}).
+// LO = 4 at the sites whose rule refuses F(2x2) (statistics, the inference epilogue, reflection padding) and at the input transform, whose
+// F(2x2) form is wino_input_kernel: they instantiate no M = 2.
+template <int M> using TileC = std::integral_constant<int, M>;
+template <int LO = 2, typename F>
+static auto with_tile(int64_t tile, F&& f) {
+    if (tile == 6) return f(TileC<6>{});
+    if constexpr (LO == 2) {
+        if (tile == 2) return f(TileC<2>{});
+    }
+    return f(TileC<4>{});
+}
+template <int M, bool REFLECT>
 static void launch_input_m(const float* x, int64_t ld, const int4* tab, float* V, int64_t Tp, int64_t C, int64_t H, int64_t W, int64_t d,
-                           hipStream_t st, int reflect) {
+                           hipStream_t st) {
     using VT = typename Vec<M>::In;
     constexpr int VW = sizeof(VT) / 4;
-    const dim3 grid((unsigned)ceil_div(Tp * (C / VW), 256));
-    if (reflect)
-        hipLaunchKernelGGL((winoM_input_kernel<M, VT, true>), grid, dim3(256), 0, st, x, ld, tab, V, Tp, (int)C, (int)H, (int)W, (int)d);
-    else
-        hipLaunchKernelGGL((winoM_input_kernel<M, VT, false>), grid, dim3(256), 0, st, x, ld, tab, V, Tp, (int)C, (int)H, (int)W, (int)d);
+    hipLaunchKernelGGL((winoM_input_kernel<M, VT, REFLECT>), dim3((unsigned)ceil_div(Tp * (C / VW), 256)), dim3(256), 0, st, x, ld, tab, V, Tp,
+                       (int)C, (int)H, (int)W, (int)d);
 }
 static void launch_input(int64_t tile, const float* x, int64_t ld, const int4* tab, float* V, int64_t Tp, int64_t C, int64_t H, int64_t W,
                          int64_t d, hipStream_t st, int reflect = 0) {
-    if (tile == 6) launch_input_m<6>(x, ld, tab, V, Tp, C, H, W, d, st, reflect);
-    else if (tile == 4) launch_input_m<4>(x, ld, tab, V, Tp, C, H, W, d, st, reflect);
-    else
-        hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)ceil_div(Tp * (C / 4), 256)), dim3(256), 0, st, x, ld, tab, V, Tp, (int)C,
-                           (int)H, (int)W, (int)d);
+    if (reflect) with_tile<4>(tile, [&](auto m) { launch_input_m<decltype(m)::value, true>(x, ld, tab, V, Tp, C, H, W, d, st); });
+    else if (tile == 2)        // (the one hand-written F(2x2) pass: see wino_input_kernel)
+        hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)ceil_div(Tp * (C / 4), 256)), dim3(256), 0, st, x, ld, tab, V, Tp, (int)C, (int)H,
+                           (int)W, (int)d);
+    else with_tile<4>(tile, [&](auto m) { launch_input_m<decltype(m)::value, false>(x, ld, tab, V, Tp, C, H, W, d, st); });
 }
 template <int M>
 static void launch_weight_m(const float* w, float* U, int64_t Cout, int64_t Cin, int flip, hipStream_t st) {
@@ -1020,7 +832,7 @@ static WinoStatsPlan stats_plan_m(const WinoGeom& g, int64_t Cout) {
     return p;
 }
 static WinoStatsPlan stats_plan(const WinoGeom& g, int64_t Cout) {
-    return g.m == 6 ? stats_plan_m<6>(g, Cout) : stats_plan_m<4>(g, Cout);
+    return with_tile<4>(g.m, [&](auto m) { return stats_plan_m<decltype(m)::value>(g, Cout); });
 }
 template <int M>
 static void launch_output_stats_m(const float* Mb, const int4* tab, const float* bias, float* out, int64_t out_ld, const WinoGeom& g,
@@ -1033,13 +845,12 @@ static void launch_output_stats_m(const float* Mb, const int4* tab, const float*
                        Mb, tab, bias, out, out_ld, g.T, g.Tp, (int)Cout, g.H, g.W, g.d, p.tpb, p.CG, stats, counts);
 }
 
-constexpr int kEpiTileLanes = 2;    // tile lanes of the backward-data output transform (round 4: 11.5 / 10.1 / 9.8 ms per step with 4 / 2 / 1)
 template <int M, bool ADD, int MASK>
 static void launch_output_epi2_sums(const float* Mb, const int4* tab, float* out, int64_t out_ld, const WinoGeom& g, int64_t Cout, int64_t G,
                                     int tpb, const WinoEpi& ep, hipStream_t st) {
     using VT = typename Vec<M>::Out;
     constexpr int VW = sizeof(VT) / 4;
-    constexpr int TL = kEpiTileLanes;
+    constexpr int TL = Vec<M>::EpiLanes;
     const dim3 grid((unsigned)G, (unsigned)ceil_div(Cout, (256 / TL) * VW));
     if (ep.partials != nullptr)
         hipLaunchKernelGGL((winoM_output_epi2_kernel<M, VT, TL, ADD, MASK, true>), grid, dim3(256), 0, st, Mb, tab, out, out_ld, g.T, g.Tp,
@@ -1072,7 +883,9 @@ static void launch_dy_m(const float* dy, int64_t dy_ld, const int4* tab, float* 
 }
 template <int M>
 static void launch_dw_m(const float* dU, float* dw, int64_t Cout, int64_t Cin, hipStream_t st) {
-    hipLaunchKernelGGL((winoM_dw_kernel<M, float2>), dim3((unsigned)ceil_div(Cout * (Cin / 2), 256)), dim3(256), 0, st, dU, dw, (int)Cout, (int)Cin);
+    using VT = typename Vec<M>::Dw;
+    constexpr int VW = sizeof(VT) / 4;
+    hipLaunchKernelGGL((winoM_dw_kernel<M, VT>), dim3((unsigned)ceil_div(Cout * (Cin / VW), 256)), dim3(256), 0, st, dU, dw, (int)Cout, (int)Cin);
 }
 
 struct WinoWgradLayout {
@@ -1198,11 +1011,7 @@ static int winograd_conv(const WinoCall& c) {
     // (the table depends on the geometry only: a caller that keeps one per geometry -- diga_conv2d_winograd_tile_table -- saves the launch)
     if (tile_table == nullptr)
         hipLaunchKernelGGL(wino_tiles_kernel, dim3((unsigned)ceil_div(g.Tp, 256)), dim3(256), 0, st, reinterpret_cast<int4*>(ws + l.tab), g);
-    if (tile == 6) launch_weight_m<6>(wgt, U, Cout, Cin, flip, st);
-    else if (tile == 4) launch_weight_m<4>(wgt, U, Cout, Cin, flip, st);
-    else
-        hipLaunchKernelGGL(wino_weight_kernel, dim3((unsigned)ceil_div(Cout * (Cin / 4), 256)), dim3(256), 0, st, wgt, U, (int)Cout, (int)Cin,
-                           flip);
+    with_tile(tile, [&](auto m) { launch_weight_m<decltype(m)::value>(wgt, U, Cout, Cin, flip, st); });
     launch_input(tile, in, in_ld, tab, V, g.Tp, Cin, H, W, dilation, st, reflect);
     int rc;
     if (x6) {
@@ -1214,17 +1023,11 @@ static int winograd_conv(const WinoCall& c) {
     }
     if (rc) return rc;
     if (epi == nullptr && stats != nullptr) {
-        if (tile == 6) launch_output_stats_m<6>(Mb, tab, bias, out, out_ld, g, Cout, stats, st);
-        else launch_output_stats_m<4>(Mb, tab, bias, out, out_ld, g, Cout, stats, st);
+        with_tile<4>(tile, [&](auto m) { launch_output_stats_m<decltype(m)::value>(Mb, tab, bias, out, out_ld, g, Cout, stats, st); });
     } else if (epi == nullptr && inf != nullptr) {
-        if (tile == 6) launch_output_infer_m<6>(Mb, tab, bias, out, out_ld, g, Cout, *inf, st);
-        else launch_output_infer_m<4>(Mb, tab, bias, out, out_ld, g, Cout, *inf, st);
+        with_tile<4>(tile, [&](auto m) { launch_output_infer_m<decltype(m)::value>(Mb, tab, bias, out, out_ld, g, Cout, *inf, st); });
     } else if (epi == nullptr) {
-        if (tile == 6) launch_output_m<6>(Mb, tab, bias, out, out_ld, g, Cout, st);
-        else if (tile == 4) launch_output_m<4>(Mb, tab, bias, out, out_ld, g, Cout, st);
-        else
-            hipLaunchKernelGGL(wino_output_kernel, dim3((unsigned)ceil_div(g.T * (Cout / 4), 256)), dim3(256), 0, st, Mb, tab, bias, out,
-                               out_ld, g.T, g.Tp, (int)Cout, (int)H, (int)W, (int)dilation);
+        with_tile(tile, [&](auto m) { launch_output_m<decltype(m)::value>(Mb, tab, bias, out, out_ld, g, Cout, st); });
     } else {
         WinoEpi ep;
         ep.add = epi->addend; ep.add_ld = epi->addend_ld;
@@ -1234,11 +1037,7 @@ static int winograd_conv(const WinoCall& c) {
         ep.relu_ab = epi->relu_ab; ep.mean = epi->mean; ep.invstd = epi->invstd; ep.partials = epi->partials;
         const int64_t G = ceil_div(N * H * W, 128);
         const int tpb = (int)ceil_div(g.T, G);
-        if (tile == 6) launch_output_epi2_m<6>(Mb, tab, out, out_ld, g, Cout, G, tpb, ep, st);
-        else if (tile == 4) launch_output_epi2_m<4>(Mb, tab, out, out_ld, g, Cout, G, tpb, ep, st);
-        else
-            hipLaunchKernelGGL(wino_output_epi_kernel, dim3((unsigned)G, (unsigned)ceil_div(Cout, 256)), dim3(256), 0, st, Mb, tab, out,
-                               out_ld, g.T, g.Tp, (int)Cout, (int)H, (int)W, (int)dilation, tpb, ep);
+        with_tile(tile, [&](auto m) { launch_output_epi2_m<decltype(m)::value>(Mb, tab, out, out_ld, g, Cout, G, tpb, ep, st); });
     }
     return launch_status(x6 ? (reflect ? "diga_conv_winograd_bf16x6_opts" : "diga_conv2d_winograd_bf16x6") : "diga_conv2d_winograd_f32");
 }
@@ -1375,18 +1174,11 @@ static int winograd_wgrad(const WinoWgradCall& c) {
         hipLaunchKernelGGL(wino_tiles_kernel, dim3((unsigned)ceil_div(g.Tp, 256)), dim3(256), 0, st, reinterpret_cast<int4*>(ws + l.tab), g);
     if (v_kept == nullptr)
         launch_input(tile, x, x_ld, tab, reinterpret_cast<float*>(ws + l.V), g.Tp, Cin, H, W, dilation, st);
-    if (tile == 6) launch_dy_m<6>(dy, dy_ld, tab, Z, g, Cout, st);
-    else if (tile == 4) launch_dy_m<4>(dy, dy_ld, tab, Z, g, Cout, st);
-    else
-        hipLaunchKernelGGL(wino_dy_kernel, dim3((unsigned)ceil_div(g.Tp * (Cout / 4), 256)), dim3(256), 0, st, dy, dy_ld, tab, Z, g.Tp,
-                           (int)Cout, (int)H, (int)W, (int)dilation);
+    with_tile(tile, [&](auto m) { launch_dy_m<decltype(m)::value>(dy, dy_ld, tab, Z, g, Cout, st); });
     int rc = x6 ? wgrad_batched_bf16x6(Z, V, dU, slab, g.Tp, products(tile), Cout, Cin, st)
                 : wgrad_batched_f32_dma(Z, V, dU, slab, g.Tp, products(tile), Cout, Cin, st);
     if (rc) return rc;
-    if (tile == 6) launch_dw_m<6>(dU, dw, Cout, Cin, st);
-    else if (tile == 4) launch_dw_m<4>(dU, dw, Cout, Cin, st);
-    else
-        hipLaunchKernelGGL(wino_dw_kernel, dim3((unsigned)ceil_div(Cout * (Cin / 4), 256)), dim3(256), 0, st, dU, dw, (int)Cout, (int)Cin);
+    with_tile(tile, [&](auto m) { launch_dw_m<decltype(m)::value>(dU, dw, Cout, Cin, st); });
     return launch_status(x6 ? "diga_conv2d_wgrad_winograd_bf16x6" : "diga_conv2d_wgrad_winograd_f32");
 }
 

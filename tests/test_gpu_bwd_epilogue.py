@@ -71,7 +71,7 @@ for _fam, _k1, _k2 in (("bf16x3", "conv_fwd_x3w_kernel<1,false,true>", "conv_fwd
         for _mn, _nhw in (("m297", M297), ("m400", M400)):
             SHAPES.append(_sh(_fam, f"1x1_{_mn}_c{_cout}", _nhw, 32, _cout, 1, 1, _kern))
             SHAPES.append(_sh(_fam, f"3x3d2_{_mn}_c{_cout}", _nhw, 32, _cout, 3, 2, _kern))
-for _tile, _kern in ((2, "wino_output_epi_kernel"), (4, "winoM_output_epi2_kernel<4>"), (6, "winoM_output_epi2_kernel<6>")):
+for _tile, _kern in ((2, "winoM_output_epi2_kernel<2>"), (4, "winoM_output_epi2_kernel<4>"), (6, "winoM_output_epi2_kernel<6>")):
     for _cout in (96, 320):                                             # 320: a second 256-channel block with 64 valid channels
         SHAPES.append(_sh("wino", f"t{_tile}_d1_m286_c{_cout}", (2, 13, 11), 32, _cout, 3, 1, _kern, tile=_tile))
         SHAPES.append(_sh("wino", f"t{_tile}_d2_m323_c{_cout}", (1, 17, 19), 32, _cout, 3, 2, _kern, tile=_tile))   # sub-images < a tile
@@ -120,7 +120,7 @@ def _kernel_with_epilogue(s):
     if s.family == "twin":                                              # conv2d_twin
         return f"conv_fwd_x3t8_kernel<{tn},true>"
     if s.family == "wino":                                              # winograd_conv
-        return "wino_output_epi_kernel" if s.tile == 2 else f"winoM_output_epi2_kernel<{s.tile}>"
+        return f"winoM_output_epi2_kernel<{s.tile}>"
     return f"conv_fwd_x6_kernel<{tn}> ({'taps' if s.family == 'x6taps' else 'pointwise, loader'})"
 
 
