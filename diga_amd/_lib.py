@@ -149,6 +149,11 @@ SIGNATURES = {
     "diga_maxpool3x3s2_fwd": (INT, [P, P, P, I64, I64, I64, I64, I64, I64, P]),
     "diga_maxpool3x3s2_bwd": (INT, [P, P, P, I64, I64, I64, I64, I64, I64, P]),
     "diga_color_aug_view": (INT, [P, P, P, P, I64, I64, I64, F32, P, P, P]),
+    "diga_ocr_workspace_bytes": (SZ, [I64, I64, I64, I64]),
+    "diga_ocr_region_fwd": (INT, [P, I64, P, I64, P, P, I64, I64, I64, I64, P, SZ, P]),
+    "diga_ocr_region_bwd": (INT, [P, I64, P, I64, P, P, P, P, I64, P, I64, I64, I64, I64, I64, P]),
+    "diga_ocr_attend_fwd": (INT, [P, I64, P, P, P, I64, P, I64, I64, I64, I64, I64, F32, P]),
+    "diga_ocr_attend_bwd": (INT, [P, I64, P, P, P, P, I64, P, I64, P, P, I64, I64, I64, I64, I64, F32, P, SZ, P]),
     # ---- include/diga_mit.h
     "diga_mit_gemm_nt": (INT, [P, I64, P, I64, P, P, I64, INT, P, I64, P, I64, INT, F32, I64, I64, I64, P]),
     "diga_mit_gemm_tn_workspace_bytes": (SZ, [I64, I64, I64]),

@@ -66,7 +66,7 @@ class _BnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var, training, relu, momentum, eps,
-                partials=None, twin_out=False, dx_twin=False, box=None, res_box=None, res_ab=None, defer_apply=None):
+                partials=None, twin_out=False, dx_twin=False, box=None, res_box=None, res_ab=None, defer_apply=None, out=None):
         _lib.require_gpu(x)
         xn = nhwc(x.detach())
         n, h, w, c = xn.shape
@@ -80,6 +80,14 @@ class _BnFn(torch.autograd.Function):
         if res_ab is not None and not (relu and residual is not None and not twin_out):
             raise RuntimeError("DigaBatchNorm2d: residual coefficients need relu and a residual")
         y = None if defer_apply is not None else torch.empty_like(xn)
+        ld_y = c
+        if out is not None:
+            # a channel slice of a wider NHWC buffer to write into (the OCR head's concat buffer): the plain forms only
+            ld_y = rows_ld(out)
+            if (ld_y is None or tuple(out.shape) != tuple(xn.shape) or defer_apply is not None or twin_out or box is not None
+                    or res_ab is not None or (partials is not None and training and isinstance(partials[1], tuple))):
+                raise ValueError("BatchNorm output slice: a channel slice of a contiguous NHWC tensor, on the plain forward only")
+            y = out
         save_mean = torch.empty(c, dtype=torch.float32, device=xn.device)
         save_invstd = torch.empty_like(save_mean)
         # ReLU without residual: the backward re-derives the mask from x and the forward coefficients (no y read)
@@ -107,14 +115,14 @@ class _BnFn(torch.autograd.Function):
                       _lib.stream())
         elif partials is not None and training:
             # the producing conv already reduced its output tile by tile: finalise + apply only
-            _lib.call("diga_bn_fwd_partials", _lib.ptr(xn), c, _lib.ptr(y), c, _lib.ptr(rn), c, _lib.ptr(weight),
+            _lib.call("diga_bn_fwd_partials", _lib.ptr(xn), c, _lib.ptr(y), ld_y, _lib.ptr(rn), c, _lib.ptr(weight),
                       _lib.ptr(bias), _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(save_mean),
                       _lib.ptr(save_invstd), _lib.ptr(save_ab), m, c, 1 if relu else 0, 1 if twin_out else 0,
                       _lib.ptr(bits),
                       float(momentum), float(eps), _lib.ptr(partials[0]), int(partials[1]), _lib.ptr(ws), ws.numel(),
                       _lib.stream())
         else:
-            _lib.call("diga_bn_fwd", _lib.ptr(xn), c, _lib.ptr(y), c, _lib.ptr(rn), c, _lib.ptr(weight), _lib.ptr(bias),
+            _lib.call("diga_bn_fwd", _lib.ptr(xn), c, _lib.ptr(y), ld_y, _lib.ptr(rn), c, _lib.ptr(weight), _lib.ptr(bias),
                       _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(save_mean), _lib.ptr(save_invstd),
                       _lib.ptr(save_ab), m, c, 1 if training else 0, 1 if relu else 0, 1 if twin_out else 0,
                       _lib.ptr(bits),
@@ -154,7 +162,7 @@ class _BnFn(torch.autograd.Function):
                       _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(dx), c, _lib.ptr(dgamma), _lib.ptr(dbeta), m, c,
                       1 if training else 0, _lib.ptr(ws), ws.numel(), _lib.stream())
             return (dx.permute(0, 3, 1, 2), None, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None,
-                    None, None, None, None, None, None, None, None, None, None, None, None, None)
+                    None, None, None, None, None, None, None, None, None, None, None, None, None, None)
         pre = ctx.box.pop("premasked", None) if ctx.box is not None else None
         # (same buffer AND untouched since the conv wrote it: autograd sums a second gradient into a NEW tensor while the
         #  box holds a reference to this one; the version check also catches an in-place accumulation)
@@ -178,7 +186,7 @@ class _BnFn(torch.autograd.Function):
             ctx.res_box["dres"] = dres
             dres = None
         return (dx.permute(0, 3, 1, 2), None if dres is None else dres.permute(0, 3, 1, 2),
-                dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, None)
+                dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 def eval_coefficients(bn):
@@ -250,14 +258,15 @@ class DigaTrainableBatchNorm2d(DigaBatchNorm2d):
     (G5/model/networks/segformer_head.py:63-68, norm_cfg=dict(type='BN', requires_grad=True)).  Same forward kernels as the frozen
     BatchNorm of the DeepLab path; the backward is diga_bn_bwd_affine (the input gradient's two column sums are d gamma, d beta)."""
 
-    def forward(self, x, relu=False):
+    def forward(self, x, relu=False, out=None):
+        """out: an [N,H,W,C] channel slice of a contiguous NHWC buffer to write the result into (norm.alias_slice), else None."""
         training = self.training or self.running_mean is None
         if getattr(self, "_nbt_external", False):
             self._nbt_external = False                # (bump_batches_tracked counted this call)
         elif self.training and self.num_batches_tracked is not None:
             self.num_batches_tracked.add_(1)
         return _BnFn.apply(x, None, self.weight, self.bias, self.running_mean, self.running_var, training, relu, self.momentum, self.eps,
-                           getattr(x, "_diga_bn_partials", None), False, False, None, None)
+                           getattr(x, "_diga_bn_partials", None), False, False, None, None, None, None, out)
 
 
 def bump_batches_tracked(model):

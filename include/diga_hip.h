@@ -879,6 +879,44 @@ int diga_color_aug_view(const float* x, float* out, const float* params, const i
                         int64_t W, float beta, const float* mean_host, const float* std_host, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Object-contextual representations (csrc/ocr.hip): the two attention-shaped operations of the OCR head
+ * (semi-supervised_segmentation/model/networks/ocrnet_module.py:24-44, 77-95, 231), K <= 32 "tokens" against a long pixel axis P.
+ * Exact fp32 whatever the convolution arithmetic is; no floating-point atomics: sums over pixels are per-block partials (blocks of
+ * 256 pixels) in `workspace`, added in block order by a second kernel -- two runs give the same bits.  No profiling tag.
+ *
+ * Common rules, all checked before anything touches a device (DIGA_EINVAL and a diga_last_error_string otherwise, a workspace
+ * smaller than diga_ocr_workspace_bytes included): pointers non-null; tensors with a channel axis (x, dx, region, d_region, q,
+ * dq, key, val, out, d_out, d_key, d_val, stat, workspace) 16-byte aligned, the K-wide ones (s, ds, attn) 4-byte aligned; pitches
+ * (floats between consecutive pixels) >= the row and, on the channel tensors, % 4 == 0; 1 <= K <= 32; channel counts % 4 == 0 and
+ * <= 1024; 1 <= N <= 65535; P >= 1.
+ *
+ * diga_ocr_workspace_bytes(N, P, K, C): C = the widest channel count of the call (region: C; attend_bwd: max(D, Dv)).  Monotone in
+ *   every argument; 0 for a shape the entry points refuse.
+ * diga_ocr_region_fwd: x [N][P][ld_x] (C used), s [N][P][ld_s] (K used) logits.  region [N][K][C] = sum_p softmax_p(s[n, :, k])[p]
+ *   x[n, p, :], online: every block takes the maximum of its own 256 pixels, the reduce kernel rescales; accumulated, kept as partials
+ *   and reduced in float64.  stat, N * K * (C + 2) floats for the backward pass: [N][K][C] what rounding the sum to fp32 `region`
+ *   dropped (region + that = sum e x / sum e, normalised in float64, to ~2^-48), then [N][K][2] = (maximum, 1 / sum of exp(s - maximum)).  x and s are read once.
+ * diga_ocr_region_bwd: with w = exp(s - max) / sum, g[p, k] = <d_region[k], x[p]>, dot[k] = <d_region[k], region[k]>:
+ *   ds[p, k] = w (g - dot[k]), dx[p, :] = sum_k w[p, k] d_region[k, :] (written, not accumulated).  One pass over the pixels; dot and
+ *   g - dot in float64 on region + its low-order part, so that sum_p ds[p, k] vanishes as far as a softmax backward's does.
+ * diga_ocr_attend_fwd: q [N][P][ld_q] (D used), key [N][K][D], val [N][K][Dv] dense.  attn [N][P][K] = softmax_k(scale <q, key_k>)
+ *   (nullable: not written), out [N][P][ld_out] (Dv used) = attn val.  (K * (D + Dv) + 64) * 4 bytes must fit the 160 KB of LDS.
+ * diga_ocr_attend_bwd: dA = d_out val^T, dl = attn o (dA - sum_k attn dA); dq = scale dl key; d_key [N][K][D] = scale sum_p dl^T q,
+ *   d_val [N][K][Dv] = sum_p attn^T d_out through the workspace partials (which also hold dl, [N][P][K]).
+ * ---------------------------------------------------------------------------------- */
+size_t diga_ocr_workspace_bytes(int64_t N, int64_t P, int64_t K, int64_t C);
+int diga_ocr_region_fwd(const float* x, int64_t ld_x, const float* s, int64_t ld_s, float* region, float* stat, int64_t N, int64_t P,
+                        int64_t K, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+int diga_ocr_region_bwd(const float* x, int64_t ld_x, const float* s, int64_t ld_s, const float* stat, const float* region,
+                        const float* d_region, float* dx, int64_t ld_dx, float* ds, int64_t ld_ds, int64_t N, int64_t P, int64_t K,
+                        int64_t C, void* stream);
+int diga_ocr_attend_fwd(const float* q, int64_t ld_q, const float* key, const float* val, float* out, int64_t ld_out, float* attn,
+                        int64_t N, int64_t P, int64_t K, int64_t D, int64_t Dv, float scale, void* stream);
+int diga_ocr_attend_bwd(const float* q, int64_t ld_q, const float* key, const float* val, const float* attn, const float* d_out,
+                        int64_t ld_do, float* dq, int64_t ld_dq, float* d_key, float* d_val, int64_t N, int64_t P, int64_t K,
+                        int64_t D, int64_t Dv, float scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Kernel-family timing (bench.py's roofline leg): when enabled, every entry point brackets its
  * launches with HIP events recorded on the launch stream.  Not for production steps.
  * ---------------------------------------------------------------------------------- */

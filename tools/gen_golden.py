@@ -1413,7 +1413,104 @@ def gen_ohem():
     save("ohem", **out)
 
 
-ALL = dict(trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
+# ------------------------------------------------------------------ G-ocr-head (OCR head of the semi-supervised tree)
+OCR_REF = os.path.join(os.path.dirname(os.path.dirname(REF)), "semi-supervised_segmentation", "model", "networks", "ocrnet_module.py")
+OCR_CFG = {"OCRNET_MODEL": {"RAW_IN_CHANNELS": 48, "PIXEL_REP_CHANNELS": 64, "KEY_CHANNELS": 32, "NUM_CLASSES": 19}}
+
+
+def _import_reference_ocrnet():
+    """By file path: the name `model` on sys.path is the GTA5 tree's, and the file imports torch only."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("ref_ocrnet_module", OCR_REF)
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def _ocr_half_grid(t):
+    """Values on the float16 grid: stored at 2 bytes, exact in fp32 and fp64 alike."""
+    return t.half().float()
+
+
+def _ocr_state(ref, g):
+    """Seeded state dict: conv weights at 1.5 x the fan-in scale (ReLUs on both sides), non-trivial BatchNorm affine pairs and
+    running statistics, all on the float16 grid."""
+    sd = {}
+    for k, v in ref.OCRNet(OCR_CFG).state_dict().items():
+        if k.endswith("num_batches_tracked"):
+            sd[k] = torch.tensor(3)
+        elif k.endswith("running_var"):
+            sd[k] = _ocr_half_grid(1.0 + 0.5 * torch.rand(v.shape, generator=g))
+        elif k.endswith("running_mean"):
+            sd[k] = _ocr_half_grid(0.2 * torch.randn(v.shape, generator=g))
+        elif v.dim() == 4:
+            sd[k] = _ocr_half_grid(torch.randn(v.shape, generator=g) * (1.5 / (v.shape[1] * v.shape[2] * v.shape[3]) ** 0.5))
+        elif k.endswith("weight"):
+            sd[k] = _ocr_half_grid(1.0 + 0.2 * torch.randn(v.shape, generator=g))        # BatchNorm gamma
+        else:
+            sd[k] = _ocr_half_grid(0.2 * torch.randn(v.shape, generator=g))              # conv / BatchNorm biases
+    return sd
+
+
+def _ocr_run(ref, sd, dtype, x, probes, x_eval):
+    """One train-mode step and one eval-mode pass of the reference class in `dtype`; every tensor of the capture by name."""
+    head = ref.OCRNet(OCR_CFG)
+    head.load_state_dict(sd)
+    head = head.to(dtype)
+    head.augmented_rep[3].p = 0.0                                # Dropout2d off: its draws are not part of the pin
+    head.train()
+    xin = x.to(dtype).requires_grad_()
+    soft, seg, aug = head(xin)
+    ((soft * probes[0].to(dtype)).sum() + (seg * probes[1].to(dtype)).sum()).backward()
+    res = {"soft": soft, "seg": seg, "aug": aug, "dx": xin.grad}
+    for k, p in head.named_parameters():
+        res["g_" + k.replace(".", "_")] = p.grad
+    for k, b in head.named_buffers():
+        if not k.endswith("num_batches_tracked"):
+            res["b_" + k.replace(".", "_")] = b.clone()
+    nbt = {k: int(b) for k, b in head.named_buffers() if k.endswith("num_batches_tracked")}
+    head.eval()
+    with torch.no_grad():
+        soft_e, seg_e, aug_e = head(x_eval.to(dtype))
+    res.update(soft_eval=soft_e, seg_eval=seg_e, aug_eval=aug_e)
+    return {k: v.detach().double() for k, v in res.items()}, nbt
+
+
+def gen_ocr_head():
+    ref = _import_reference_ocrnet()
+    g = synth.gen(2301)
+    sd = _ocr_state(ref, g)
+    x = _ocr_half_grid(torch.randn((2, 48, 13, 11), generator=g))
+    probes = [_ocr_half_grid(torch.randn((2, 19, 13, 11), generator=g)) for _ in range(2)]
+    x_eval = _ocr_half_grid(torch.randn((1, 48, 9, 14), generator=g))
+    r64, nbt = _ocr_run(ref, sd, torch.float64, x, probes, x_eval)
+    r32, nbt32 = _ocr_run(ref, sd, torch.float32, x, probes, x_eval)
+    assert nbt == nbt32 and set(nbt.values()) == {4}
+    res = {"keys": np.array(list(sd.keys())), "x": x.half(), "probe_soft": probes[0].half(), "probe_seg": probes[1].half(),
+           "x_eval": x_eval.half(), "nbt": np.array(4)}
+    for k, v in sd.items():
+        res["w_" + k.replace(".", "_")] = v if k.endswith("num_batches_tracked") else v.half()
+    # a conv bias in front of a train-mode BatchNorm has no gradient: float64 leaves 1e-14 of rounding there, so "of scale" means
+    # the scale of the sum it is made of -- the gradient of that BatchNorm's own bias
+    vanishing = {"g_pixel_representations_0_bias": "g_pixel_representations_1_bias",
+                 "g_soft_object_regions_0_bias": "g_soft_object_regions_1_bias"}
+    for k, v in r64.items():
+        scale = float(v.abs().max())
+        if k in vanishing:
+            assert scale < 1e-10 * float(r64[vanishing[k]].abs().max())
+            scale = float(r64[vanishing[k]].abs().max())
+        err = float((r32[k] - v).abs().max()) / scale
+        res[k] = v
+        res["scale_" + k] = np.array(scale)
+        res["err32_" + k] = np.array(err)
+        # the fp32 run of the reference itself never needs assert_mostly_close's cap at the mode-0 bound (4 x its own error)
+        assert not bool(((r32[k] - v).abs() > 4.0 * err * scale).any()), k
+        print(f"  {k:48s} scale {scale:9.3e}  err32 {err:.2e}")
+    save("ocr_head", **res)
+    assert os.path.getsize(os.path.join(OUT, "ocr_head.npz")) < 1000000
+
+
+ALL = dict(ocr_head=gen_ocr_head, trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
            classmix=gen_classmix, centroid=gen_centroid, meanvec=gen_meanvec, aspp=gen_aspp,
            model=gen_model, step=gen_step, selftrain=gen_selftrain, translator=gen_translator, miou=gen_miou, valmiou=gen_valmiou)
 
