@@ -73,6 +73,7 @@ SIGNATURES = {
     "diga_conv2d_wgrad_twin_workspace_bytes": (SZ, [I64] * 7),
     "diga_conv2d_wgrad_twin": (INT, [P, P, P, P, SZ] + [I64] * 15 + [P]),
     "diga_weight_transpose": (INT, [P, P, I64, I64, I64, P]),
+    "diga_dgrad_strided_f32": (INT, [P, I64, P, P] + [I64] * 14 + [P]),
     "diga_make_triplet": (INT, [P, I64, P, I64, I64, P]),
     "diga_split_bf16x6_image_bytes": (SZ, [I64, I64, I64]),
     "diga_split_bf16x6_image": (INT, [P, P, I64, I64, I64, P]),

@@ -189,7 +189,8 @@ flop_log = None
 # "winograd" / "winograd/x6" (the Winograd path with its products on bf16x6, config.x6_winograd); "f32+bn" / "winograd+bn": a forward with the eval-mode BatchNorm behind it
 # folded into its epilogue (config.fold_eval_bn); "bf16x6+bn" / "bf16x6/ls+bn" / "winograd/x6+bn": the same on the bf16x6 kernels
 # (config.fold_eval_bn_x6); "bf16x6/taps" / "bf16x6/taps+bn": a multi-tap call on the bf16x6 kernels (config.x6_taps);
-# "bf16x6/ls/fit" / "bf16x6/taps/fit" (wgrad only): the loader-form weight gradient on a narrow tile (config.x6_wgrad_tile = "fit")
+# "bf16x6/ls/fit" / "bf16x6/taps/fit" (wgrad only): the loader-form weight gradient on a narrow tile (config.x6_wgrad_tile = "fit");
+# "f32/s2" (dgrad only): the phase-split backward-data of a stride-2 multi-tap conv (diga_dgrad_strided_f32; exact fp32 in every mode)
 path_log = None
 
 
@@ -197,6 +198,13 @@ def _log_path(tag, arith):
     if path_log is not None:
         key = (tag if isinstance(tag, str) else ("dgrad" if tag == _TAG_BWD_DATA else "fwd"), arith)
         path_log[key] = path_log.get(key, 0) + 1
+
+
+def _strided_dgrad_ok(r, s, stride, padding, dilation):
+    """True where a strided conv's input gradient runs on diga_dgrad_strided_f32 (the phase-split kernel, path_log arithmetic "f32/s2"):
+    stride (2, 2), dilation (1, 1), more than one tap, padding smaller than the kernel.  A strided 1x1 keeps its GEMM + scatter route."""
+    return (tuple(stride) == (2, 2) and tuple(dilation) == (1, 1) and r * s > 1
+            and 0 <= padding[0] < r and 0 <= padding[1] < s)
 
 
 def _log_flops(name, direct, executed):
@@ -980,9 +988,24 @@ class _Conv2dFn(torch.autograd.Function):
                 _conv_launch(gyp, wt, None, dxn, (1, 1), (padding[0], padding[1]), (-dilation[0], -dilation[1]),
                              _TAG_BWD_DATA, None, dy_box if (((use_tw or ctx.dy_is_twin) and cp > 64) or dm == 2) else None,
                              must_twin=ctx.dy_is_twin, epi=epi)
+            elif _strided_dgrad_ok(r, s, stride, padding, dilation):
+                # stride 2 with more than one tap: the four phases of dx in one launch, exact fp32 under every conv_math (no split
+                # form of this kernel exists).  The forward claims a bn_box and keeps a chain enabled for stride 1 only, so neither
+                # can be live here; a twin dy would be bytes this kernel cannot read.  All three are refused rather than ignored.
+                if ctx.dy_is_twin or ctx.bn_box is not None or (ctx.chain is not None and not ctx.chain.get("disabled")):
+                    raise RuntimeError("DigaConv2d: backward-data of a stride-2 multi-tap conv takes no twin gradient (twin_grad), no "
+                                       "BatchNorm-backward epilogue (bn_box) and no gradient chain")
+                dxn = torch.empty((n, hi, wi, cp), dtype=torch.float32, device=w.device)
+                _lib.call("diga_dgrad_strided_f32", _lib.ptr(gyp), kp, _lib.ptr(wt), _lib.ptr(dxn), cp, n, hi, wi, cp, ho, wo, kp, r, s,
+                          stride[0], stride[1], padding[0], padding[1], st)
+                _log_path(_TAG_BWD_DATA, "f32/s2")
+                direct = 2.0 * n * ho * wo * kp * r * s * cp
+                _log_flops("conv_bwd_data", direct, direct)
             else:
                 if (r, s) != (1, 1) or padding != (0, 0):
-                    raise NotImplementedError("backward-data of strided convs is only needed (and built) for 1x1")
+                    raise NotImplementedError("backward-data of strided convs is built for 1x1 without padding (any stride) and for stride "
+                                              f"(2, 2), dilation (1, 1), padding < kernel; got kernel {(r, s)}, stride {tuple(stride)}, "
+                                              f"padding {tuple(padding)}, dilation {tuple(dilation)}")
                 dense = torch.empty((n, ho, wo, cp), dtype=torch.float32, device=w.device)
                 _conv_launch(gyp, wt, None, dense, (1, 1), (0, 0), (1, 1), _TAG_BWD_DATA, twin_box=dy_box if dm == 2 else None)
                 dxn = torch.zeros((n, hi, wi, cp), dtype=torch.float32, device=w.device)

@@ -723,6 +723,23 @@ int diga_im2col_nchw(const float* x, float* out, int64_t N, int64_t C, int64_t H
 /* w [K][RS][C] -> wt [C][RS][K] (weights for backward-data). */
 int diga_weight_transpose(const float* w, float* wt, int64_t K, int64_t RS, int64_t C, void* stream);
 
+/* Backward-data of a stride-2 convolution (dilation 1, zero padding), exact fp32 under every diga_set_conv_math mode:
+ *   dx[n, y, x, c] = sum_{r,s,k} dy[n, (y + pad_y - r)/2, (x + pad_x - s)/2, k] * wgt_t[c][r][s][k]
+ * over the taps whose two quotients are exact and inside [0, Ho) x [0, Wo).  Hi, Wi, Cin, Ho, Wo, Cout, R, S name the FORWARD
+ * convolution (x [N][Hi][Wi][Cin] -> y [N][Ho][Wo][Cout]); dy is [N][Ho][Wo][dy_ld], dx [N][Hi][Wi][dx_ld], wgt_t the
+ * [Cin][R][S][Cout] transpose (diga_weight_transpose).  dx is split into its four phases (y & 1, x & 1); each is a stride-1
+ * correlation of dy with the taps of its parity, read in place from wgt_t, so the call multiplies what the forward multiplies
+ * (a quarter of the zero-insertion form) in one launch.  Every element of dx[.., :Cin] is written -- zeros where a phase has no
+ * tap (R or S = 1, or 2 with one parity of the padding) and where no tap reaches (e.g. Hi = 8, R = 3, pad 0: row 7) -- so dx
+ * may be uninitialised; channels Cin .. dx_ld are not touched.  Fixed summation order (tap-major, channel-minor): deterministic.
+ * Rules, all DIGA_EINVAL and checked before the launch: non-null, 16-byte aligned pointers; dy_ld >= Cout, dx_ld >= Cin, both
+ * % 4 == 0; Cout % 32 == 0, Cin % 4 == 0; stride_y == stride_x == 2; 1 <= R, S <= 7; 0 <= pad_y < R, 0 <= pad_x < S;
+ * Ho == (Hi + 2 pad_y - R) / 2 + 1 >= 1 and Wo likewise; every phase's row count and all pixel coordinates below 2^30.
+ * N == 0: DIGA_OK without a launch.  Profiling tag: DIGA_PROF_CONV_BWD_DATA. */
+int diga_dgrad_strided_f32(const float* dy, int64_t dy_ld, const float* wgt_t /* [Cin][R][S][Cout] */, float* dx, int64_t dx_ld,
+                           int64_t N, int64_t Hi, int64_t Wi, int64_t Cin, int64_t Ho, int64_t Wo, int64_t Cout, int64_t R, int64_t S,
+                           int64_t stride_y, int64_t stride_x, int64_t pad_y, int64_t pad_x, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Normalisation / pooling on NHWC fp32 (nn.BatchNorm2d with frozen affine in train mode, nn.GroupNorm(32),
  * SEBlock, nn.Dropout2d, nn.MaxPool2d(3,2,1,ceil_mode) of G5/model/seg_model_noaux.py:57-101,122-137,

@@ -1510,7 +1510,87 @@ def gen_ocr_head():
     assert os.path.getsize(os.path.join(OUT, "ocr_head.npz")) < 1000000
 
 
-ALL = dict(ocr_head=gen_ocr_head, trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
+# ------------------------------------------------------------------ G-hrnet-fuse-down (the downward path of HRNet's exchange unit)
+HRNET_REF = os.path.join(os.path.dirname(OCR_REF), "hrnet_module.py")
+
+
+def _import_reference_hrnet():
+    """By file path, as the OCR head: the file imports torch only."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("ref_hrnet_module", HRNET_REF)
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def _hrnet_fuse_down(ref):
+    """fuse_layers[2][0] of a three-branch exchange unit: conv 3x3/2 32->32, BN, ReLU, conv 3x3/2 32->128, BN."""
+    unit = ref.HighResolutionModule(3, ref.BasicBlock, [1, 1, 1], [32, 64, 128], [32, 64, 128], "SUM")
+    return unit.fuse_layers[2][0]
+
+
+def _hrnet_fuse_run(ref, sd, dtype, x, dy):
+    """One train-mode forward and backward of the reference's chain in `dtype`."""
+    chain = _hrnet_fuse_down(ref)
+    chain.load_state_dict(sd)
+    chain = chain.to(dtype).train()
+    xin = x.to(dtype).requires_grad_()
+    y = chain(xin)
+    y.backward(dy.to(dtype))
+    res = {"y": y, "dx": xin.grad}
+    for k, p in chain.named_parameters():
+        res["g_" + k.replace(".", "_")] = p.grad
+    for k, b in chain.named_buffers():
+        if not k.endswith("num_batches_tracked"):
+            res["b_" + k.replace(".", "_")] = b.clone()
+    return {k: v.detach().double() for k, v in res.items()}
+
+
+def gen_hrnet_fuse_down():
+    ref = _import_reference_hrnet()
+    # the first of ten seeds for which the reference's own fp32 run stays, on every element of every tensor, inside the bound the GPU
+    # test applies (4 x its max error against float64)
+    for seed in range(2400, 2410):
+        g = synth.gen(seed)
+        sd = {}
+        for k, v in _hrnet_fuse_down(ref).state_dict().items():
+            if k.endswith("num_batches_tracked"):
+                sd[k] = torch.tensor(3)
+            elif k.endswith("running_var"):
+                sd[k] = _ocr_half_grid(1.0 + 0.5 * torch.rand(v.shape, generator=g))
+            elif k.endswith("running_mean"):
+                sd[k] = _ocr_half_grid(0.2 * torch.randn(v.shape, generator=g))
+            elif v.dim() == 4:          # conv weights at 1.5 x the fan-in scale: activations of order 1 on both sides of the ReLU
+                sd[k] = _ocr_half_grid(torch.randn(v.shape, generator=g) * (1.5 / (v.shape[1] * v.shape[2] * v.shape[3]) ** 0.5))
+            elif k.endswith("weight"):
+                sd[k] = _ocr_half_grid(1.0 + 0.2 * torch.randn(v.shape, generator=g))
+            else:
+                sd[k] = _ocr_half_grid(0.2 * torch.randn(v.shape, generator=g))
+        x = _ocr_half_grid(torch.randn((2, 32, 19, 17), generator=g))
+        dy = _ocr_half_grid(torch.randn((2, 128, 5, 5), generator=g))
+        r64 = _hrnet_fuse_run(ref, sd, torch.float64, x, dy)
+        r32 = _hrnet_fuse_run(ref, sd, torch.float32, x, dy)
+        res = {"keys": np.array(list(sd.keys())), "seed": np.array(seed), "x": x.half(), "dy": dy.half()}
+        for k, v in sd.items():
+            res["w_" + k.replace(".", "_")] = v if k.endswith("num_batches_tracked") else v.half()
+        inside = True
+        for k, v in r64.items():
+            scale = float(v.abs().max())
+            err = float((r32[k] - v).abs().max()) / scale
+            res[k] = v
+            res["scale_" + k] = np.array(scale)
+            res["err32_" + k] = np.array(err)
+            inside = inside and not bool(((r32[k] - v).abs() > 4.0 * err * scale).any())
+            print(f"  seed {seed} {k:24s} scale {scale:9.3e}  err32 {err:.2e}")
+        if inside:
+            break
+    else:
+        raise RuntimeError("no seed in the first ten keeps the reference's fp32 run inside 4 x its own error")
+    save("hrnet_fuse_down", **res)
+    assert os.path.getsize(os.path.join(OUT, "hrnet_fuse_down.npz")) < 1000000
+
+
+ALL = dict(hrnet_fuse_down=gen_hrnet_fuse_down, ocr_head=gen_ocr_head, trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
            classmix=gen_classmix, centroid=gen_centroid, meanvec=gen_meanvec, aspp=gen_aspp,
            model=gen_model, step=gen_step, selftrain=gen_selftrain, translator=gen_translator, miou=gen_miou, valmiou=gen_valmiou)
 
