@@ -1369,7 +1369,7 @@ __global__ __launch_bounds__(768, DIGA_FWD_DMA_MINW) void conv_fwd_dma_kernel(Co
     const int ksteps = ntaps * cchunks;
 
     if (loader) {
-        const int lw = wv - 8;                                   // A rows lw*64 + 8 j + (lane >> 3), B rows lw*32 + 8 c + (lane >> 3)
+        const int lw = __builtin_amdgcn_readfirstlane(wv) - 8;   // (through an SGPR) A rows lw*64 + 8 j + (lane >> 3), B rows lw*32 + 8 c + (lane >> 3)
         const unsigned char* in_b = reinterpret_cast<const unsigned char*>(a.in);
         const int lrow = lane >> 3;
         int pixbase[8], yx0[8];
@@ -2325,6 +2325,8 @@ __global__ __launch_bounds__(768, 3) void conv_wgrad_dma_kernel(WgradArgs a) {
     const int ksteps = p_end > p_begin ? (p_end - p_begin + kBK - 1) / kBK : 0;
 
     if (loader) {
+        // (lw stays a vector value HERE: through an SGPR, as in conv_fwd_dma_kernel and gemm_f32_persistent_kernel, the row addresses become
+        // scalar arithmetic and this kernel measured 12 % slower -- profiles/r25_f32_lean_loader.txt)
         const int lw = wv - 8;
         const unsigned char* dyb = reinterpret_cast<const unsigned char*>(a.dy) + ((int64_t)k0 + tap * a.dy_tap_stride) * 4;
         const unsigned char* xb = reinterpret_cast<const unsigned char*>(a.x) + ((int64_t)c0 + tap * a.x_tap_stride) * 4;
@@ -2603,15 +2605,19 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
     const int64_t rowb = g.a_ld * 4, wrowb = (int64_t)g.K * 4;
 
     if (loader) {
-        const int lw = wv - 8;
+        // (wave-uniform by construction; through an SGPR so that the LDS destinations and the row test below are scalar arithmetic:
+        // the loader's vector instructions share their SIMD's issue with two MFMA waves)
+        const int lw = __builtin_amdgcn_readfirstlane(wv) - 8;
         const int lrow = lane >> 3;
         const unsigned char* pa[8];
         const unsigned char* pb[4];
         int l_it = 0, l_cc = 0, issued = 0;
+        bool whole = false;                                      // all 64 rows of this wave's quarter exist: no zero source to choose per lane
         auto set_tile = [&](int it) {
             const int t = start + slot + nslots * it;
             const int tile_n = t % g.tiles_n, tile_m = t / g.tiles_n;
             const int row0 = tile_m * 256 + lw * 64 + lrow;
+            whole = tile_m * 256 + lw * 64 + 64 <= g.M;          // (uniform)
             const unsigned char* ab = reinterpret_cast<const unsigned char*>(g.A) + (int64_t)row0 * rowb;
             const unsigned char* wb = reinterpret_cast<const unsigned char*>(g.W + (g.wb_tiles > 0 ? (int64_t)(tile_m / g.wb_tiles) * g.wb_stride : 0)) +
                                       (int64_t)(tile_n * 128 + lw * 32 + lrow) * wrowb;
@@ -2623,11 +2629,18 @@ __global__ __launch_bounds__(768, 3) void gemm_f32_persistent_kernel(GemmArgs g)
         };
         auto issue = [&](int buf) {
             unsigned char* stage = smem_b + buf * STAGE;
+            if (whole) {                                         // (uniform branch) every tile but those of the last row tile
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const unsigned char* src = pa[j] != nullptr ? pa[j] + l_cc * 128 : g_zero16;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(stage + (lw * 64 + 8 * j) * 128), 16, 0, 0);
+                for (int j = 0; j < 8; ++j)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pa[j] + l_cc * 128),
+                                                     (__attribute__((address_space(3))) void*)(stage + (lw * 64 + 8 * j) * 128), 16, 0, 0);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const unsigned char* src = pa[j] != nullptr ? pa[j] + l_cc * 128 : g_zero16;
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                                     (__attribute__((address_space(3))) void*)(stage + (lw * 64 + 8 * j) * 128), 16, 0, 0);
+                }
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c)
