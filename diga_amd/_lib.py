@@ -113,6 +113,11 @@ SIGNATURES = {
     "diga_pyramid_sum_bwd": (INT, [P, I64, I64, P, I64, I64, I64, I64, P]),
     "diga_pyramid_sum_fwd3": (INT, [P, I64, I64, P, P, P, P, P, I64, I64, P]),
     "diga_pyramid_sum_bwd3": (INT, [P, I64, I64, P, P, P, I64, I64, P]),
+    "diga_pyramid_resize_fwd": (INT, [P, I64, I64, P, I64, I64, I64, I64, I64, P]),
+    "diga_pyramid_resize_bwd": (INT, [P, I64, I64, I64, P, I64, I64, I64, I64, P]),
+    "diga_dwconv3x3_f32": (INT, [P, I64, P, P, I64, I64, I64, I64, I64, I64, INT, P]),
+    "diga_dwconv3x3_wgrad_workspace_bytes": (SZ, [I64, I64, I64, I64]),
+    "diga_dwconv3x3_f32_wgrad": (INT, [P, I64, P, I64, P, P, SZ, I64, I64, I64, I64, I64, P]),
     "diga_bn_bwd_partials": (INT, [P, I64, P, I64, P, P, P, P, I64, I64, I64, INT, P, I64, P, SZ, P]),
     "diga_conv2d_nhwc_f32_epi": (INT, [P, P, P] + [I64] * 17 + [P, INT, P]),
     "diga_conv2d_winograd_workspace_bytes": (SZ, [I64] * 7),

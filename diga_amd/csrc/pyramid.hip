@@ -304,9 +304,112 @@ __global__ __launch_bounds__(256) void pyramid_sum_fwd3_kernel(float* __restrict
     }
 }
 
+
+// One resized map written into a channel slice of a wider fine buffer (the DAFormer head's concatenation, which that head does read:
+// its fusion is an ASPP, not a 1x1 conv that would commute with the resize): dst[.., 0:C] = resize(src), pitch dst_ld between fine
+// pixels, the other channels of the buffer untouched.  Taps, weights and order of pyramid_sum_fwd_kernel.
+__global__ __launch_bounds__(256) void pyramid_resize_fwd_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t dst_ld,
+                                                                 int h, int w, float sh, float sw, int H, int W, int C4, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c4 = (int)(idx % C4);
+    const int64_t pix = idx / C4;
+    const int x = (int)(pix % W);
+    const int64_t t = pix / W;
+    const int y = (int)(t % H);
+    const int64_t n = t / H;
+    const int C = C4 * 4;
+    if (h == H && w == W) {                        // equal grids: a copy of the bits (the weighted form would turn -0 into +0 and put a
+        *reinterpret_cast<float4*>(dst + pix * dst_ld + c4 * 4) = ld4(src + pix * C + c4 * 4);      // NaN beside an infinite neighbour)
+        return;
+    }
+    int y0, y1, x0, x1;
+    float ly, lx;
+    half_pixel_taps(y, sh, h, y0, y1, ly);
+    half_pixel_taps(x, sw, w, x0, x1, lx);
+    const float* base = src + (n * h * (int64_t)w) * C + c4 * 4;
+    const float4 v00 = ld4(base + ((int64_t)y0 * w + x0) * C), v01 = ld4(base + ((int64_t)y0 * w + x1) * C);
+    const float4 v10 = ld4(base + ((int64_t)y1 * w + x0) * C), v11 = ld4(base + ((int64_t)y1 * w + x1) * C);
+    const float hy0 = 1.f - ly, hx0 = 1.f - lx;
+    float4 o;
+    o.x = hy0 * (hx0 * v00.x + lx * v01.x) + ly * (hx0 * v10.x + lx * v11.x);
+    o.y = hy0 * (hx0 * v00.y + lx * v01.y) + ly * (hx0 * v10.y + lx * v11.y);
+    o.z = hy0 * (hx0 * v00.z + lx * v01.z) + ly * (hx0 * v10.z + lx * v11.z);
+    o.w = hy0 * (hx0 * v00.w + lx * v01.w) + ly * (hx0 * v10.w + lx * v11.w);
+    *reinterpret_cast<float4*>(dst + pix * dst_ld + c4 * 4) = o;
+}
+
+// Its exact adjoint: pyramid_sum_bwd_kernel's gather with a pitch on the fine gradient (a channel slice of the concatenation's gradient).
+__global__ __launch_bounds__(256) void pyramid_resize_bwd_kernel(const float* __restrict__ dout, int64_t dout_ld, float* __restrict__ ds, int H,
+                                                                 int W, int h, int w, float sh, float sw, int C4, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c4 = (int)(idx % C4);
+    const int64_t pix = idx / C4;
+    const int i = (int)(pix % w);
+    const int64_t t = pix / w;
+    const int j = (int)(t % h);
+    const int64_t n = t / h;
+    int ylo, yhi, xlo, xhi;
+    footprint(j, sh, H, ylo, yhi);
+    footprint(i, sw, W, xlo, xhi);
+    const float* base = dout + (n * H * (int64_t)W) * dout_ld + c4 * 4;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int y = ylo; y <= yhi; ++y) {
+        const float wy = tap_weight(y, sh, h, j);
+        if (wy == 0.f) continue;
+        float4 row = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int x = xlo; x <= xhi; ++x) {
+            const float wx = tap_weight(x, sw, w, i);
+            if (wx == 0.f) continue;
+            const float4 g = ld4(base + ((int64_t)y * W + x) * dout_ld);
+            row.x += wx * g.x, row.y += wx * g.y, row.z += wx * g.z, row.w += wx * g.w;
+        }
+        acc.x += wy * row.x, acc.y += wy * row.y, acc.z += wy * row.z, acc.w += wy * row.w;
+    }
+    *reinterpret_cast<float4*>(ds + idx * 4) = acc;
+}
+
 }  // namespace diga
 
 using namespace diga;
+
+extern "C" int diga_pyramid_resize_fwd(const float* src, int64_t h, int64_t w, float* dst, int64_t dst_ld, int64_t H, int64_t W, int64_t N,
+                                       int64_t C, void* stream) {
+    DIGA_REQUIRE(src && dst && N > 0 && H > 0 && W > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0, DIGA_EINVAL,
+                 "pyramid_resize_fwd: bad argument (C % 4 == 0)");
+    DIGA_REQUIRE(aligned16(src) && aligned16(dst), DIGA_EINVAL, "pyramid_resize_fwd: pointers must be 16-byte aligned");
+    DIGA_REQUIRE(dst_ld >= C && dst_ld % 4 == 0, DIGA_EINVAL, "pyramid_resize_fwd: bad dst_ld (>= C, %% 4 == 0)");
+    DIGA_REQUIRE(h <= H && w <= W, DIGA_EINVAL, "pyramid_resize_fwd: upsampling only (h=%lld w=%lld to H=%lld W=%lld)", (long long)h,
+                 (long long)w, (long long)H, (long long)W);
+    DIGA_REQUIRE(H < (1ll << 30) && W < (1ll << 30) && C < (1ll << 30), DIGA_EINVAL, "pyramid_resize_fwd: extent beyond 2^30");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof(DIGA_PROF_ELEMENTWISE, st, ((double)N * H * W + (double)N * h * w) * C * 4.0);
+    const int64_t total = N * H * W * (C / 4);
+    DIGA_REQUIRE(ceil_div(total, 256) < (1ll << 31), DIGA_EINVAL, "pyramid_resize_fwd: too many elements for one launch");
+    hipLaunchKernelGGL(pyramid_resize_fwd_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, src, dst, dst_ld, (int)h, (int)w,
+                       (float)h / (float)H, (float)w / (float)W, (int)H, (int)W, (int)(C / 4), total);
+    return launch_status("diga_pyramid_resize_fwd");
+}
+
+extern "C" int diga_pyramid_resize_bwd(const float* dout, int64_t dout_ld, int64_t H, int64_t W, float* ds, int64_t h, int64_t w, int64_t N,
+                                       int64_t C, void* stream) {
+    DIGA_REQUIRE(dout && ds && N > 0 && H > 0 && W > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0, DIGA_EINVAL,
+                 "pyramid_resize_bwd: bad argument (C % 4 == 0)");
+    DIGA_REQUIRE(aligned16(dout) && aligned16(ds), DIGA_EINVAL, "pyramid_resize_bwd: pointers must be 16-byte aligned");
+    DIGA_REQUIRE(dout_ld >= C && dout_ld % 4 == 0, DIGA_EINVAL, "pyramid_resize_bwd: bad dout_ld (>= C, %% 4 == 0)");
+    DIGA_REQUIRE(h <= H && w <= W, DIGA_EINVAL, "pyramid_resize_bwd: the adjoint of an upsampling only (h=%lld w=%lld from H=%lld W=%lld)",
+                 (long long)h, (long long)w, (long long)H, (long long)W);
+    DIGA_REQUIRE(H < (1ll << 30) && W < (1ll << 30) && C < (1ll << 30), DIGA_EINVAL, "pyramid_resize_bwd: extent beyond 2^30");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof(DIGA_PROF_ELEMENTWISE, st, ((double)N * H * W + (double)N * h * w) * C * 4.0);
+    const int64_t total = N * h * w * (C / 4);
+    DIGA_REQUIRE(ceil_div(total, 256) < (1ll << 31), DIGA_EINVAL, "pyramid_resize_bwd: too many elements for one launch");
+    hipLaunchKernelGGL(pyramid_resize_bwd_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, dout, dout_ld, ds, (int)H, (int)W,
+                       (int)h, (int)w, (float)h / (float)H, (float)w / (float)W, (int)(C / 4), total);
+    return launch_status("diga_pyramid_resize_bwd");
+}
+
 
 extern "C" int diga_pyramid_sum_fwd(float* dst, int64_t H, int64_t W, const float* bias, const float* s0, int64_t h0, int64_t w0,
                                     const float* s1, int64_t h1, int64_t w1, const float* s2, int64_t h2, int64_t w2, int64_t N,

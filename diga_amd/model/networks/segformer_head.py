@@ -232,3 +232,6 @@ class SegFormerHead(nn.Module):
         x = self.dropout(_c) if self.dropout is not None else _c
         x = self.linear_pred(x)
         return x, (self.raw_features(feats) if self.return_raw else _c)
+
+
+from diga_amd.model.networks.daformer_head import ASPPWrapper, DAFormerHead, DepthwiseSeparableConvModule  # noqa: E402,F401  (the reference keeps them in this file)

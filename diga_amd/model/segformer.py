@@ -12,6 +12,9 @@ head="segformer" (default): the SegFormer all-MLP head on all four stages, logit
 head="aspp": the reference's DeepLab classifier `Classifier_Module2` (seg_model_noaux.py:140-214) on the last stage only (512
 channels, stride 32, logits 24x24 for a 768x768 crop) -- the round-3 wiring, a much lighter workload than a SegFormer; kept for
 comparison (bench.py --c5-head aspp).
+head="daformer": the reference's `DAFormerHead` (segformer_head.py:167-307; diga_amd/model/networks/daformer_head.py) on all four
+stages: 256-channel embeddings, a separable ASPP over their 1024-channel concatenation, logits at 1/4 scale and a fused feature of 256
+channels -- the width of `Class_Features`' centroid bank.
 
 Everything downstream (upsample + CE + distillation block, EMA teacher, ClassMix, fused SGD, gradient all-reduce) is the
 DeepLab path's code unchanged, so `DigaTrainer` drives it as it drives `SegModel`.
@@ -27,6 +30,7 @@ if os.path.dirname(_pkg) not in sys.path:
     sys.path.append(os.path.dirname(_pkg))
 from diga_amd import _lib  # noqa: E402
 from diga_amd.model.networks import MixTransfomer as mit  # noqa: E402
+from diga_amd.model.networks.daformer_head import DAFormerHead  # noqa: E402
 from diga_amd.model.networks.segformer_head import SegFormerHead  # noqa: E402
 from diga_amd.model.seg_model_noaux import Classifier_Module2  # noqa: E402
 
@@ -34,8 +38,8 @@ from diga_amd.model.seg_model_noaux import Classifier_Module2  # noqa: E402
 class SegFormerStudent(nn.Module):
     def __init__(self, backbone="mit_b5", n_classes=19, drop_path_rate=None, head="segformer"):
         super().__init__()
-        if head not in ("segformer", "aspp"):
-            raise ValueError("SegFormerStudent: head is 'segformer' or 'aspp'")
+        if head not in ("segformer", "aspp", "daformer"):
+            raise ValueError("SegFormerStudent: head is 'segformer', 'aspp' or 'daformer'")
         self.n_classes = n_classes
         self.head_kind = head
         self.backbone = getattr(mit, backbone)()
@@ -43,6 +47,11 @@ class SegFormerStudent(nn.Module):
             self.backbone.reset_drop_path(drop_path_rate)
         if head == "aspp":
             self.final = Classifier_Module2(self.backbone.embed_dims[-1], [6, 12, 18, 24], [6, 12, 18, 24], n_classes)
+        elif head == "daformer":
+            self.final = DAFormerHead(in_channels=list(self.backbone.embed_dims), channels=256, feature_strides=[4, 8, 16, 32],
+                                      num_classes=n_classes, in_index=[0, 1, 2, 3], dropout_ratio=0.1, act_cfg=dict(type='ReLU'),
+                                      norm_cfg=dict(type='BN', requires_grad=True), align_corners=False)
+            self.final.init_weights()
         else:
             self.final = SegFormerHead(in_channels=list(self.backbone.embed_dims), channels=128, feature_strides=[4, 8, 16, 32],
                                        num_classes=n_classes, in_index=[0, 1, 2, 3], dropout_ratio=0.1, align_corners=False)
@@ -50,7 +59,8 @@ class SegFormerStudent(nn.Module):
 
     def forward(self, x):
         """x [N,3,H,W] -> (c2 [N,128,H/8,W/8], c4 [N,512,H/32,W/32], logits, feat): logits [N,19,H/4,W/4] and the fused feature
-        [N,768,H/4,W/4] with the SegFormer head; [N,19,H/32,W/32] and [N,256,H/32,W/32] with the ASPP head."""
+        [N,768,H/4,W/4] with the SegFormer head; [N,19,H/4,W/4] and [N,256,H/4,W/4] with the DAFormer head; [N,19,H/32,W/32] and
+        [N,256,H/32,W/32] with the ASPP head."""
         _lib.require_gpu(x)
         c1, c2, c3, c4 = self.backbone(x)
         if self.head_kind == "aspp":

@@ -875,6 +875,35 @@ int diga_pyramid_sum_fwd3(float* dst, int64_t H, int64_t W, const float* bias, c
                           float* stats, int64_t N, int64_t C, void* stream);
 int diga_pyramid_sum_bwd3(const float* dout, int64_t H, int64_t W, float* ds2, float* ds4, float* ds8, int64_t N, int64_t C, void* stream);
 
+/* One bilinearly resized map (align_corners=False, torch's half-pixel taps and tap order: the expressions of diga_pyramid_sum_fwd)
+ * written into the C channels that start at dst of every pixel of a wider fine buffer: dst[n, y, x, 0:C] = resize(src)[n, y, x, :],
+ * dst_ld floats between fine pixels (dst_ld >= C, % 4 == 0); nothing else of the buffer is written.  src [N,h,w,C] dense.  Upsampling
+ * only (h <= H, w <= W; h == H and w == W is a plain copy: the bits, signed zeros, infinities and NaNs included), else DIGA_EINVAL.  diga_pyramid_resize_bwd is its exact adjoint on a
+ * pitched fine gradient (dout_ld floats between fine pixels): a gather over every coarse pixel's footprint with the forward's weights
+ * recomputed, no atomics, deterministic; ds [N,h,w,C] dense, every element written.  C % 4 == 0, pointers 16-byte aligned. */
+int diga_pyramid_resize_fwd(const float* src, int64_t h, int64_t w, float* dst, int64_t dst_ld, int64_t H, int64_t W, int64_t N, int64_t C,
+                            void* stream);
+int diga_pyramid_resize_bwd(const float* dout, int64_t dout_ld, int64_t H, int64_t W, float* ds, int64_t h, int64_t w, int64_t N, int64_t C,
+                            void* stream);
+
+/* Depthwise 3x3 convolution, stride 1, padding = dilation, fp32 NHWC, pitched operands (csrc/dwconv.hip):
+ *   y[n,i,j,c] = sum_{r,s} w9[3r+s][c] * x[n, i+(r-1)d, j+(s-1)d, c], zeros outside the map; w9 is [9][C], tap-major.
+ * flip = 1 reads tap 8 - t in place of t: with x = dy that is the backward-data pass.  The nine products are added in tap order in one
+ * fmaf chain from 0, a tap outside the map as an exact 0.  Every element of the C channels of every pixel of y is written (pass
+ * uninitialised memory); columns C .. y_ld are not touched.  Exact fp32: no conv_math applies.
+ * Rules (DIGA_EINVAL with a message, before any launch): non-null 16-byte aligned pointers; C % 4 == 0; x_ld, y_ld >= C, % 4 == 0 and
+ * below 2^30; dilation >= 1; flip 0 or 1; x and y must not alias (two disjoint column windows of one matrix do not); extents below
+ * 2^30 and N * H * W * ld of either operand at most 2^44.
+ * N == 0: DIGA_OK without a launch.  Profiling tag: DIGA_PROF_ELEMENTWISE (work = 8 bytes per element). */
+int diga_dwconv3x3_f32(const float* x, int64_t x_ld, const float* w9 /* [9][C], tap-major */, float* y, int64_t y_ld, int64_t N, int64_t H,
+                       int64_t W, int64_t C, int64_t dilation, int flip, void* stream);
+/* Its weight gradient: dw9[t][c] = sum over the pixels p of dy[p,c] * x[p + off_t, c].  Per-block partial sums go to the caller's
+ * workspace (diga_dwconv3x3_wgrad_workspace_bytes; 0 for an unsupported shape), a second kernel adds them in block order: no float
+ * atomics, bit-reproducible from run to run.  Rules as above, plus N > 0 and workspace_bytes >= the queried size. */
+size_t diga_dwconv3x3_wgrad_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t C);
+int diga_dwconv3x3_f32_wgrad(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dw9 /* [9][C] */, void* workspace,
+                             size_t workspace_bytes, int64_t N, int64_t H, int64_t W, int64_t C, int64_t dilation, void* stream);
+
 /* 3x3 stride-2 pad-1 max-pool with ceil_mode (Ho = ceil((H-1)/2)+1 clipped so the last window starts inside);
  * idx [N,Ho,Wo,C] uint8 = winning tap (first maximum); backward gathers, no atomics. */
 int diga_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int64_t N, int64_t H, int64_t W, int64_t C,

@@ -1590,7 +1590,128 @@ def gen_hrnet_fuse_down():
     assert os.path.getsize(os.path.join(OUT, "hrnet_fuse_down.npz")) < 1000000
 
 
-ALL = dict(hrnet_fuse_down=gen_hrnet_fuse_down, ocr_head=gen_ocr_head, trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
+# ------------------------------------------------------------------ G-daformer-head (DAFormerHead + ASPPWrapper of segformer_head.py)
+def _import_reference_daformer_head():
+    """The reference's model/networks/segformer_head.py with an mmcv stand-in that covers what DAFormerHead builds (the stand-in of
+    _import_reference_segformer_head covers `linear_fuse` only and stays as it is).  mmcv 1.x's documented behaviour:
+      ConvModule(in, out, kernel_size, stride, padding, dilation, groups, norm_cfg, act_cfg): conv (bias = False when a norm follows,
+        bias='auto') -> BatchNorm2d -> ReLU when act_cfg is given; children `conv`, `bn`, `activate`;
+      DepthwiseSeparableConvModule(in, out, kernel_size, ..., norm_cfg, act_cfg): `depthwise_conv` = ConvModule(in, in, kernel_size,
+        groups=in, ...) then `pointwise_conv` = ConvModule(in, out, 1, ...), both with the block's norm_cfg and act_cfg.
+    Those blocks of the capture are therefore pinned to mmcv's documentation, NOT its code: PARITY UNPINNED for them.  Everything else
+    that runs (MLP, the resizes, the concatenation order, ASPPWrapper, DepthwiseSeparableASPPModule, cls_seg) is the reference class."""
+    import importlib.util
+
+    class _ConvModule(torch.nn.Module):
+        def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, conv_cfg=None, norm_cfg=None,
+                     act_cfg=dict(type="ReLU")):
+            super().__init__()
+            assert conv_cfg is None and (norm_cfg is None or norm_cfg["type"] == "BN") and (act_cfg is None or act_cfg["type"] == "ReLU")
+            self.conv = torch.nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias=norm_cfg is None)
+            if norm_cfg is not None:
+                self.bn = torch.nn.BatchNorm2d(out_channels)
+            if act_cfg is not None:
+                self.activate = torch.nn.ReLU(inplace=True)
+
+        def forward(self, x):
+            x = self.conv(x)
+            if hasattr(self, "bn"):
+                x = self.bn(x)
+            return self.activate(x) if hasattr(self, "activate") else x
+
+    class _DepthwiseSeparableConvModule(torch.nn.Module):
+        def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, norm_cfg=None, act_cfg=dict(type="ReLU")):
+            super().__init__()
+            self.depthwise_conv = _ConvModule(in_channels, in_channels, kernel_size, stride, padding, dilation, groups=in_channels,
+                                              norm_cfg=norm_cfg, act_cfg=act_cfg)
+            self.pointwise_conv = _ConvModule(in_channels, out_channels, 1, norm_cfg=norm_cfg, act_cfg=act_cfg)
+
+        def forward(self, x):
+            return self.pointwise_conv(self.depthwise_conv(x))
+
+    mm = types.ModuleType("mmcv")
+    cnn = types.ModuleType("mmcv.cnn")
+    cnn.ConvModule, cnn.normal_init, cnn.DepthwiseSeparableConvModule = _ConvModule, (lambda *a, **k: None), _DepthwiseSeparableConvModule
+    mm.cnn = cnn
+    sys.modules.update({"mmcv": mm, "mmcv.cnn": cnn})
+    spec = importlib.util.spec_from_file_location("ref_daformer_head", os.path.join(REF, "model", "networks", "segformer_head.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def _daformer_run(ref, dc, sd, dtype, feats, prb, feats_eval):
+    """One train-mode step and one eval-mode pass of the reference class in `dtype`: every tensor of the capture, whole, by name."""
+    head = ref.DAFormerHead(in_channels=dc.IN_CHANNELS, channels=dc.CHANNELS, feature_strides=[4, 8, 16, 32], num_classes=dc.CLASSES,
+                            in_index=[0, 1, 2, 3], act_cfg=dict(type="ReLU"), dropout_ratio=0, norm_cfg=dict(type="BN", requires_grad=True),
+                            align_corners=False)
+    assert [(k, tuple(v.shape)) for k, v in head.state_dict().items()] == list(dc.shapes().items())
+    head.load_state_dict(sd)
+    head = head.to(dtype).train()
+    xs = [f.to(dtype).requires_grad_() for f in feats]
+    fuse = {}
+    hook = head.fuse_layer.register_forward_hook(lambda m, i, o: fuse.__setitem__("feat", o))
+    logits, raw = head(xs)
+    hook.remove()
+    (logits * prb.to(dtype)).sum().backward()
+    res = {"logits": logits, "feat": fuse["feat"], "feat_raw": raw}
+    for i, x in enumerate(xs):
+        res[f"dc{i + 1}"] = x.grad
+    for k, p in head.named_parameters():
+        res["g_" + k.replace(".", "_")] = p.grad
+    for k, b in head.named_buffers():
+        if not k.endswith("num_batches_tracked"):
+            res["b_" + k.replace(".", "_")] = b.clone()
+    nbt = {int(b) for k, b in head.named_buffers() if k.endswith("num_batches_tracked")}
+    head.eval()
+    with torch.no_grad():
+        res["logits_eval"] = head([f.to(dtype) for f in feats_eval])[0]
+    return {k: v.detach().double() for k, v in res.items()}, nbt
+
+
+def gen_daformer_head():
+    """tests/golden/daformer_head.npz: the reference's DAFormerHead (mmcv blocks: the stand-in above, parity unpinned for them) at
+    in_channels [8, 16, 24, 32], channels 32, 19 classes, N = 2, stage grids 40x28 / 20x14 / 10x7 / 5x4, Dropout2d off, in float64, and
+    for every stored quantity the class's own fp32 error against that run (err32_*).  Weights, inputs and sample positions come from
+    tests/daformer_cases.py (only their checksums are stored); logits, input gradients and the eval-mode logits (odd grids 37x29 ...)
+    are kept whole, every other tensor as a fixed sample and an L2 norm.  err32 of a sample or a whole tensor: max |fp32 - float64| over
+    what is stored, in units of the whole tensor's max |float64| (scale_*); of a norm: the L2 distance of the fp32 tensor from the
+    float64 one in units of the norm."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import daformer_cases as dc
+    ref = _import_reference_daformer_head()
+    sd = dc.state()
+    feats, feats_eval = dc.inputs(), dc.inputs(dc.GRIDS_EVAL, n=1, tag="eval")
+    prb = dc.probe((dc.BATCH, dc.CLASSES) + dc.GRIDS[0])
+    r64, nbt = _daformer_run(ref, dc, sd, torch.float64, feats, prb, feats_eval)
+    r32, nbt32 = _daformer_run(ref, dc, sd, torch.float32, feats, prb, feats_eval)
+    assert nbt == nbt32 == {4}
+    s64, s32 = dc.stored(r64), dc.stored(r32)
+    shp = dc.shapes()
+    res = {"keys": np.array(list(shp)), "shapes": np.array([",".join(str(d) for d in s) for s in shp.values()]), "nbt": np.array(4),
+           "state_sum": np.array(dc.checksum([v for k, v in sd.items() if not k.endswith("num_batches_tracked")])),
+           "inputs_sum": np.array(dc.checksum(feats + feats_eval + [prb]))}
+    for k, v in s64.items():
+        name = k[:-5] if k.endswith("_norm") else k[:-7] if k.endswith("_sample") else k
+        whole = r64[name]
+        if k.endswith("_norm"):
+            # | ||a|| - ||b|| | <= ||a - b||: the fp32 run's error in a norm is held against the L2 distance of its tensor from the
+            # float64 one (the difference of the two norms themselves is a chance figure: 3e-11 for feat_raw in this run)
+            scale = float(v)
+            err = float((r32[name] - whole).norm()) / scale
+            assert abs(float(s32[k]) - scale) <= err * scale
+        else:
+            scale = float(whole.abs().max())
+            err = float((s32[k] - v).abs().max()) / scale
+        res[k] = v
+        res["scale_" + k] = np.array(scale)
+        res["err32_" + k] = np.array(err)
+        print(f"  {k:64s} scale {scale:9.3e}  err32 {err:.2e}")
+    save("daformer_head", **res)
+    assert os.path.getsize(os.path.join(OUT, "daformer_head.npz")) < 1000000
+
+
+ALL = dict(daformer_head=gen_daformer_head, hrnet_fuse_down=gen_hrnet_fuse_down,ocr_head=gen_ocr_head, trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
            classmix=gen_classmix, centroid=gen_centroid, meanvec=gen_meanvec, aspp=gen_aspp,
            model=gen_model, step=gen_step, selftrain=gen_selftrain, translator=gen_translator, miou=gen_miou, valmiou=gen_valmiou)
 
