@@ -181,6 +181,9 @@ SIGNATURES = {
     "diga_mit_attention_fwd": (INT, [P, I64, P, I64, P, I64, P, I64, I64, I64, I64, F32, P]),
     "diga_mit_attention_bwd_workspace_bytes": (SZ, [I64, I64, I64, I64]),
     "diga_mit_attention_bwd": (INT, [P, I64, P, I64, P, P, I64, P, P, P, P, SZ, I64, I64, I64, I64, F32, P]),
+    "diga_mit_attention_hd_fwd": (INT, [P, I64, P, I64, P, I64, P, I64, I64, I64, I64, I64, F32, P]),
+    "diga_mit_attention_hd_bwd_workspace_bytes": (SZ, [I64, I64, I64, I64, I64]),
+    "diga_mit_attention_hd_bwd": (INT, [P, I64, P, I64, P, P, I64, P, P, P, P, SZ, I64, I64, I64, I64, I64, F32, P]),
     "diga_prof_enable": (INT, [INT]),
     "diga_prof_reset": (INT, []),
     "diga_prof_query": (INT, [INT, P, P]),

@@ -77,8 +77,8 @@ class Attention(nn.Module):
         self.dim = dim
         self.num_heads = num_heads
         head_dim = dim // num_heads
-        if head_dim != 64:
-            raise NotImplementedError(f"the attention kernel is built for head_dim 64 (every stage of mit_b1..b5); got {head_dim}")
+        if head_dim not in (32, 64):
+            raise NotImplementedError(f"the attention kernels are built for head_dim 32 (mit_b0) and 64 (mit_b1..b5); got {head_dim}")
         self.scale = qk_scale or head_dim ** -0.5
         self.q = nn.Linear(dim, dim, bias=qkv_bias)
         self.kv = nn.Linear(dim, dim * 2, bias=qkv_bias)
@@ -311,7 +311,7 @@ class _MitStageFn(torch.autograd.Function):
                     nk = ho * wo
                 o16 = ops.empty((M, C))
                 lse = ops.empty((B, heads, ho * wo), torch.float32) if need_grad else None
-                _lib.call("diga_mit_attention_fwd", P(q16), C, P(kv16), 2 * C, P(o16), C, P(lse), B, heads, ho * wo, nk,
+                _lib.call("diga_mit_attention_hd_fwd", P(q16), C, P(kv16), 2 * C, P(o16), C, P(lse), B, heads, C // heads, ho * wo, nk,
                           float(st["scale"]), _lib.stream())
                 x1 = ops.gemm(o16, wpr, par[bp + ".attn.proj.bias"], C, out_f32=True, residual=xcur, seg=seg_a, rows_per_seg=ho * wo)
                 b16, _, m2, r2 = ops.ln_fwd(x1, par[bp + ".norm2.weight"], par[bp + ".norm2.bias"], eps[bp + ".norm2"], save=need_grad)
@@ -401,9 +401,9 @@ class _MitStageFn(torch.autograd.Function):
                 nk = bs["nk"]
                 dq = ops.empty((M, C))
                 dkv = ops.empty((B * nk, 2 * C))
-                ws = _lib.workspace(_lib.lib.diga_mit_attention_bwd_workspace_bytes(B, heads, ho * wo, nk), dev, "mit_attn")
-                _lib.call("diga_mit_attention_bwd", P(bs["q16"]), C, P(bs["kv16"]), 2 * C, P(bs["o16"]), P(d_o), C, P(bs["lse"]), P(dq),
-                          P(dkv), P(ws), ws.numel(), B, heads, ho * wo, nk, float(st["scale"]), _lib.stream())
+                ws = _lib.workspace(_lib.lib.diga_mit_attention_hd_bwd_workspace_bytes(B, heads, C // heads, ho * wo, nk), dev, "mit_attn")
+                _lib.call("diga_mit_attention_hd_bwd", P(bs["q16"]), C, P(bs["kv16"]), 2 * C, P(bs["o16"]), P(d_o), C, P(bs["lse"]), P(dq),
+                          P(dkv), P(ws), ws.numel(), B, heads, C // heads, ho * wo, nk, float(st["scale"]), _lib.stream())
                 d_a = ops.gemm(dq, bs["wqt"], None, C)
                 has_qb, has_kvb = (bp + ".attn.q.bias") in par, (bp + ".attn.kv.bias") in par
                 gq = ops.wgrad(dq, bs["a16"], inv, bias=has_qb)
@@ -668,15 +668,11 @@ def _mit(embed_dims, depths):
     return _M
 
 
-class mit_b0(MixVisionTransformer):
-    def __init__(self, **kwargs):
-        raise NotImplementedError("mit_b0 has head_dim 32; the attention kernel is built for head_dim 64 (mit_b1..b5)")
-
-
+mit_b0 = _mit([32, 64, 160, 256], [2, 2, 2, 2])                 # head_dim 32 in every stage (the others: 64)
 mit_b1 = _mit([64, 128, 320, 512], [2, 2, 2, 2])
 mit_b2 = _mit([64, 128, 320, 512], [3, 4, 6, 3])
 mit_b3 = _mit([64, 128, 320, 512], [3, 4, 18, 3])
 mit_b4 = _mit([64, 128, 320, 512], [3, 8, 27, 3])
 mit_b5 = _mit([64, 128, 320, 512], [3, 6, 40, 3])
-for _n, _c in (("mit_b1", mit_b1), ("mit_b2", mit_b2), ("mit_b3", mit_b3), ("mit_b4", mit_b4), ("mit_b5", mit_b5)):
+for _n, _c in (("mit_b0", mit_b0), ("mit_b1", mit_b1), ("mit_b2", mit_b2), ("mit_b3", mit_b3), ("mit_b4", mit_b4), ("mit_b5", mit_b5)):
     _c.__name__ = _c.__qualname__ = _n

@@ -58,7 +58,8 @@ class SegFormerStudent(nn.Module):
             self.final.init_weights()
 
     def forward(self, x):
-        """x [N,3,H,W] -> (c2 [N,128,H/8,W/8], c4 [N,512,H/32,W/32], logits, feat): logits [N,19,H/4,W/4] and the fused feature
+        """x [N,3,H,W] -> (c2 [N,128,H/8,W/8], c4 [N,512,H/32,W/32], logits, feat) -- c2 / c4 of mit_b1..b5; mit_b0: 64 and 256
+        channels -- with logits [N,19,H/4,W/4] and the fused feature
         [N,768,H/4,W/4] with the SegFormer head; [N,19,H/4,W/4] and [N,256,H/4,W/4] with the DAFormer head; [N,19,H/32,W/32] and
         [N,256,H/32,W/32] with the ASPP head."""
         _lib.require_gpu(x)

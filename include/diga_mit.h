@@ -125,6 +125,17 @@ int diga_mit_attention_bwd(const void* q, int64_t ldq, const void* kv, int64_t l
                            const float* lse, void* dq, void* dkv, void* workspace, size_t workspace_bytes, int64_t B, int64_t heads,
                            int64_t N, int64_t Nk, float scale, void* stream);
 
+/* The same three with the head width as an argument: head_dim = 64 (mit_b1..b5; identical to the entry points above, which are
+ * thin calls into these) or 32 (mit_b0: embed dims 32/64/160/256 over 1/2/5/8 heads).  Read "64" as head_dim in the layouts
+ * above: head h at columns head_dim*h.., V at head_dim*heads + head_dim*h.., dkv [B*Nk][2*heads*head_dim].  Any other head_dim
+ * returns DIGA_EINVAL (the message names the value) without a launch; the workspace query returns 0 for it. */
+int diga_mit_attention_hd_fwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, void* out, int64_t ldo, float* lse, int64_t B,
+                              int64_t heads, int64_t head_dim, int64_t N, int64_t Nk, float scale, void* stream);
+size_t diga_mit_attention_hd_bwd_workspace_bytes(int64_t B, int64_t heads, int64_t head_dim, int64_t N, int64_t Nk);
+int diga_mit_attention_hd_bwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const void* out, const void* d_out, int64_t ldo,
+                              const float* lse, void* dq, void* dkv, void* workspace, size_t workspace_bytes, int64_t B, int64_t heads,
+                              int64_t head_dim, int64_t N, int64_t Nk, float scale, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

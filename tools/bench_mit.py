@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""MiT-B5 encoder forward + backward on synthetic 768x768 crops (the profiling harness behind profiles/r03_mit_*):
+"""MiT encoder (--arch mit_b0 .. mit_b5, default mit_b5) forward + backward on synthetic 768x768 crops (the profiling harness
+behind profiles/r03_mit_* and r27_mit_b0_b1_encoder.json):
     python tools/bench_mit.py [--batch 16] [--steps 3] [--arch mit_b5] [--fwd-only]
 prints per-family HIP-event times (diga_prof_*) and ms per pass."""
 import argparse
@@ -17,7 +18,7 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, nargs=2, default=[768, 768])
     ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--arch", default="mit_b5")
+    ap.add_argument("--arch", default="mit_b5", choices=["mit_b0", "mit_b1", "mit_b2", "mit_b3", "mit_b4", "mit_b5"])
     ap.add_argument("--fwd-only", action="store_true")
     a = ap.parse_args()
     import torch

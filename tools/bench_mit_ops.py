@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
-"""Per-shape timing of the MiT kernels at the MiT-B5 / 16 x 768x768 sizes (operands cold: a 1 GB sweep between launches
-when --cold):  python tools/bench_mit_ops.py [--cold] [--what gemm,wgrad,attn,ln,dw]"""
+"""Per-shape timing of the MiT kernels at the 16 x 768x768 sizes of MiT-B1..B5 (widths 64/128/320/512, head_dim 64) or, with
+--arch b0, of MiT-B0 (widths 32/64/160/256, head_dim 32); operands cold (a 1 GB sweep between launches) when --cold:
+    python tools/bench_mit_ops.py [--arch b0] [--cold] [--what gemm,wgrad,attn,ln,dw] [--sdpa]
+--sdpa: every attention row is followed by torch's scaled_dot_product_attention in fp16 on the SAME tensors, measured as five
+alternated warm pairs (ours, torch, ours, torch, ...; medians and all ten values), with the FLOPs / bytes / exponentials the shape
+needs and the time each of the matrix, memory and vector pipes would take for them alone."""
 import argparse
 import os
 import sys
@@ -14,6 +18,8 @@ def main():
     ap.add_argument("--cold", action="store_true")
     ap.add_argument("--what", default="gemm,wgrad,attn,ln,dw")
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--arch", default="b5", choices=["b5", "b0"], help="stage widths: b5 = 64/128/320/512 (b1..b5), b0 = 32/64/160/256")
+    ap.add_argument("--sdpa", action="store_true", help="attention rows: five alternated pairs against torch SDPA (fp16)")
     a = ap.parse_args()
     import torch
     from diga_amd import _lib
@@ -39,7 +45,29 @@ def main():
         return tot / a.reps * 1e3          # us
 
     B = 16
-    stages = [(B * 192 * 192, 64, 1, 8), (B * 96 * 96, 128, 2, 4), (B * 48 * 48, 320, 5, 2), (B * 24 * 24, 512, 8, 1)]
+    wid = {"b5": (64, 128, 320, 512), "b0": (32, 64, 160, 256)}[a.arch]
+    stages = [(B * 192 * 192, wid[0], 1, 8), (B * 96 * 96, wid[1], 2, 4), (B * 48 * 48, wid[2], 5, 2), (B * 24 * 24, wid[3], 8, 1)]
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    def pairs(ours, theirs, n=5):
+        """n alternated warm pairs -> (median ours, median theirs, all values) in us."""
+        for _ in range(2):
+            ours()
+            theirs()
+        torch.cuda.synchronize()
+        va, vb = [], []
+        for _ in range(n):
+            va.append(once(ours))
+            vb.append(once(theirs))
+        return sorted(va)[n // 2], sorted(vb)[n // 2], va, vb
+
     what = a.what.split(",")
     for si, (M, C, heads, sr) in enumerate(stages):
         hid = 4 * C
@@ -64,20 +92,69 @@ def main():
                 us = timed(lambda: ops.wgrad(dy, x, 1.0, bias=True))
                 print(f"  wgrad {name:7s} [{m}: {n}x{k}] {us:8.1f} us  {2.0 * m * n * k / us / 1e6:7.1f} TFLOP/s  {(m * (n + k) * 2) / us / 1e3:7.1f} GB/s")
         if "attn" in what:
-            N, nk = M // B, 576
+            N, nk, hd = M // B, 576, C // heads
+            scale = hd ** -0.5
             q = torch.randn((M, C), device=dev).half()
             kv = torch.randn((B * nk, 2 * C), device=dev).half()
             o = torch.empty_like(q)
             lse = torch.empty((B, heads, N), device=dev)
-            us = timed(lambda: _lib.call("diga_mit_attention_fwd", P(q), C, P(kv), 2 * C, P(o), C, P(lse), B, heads, N, nk, 0.125, _lib.stream()))
-            fl = 4.0 * B * heads * N * nk * 64
-            print(f"  attn fwd {us:8.1f} us {fl / us / 1e6:7.1f} TFLOP/s")
+
+            # head_dim 64 stays on the three old entry points (the rows every earlier record was timed through); 32 needs the new ones
+            def fwd():
+                if hd == 64:
+                    _lib.call("diga_mit_attention_fwd", P(q), C, P(kv), 2 * C, P(o), C, P(lse), B, heads, N, nk, scale, _lib.stream())
+                else:
+                    _lib.call("diga_mit_attention_hd_fwd", P(q), C, P(kv), 2 * C, P(o), C, P(lse), B, heads, hd, N, nk, scale, _lib.stream())
+
+            us = timed(fwd)
+            fl = 4.0 * B * heads * N * nk * hd
+            print(f"  attn fwd (heads {heads}, N {N}, Nk {nk}, head_dim {hd}) {us:8.1f} us {fl / us / 1e6:7.1f} TFLOP/s")
             do = torch.randn_like(q)
             dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-            ws = torch.empty(_lib.lib.diga_mit_attention_bwd_workspace_bytes(B, heads, N, nk), dtype=torch.uint8, device=dev)
-            us = timed(lambda: _lib.call("diga_mit_attention_bwd", P(q), C, P(kv), 2 * C, P(o), P(do), C, P(lse), P(dq), P(dkv), P(ws), ws.numel(),
-                                         B, heads, N, nk, 0.125, _lib.stream()))
+            ws = torch.empty(_lib.lib.diga_mit_attention_hd_bwd_workspace_bytes(B, heads, hd, N, nk), dtype=torch.uint8, device=dev)
+
+            def bwd():
+                if hd == 64:
+                    _lib.call("diga_mit_attention_bwd", P(q), C, P(kv), 2 * C, P(o), P(do), C, P(lse), P(dq), P(dkv), P(ws), ws.numel(),
+                              B, heads, N, nk, scale, _lib.stream())
+                else:
+                    _lib.call("diga_mit_attention_hd_bwd", P(q), C, P(kv), 2 * C, P(o), P(do), C, P(lse), P(dq), P(dkv), P(ws), ws.numel(),
+                              B, heads, hd, N, nk, scale, _lib.stream())
+
+            us = timed(bwd)
             print(f"  attn bwd {us:8.1f} us {14.0 / 4 * fl / us / 1e6:7.1f} TFLOP/s")
+            if a.sdpa:
+                import torch.nn.functional as F
+                # the same memory, viewed [B][heads][rows][head_dim] (strided views: no copies inside the timed region)
+                tq = q.view(B, N, heads, hd).permute(0, 2, 1, 3).requires_grad_()
+                tk = kv.view(B, nk, 2, heads, hd)[:, :, 0].permute(0, 2, 1, 3).requires_grad_()
+                tv = kv.view(B, nk, 2, heads, hd)[:, :, 1].permute(0, 2, 1, 3).requires_grad_()
+                tdo = do.view(B, N, heads, hd).permute(0, 2, 1, 3)
+
+                def t_fwd():
+                    with torch.no_grad():
+                        return F.scaled_dot_product_attention(tq, tk, tv, scale=scale)
+
+                to = F.scaled_dot_product_attention(tq, tk, tv, scale=scale)
+
+                def t_bwd():
+                    return torch.autograd.grad(to, (tq, tk, tv), tdo, retain_graph=True)
+
+                elems = float(B) * heads * N * nk                     # scores = exponentials
+                byt_f = 2.0 * (2 * M * C + B * nk * 2 * C) + 4.0 * B * heads * N
+                byt_b = 2.0 * (4 * M * C + 2 * B * nk * 2 * C) + 8.0 * B * heads * N
+                # chip rates: fp16 MFMA 2.5 PFLOP/s dense, HBM 6.3 TB/s measured copy, VALU 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz,
+                # v_exp_f32 at a quarter of that; `valu` counts the forward's ~8 full-rate fp32 instructions per score beside the exp
+                # (scale fma, max, add, cvt, and the rescales' share) -- an estimate from the source, not a counter
+                lane = 256 * 4 * 16 * 2.4e9
+                for name, m_ours, m_torch, flops, byt, nexp, nvalu in (("fwd", fwd, t_fwd, fl, byt_f, elems, 8 * elems),
+                                                                       ("bwd", bwd, t_bwd, 3.5 * fl, byt_b, 2 * elems, 20 * elems)):
+                    a_us, b_us, va, vb = pairs(m_ours, m_torch)
+                    print(f"  attn {name} vs torch SDPA fp16: ours {a_us:8.1f} us  torch {b_us:8.1f} us  ratio {b_us / a_us:5.2f}x   "
+                          f"ours {[round(v, 1) for v in va]} torch {[round(v, 1) for v in vb]}")
+                    print(f"       needs {flops / 1e9:7.2f} GFLOP ({flops / 2.5e15 * 1e6:6.1f} us of MFMA)  {byt / 1e6:7.1f} MB "
+                          f"({byt / 6.3e12 * 1e6:6.1f} us of HBM)  {nexp / 1e6:7.1f} M exp ({nexp / (lane / 4) * 1e6:6.1f} us) + "
+                          f"~{nvalu / 1e6:7.1f} M fp32 VALU lane-ops ({nvalu / lane * 1e6:6.1f} us)")
         if "ln" in what:
             x = torch.randn((M, C), device=dev)
             g, b = torch.ones(C, device=dev), torch.zeros(C, device=dev)

@@ -614,6 +614,53 @@ def gen_mit():
          b5_sums=np.array([float(o.abs().sum()) for o in o5]), b5_maxs=np.array([float(o.abs().max()) for o in o5]))
 
 
+def gen_mit_b0():
+    """The reference's mit_b0 (embed dims 32/64/160/256, heads 1/2/5/8: head_dim 32 in every stage) on the input recipe of gen_mit:
+    state-dict layout, the four features and probes, every parameter's gradient norm, strided gradient samples over all stages
+    (mit_b0.npz; the first of that recipe's two images: both would exceed 1 MiB); and forward samples of one 768x768 image (mit_b0_768.npz: stage 1 = 36 864 queries x 576 keys on one head)."""
+    from oracle import mit as om
+    ref = _import_reference_mit()
+    arch = om.MitArch(embed_dims=(32, 64, 160, 256), depths=(2, 2, 2, 2))
+    torch.manual_seed(0)
+    net = ref.mit_b0()
+    sd = om.state_dict(arch)
+    assert list(net.state_dict().keys()) == list(sd.keys())
+    net.load_state_dict(sd)
+    net.eval()
+    g = synth.gen(55)
+    # gen_mit's recipe; only the FIRST of its two images is captured: with both, x + features + probes are 1052 KiB, over the size
+    # limit of a committed file (c1 and its probe alone are 2 x 192 KiB)
+    x = (torch.rand((2, 3, 128, 96), generator=g) * 2 - 1)[:1].clone()
+    outs = net(x)
+    probes = [torch.randn(o.shape, generator=g) for o in outs]
+    sum((o * p).sum() for o, p in zip(outs, probes)).backward()
+    res = {"x": x, "keys": np.array(list(sd.keys())),
+           "shapes": np.array([",".join(str(d) for d in v.shape) for v in net.state_dict().values()])}
+    for i, (o, p) in enumerate(zip(outs, probes)):
+        res[f"c{i + 1}"] = o
+        res[f"probe{i + 1}"] = p
+    named = dict(net.named_parameters())
+    res["grad_norms"] = np.array([float(named[k].grad.norm()) for k in sd.keys()])
+    for k in ["patch_embed1.proj.weight", "patch_embed3.proj.weight", "block1.0.attn.sr.weight", "block1.1.attn.q.weight",
+              "block1.0.attn.kv.weight", "block2.1.attn.kv.weight", "block2.0.attn.q.bias", "block3.0.norm1.weight",
+              "block3.1.mlp.fc1.weight", "block3.0.attn.q.weight", "block3.1.mlp.dwconv.dwconv.weight", "block3.1.mlp.fc2.bias",
+              "block4.1.attn.proj.weight", "block4.0.attn.kv.bias", "block4.1.attn.q.weight", "norm2.weight", "norm4.bias",
+              "block2.0.attn.norm.weight", "patch_embed2.norm.bias"]:
+        gr = named[k].grad
+        step = max(1, gr.numel() // 2048)
+        res["g_" + k.replace(".", "_")] = gr.reshape(-1)[::step].clone()
+        res["gstep_" + k.replace(".", "_")] = np.array(step)
+    save("mit_b0", **res)
+    assert os.path.getsize(os.path.join(OUT, "mit_b0.npz")) < 1000000
+    x1 = torch.rand((1, 3, 768, 768), generator=synth.gen(58)) * 2 - 1
+    with torch.no_grad():
+        o1 = net(x1)
+    save("mit_b0_768", seed=np.array(58), c1_sample=o1[0].reshape(-1)[::211].clone(), c2_sample=o1[1].reshape(-1)[::53].clone(),
+         c3_sample=o1[2].reshape(-1)[::7].clone(), c4_sample=o1[3].reshape(-1)[::3].clone(),
+         sums=np.array([float(o.abs().sum()) for o in o1]), maxs=np.array([float(o.abs().max()) for o in o1]))
+    assert os.path.getsize(os.path.join(OUT, "mit_b0_768.npz")) < 1000000
+
+
 def gen_mit768bwd():
     """Backward capture at the BENCHMARK geometry (768x768: 36 864 queries against 576 keys in stage 1, MixTransfomer.py:85-144):
     the reference's mit_b1 on one image, probes on all four stage outputs (regenerated from their seed by the test: c1's probe
@@ -1711,7 +1758,7 @@ def gen_daformer_head():
     assert os.path.getsize(os.path.join(OUT, "daformer_head.npz")) < 1000000
 
 
-ALL = dict(daformer_head=gen_daformer_head, hrnet_fuse_down=gen_hrnet_fuse_down,ocr_head=gen_ocr_head, trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
+ALL = dict(mit_b0=gen_mit_b0, daformer_head=gen_daformer_head,hrnet_fuse_down=gen_hrnet_fuse_down,ocr_head=gen_ocr_head, trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
            classmix=gen_classmix, centroid=gen_centroid, meanvec=gen_meanvec, aspp=gen_aspp,
            model=gen_model, step=gen_step, selftrain=gen_selftrain, translator=gen_translator, miou=gen_miou, valmiou=gen_valmiou)
 
