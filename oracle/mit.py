@@ -4,7 +4,8 @@ Follows /root/reference/domain_adaptation/GTA5/model/networks/MixTransfomer.py:
   OverlapPatchEmbed.forward :221-228, Block.forward :175-179, Attention.forward :120-139, Mlp.forward :71-79,
   DWConv.forward :415-421, MixVisionTransformer.forward_features :370-407, mit_b1..b5 :435-475.
 Plain torch ops in the dtype of the state dict (float32, or float64 for tight kernel checks).  DropPath (timm, stochastic
-depth) is the identity here: the goldens are captured in eval() mode, where it is; dropout rates are 0 in every mit_b*.
+depth) is the identity unless the caller hands in the per-image scales of a train-mode pass (`drop_scales`; pinned by
+tests/golden/mit_b0_droppath.npz, a train() capture with given masks); dropout rates are 0 in every mit_b*.
 Pinned by tests/golden/mit.npz, a capture of the REFERENCE module (tools/gen_golden.py::gen_mit imports it with stand-ins
 for timm's / mmcv's non-arithmetic helpers only).  LayerNorm epsilons: 1e-6 for Block.norm1/norm2 and the stage norms
 (`norm_layer=partial(nn.LayerNorm, eps=1e-6)`, :438), torch's default 1e-5 for OverlapPatchEmbed.norm (:202) and
@@ -137,16 +138,21 @@ def mlp(sd, p, x, H, W):
     return F.linear(x, sd[p + ".fc2.weight"], sd[p + ".fc2.bias"])
 
 
-def block(sd, p, x, H, W, heads, sr):
-    """Block.forward :175-179 (drop_path = identity)."""
+def block(sd, p, x, H, W, heads, sr, scales=None):
+    """Block.forward :175-179.  `scales` None: drop_path = identity (eval(), or rate 0).  Otherwise a [2][B] tensor of DropPath
+    scales for this block (timm's DropPath in train(): 0 or 1 / keep per image; row 0 = the attention branch, the module's first
+    call, row 1 = the Mix-FFN branch, its second call)."""
     C = x.shape[-1]
-    x = x + attention(sd, p + ".attn", F.layer_norm(x, (C,), sd[p + ".norm1.weight"], sd[p + ".norm1.bias"], 1e-6), H, W, heads, sr)
-    x = x + mlp(sd, p + ".mlp", F.layer_norm(x, (C,), sd[p + ".norm2.weight"], sd[p + ".norm2.bias"], 1e-6), H, W)
+    a = attention(sd, p + ".attn", F.layer_norm(x, (C,), sd[p + ".norm1.weight"], sd[p + ".norm1.bias"], 1e-6), H, W, heads, sr)
+    x = x + a if scales is None else x + scales[0].to(a.dtype).view(-1, 1, 1) * a
+    m = mlp(sd, p + ".mlp", F.layer_norm(x, (C,), sd[p + ".norm2.weight"], sd[p + ".norm2.bias"], 1e-6), H, W)
+    x = x + m if scales is None else x + scales[1].to(m.dtype).view(-1, 1, 1) * m
     return x
 
 
-def forward(sd, x, arch=MIT_B5):
-    """MixVisionTransformer.forward_features :370-407 -> [c1, .., c4] (NCHW)."""
+def forward(sd, x, arch=MIT_B5, drop_scales=None):
+    """MixVisionTransformer.forward_features :370-407 -> [c1, .., c4] (NCHW).  `drop_scales`: None (DropPath is the identity), or
+    one entry per stage, each None or a [depth][2][B] tensor of DropPath scales (see block())."""
     outs = []
     B = x.shape[0]
     for s in range(len(arch.embed_dims)):
@@ -157,7 +163,8 @@ def forward(sd, x, arch=MIT_B5):
         x = x.flatten(2).transpose(1, 2)
         x = F.layer_norm(x, (C,), sd[p + ".norm.weight"], sd[p + ".norm.bias"], 1e-5)
         for i in range(arch.depths[s]):
-            x = block(sd, f"block{s + 1}.{i}", x, H, W, arch.num_heads[s], arch.sr_ratios[s])
+            sc = None if drop_scales is None or drop_scales[s] is None else drop_scales[s][i]
+            x = block(sd, f"block{s + 1}.{i}", x, H, W, arch.num_heads[s], arch.sr_ratios[s], sc)
         x = F.layer_norm(x, (C,), sd[f"norm{s + 1}.weight"], sd[f"norm{s + 1}.bias"], 1e-6)
         x = x.reshape(B, H, W, -1).permute(0, 3, 1, 2).contiguous()
         outs.append(x)

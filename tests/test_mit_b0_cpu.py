@@ -67,6 +67,41 @@ def test_oracle_forward_backward_at_the_b0_widths_vs_reference(golden):
         assert float((got - want).abs().max()) < 1e-4 * float(want.abs().max()) + 1e-7, name
 
 
+def test_drop_path_scales_layout_values_and_frequencies():
+    """`_drop_path_scales` on the CPU device (plain torch: the draw needs no kernel): per stage [depth][2][B], values 0 or 1 / keep_b with
+    keep_b = 1 - linspace(0, rate, 8)[b], nothing in eval() or at rate 0, block 0 never dropped, and over n = 4000 draws at B = 8 the
+    keep frequency of every (block, branch) within 5 standard deviations sqrt(p (1 - p) / (n B)) of keep_b."""
+    from diga_amd.model.networks import MixTransfomer as M
+    rate, B, n = 0.5, 8, 4000
+    m = M.mit_b0()
+    dev = torch.device("cpu")
+    m.eval()
+    assert m._drop_path_scales(m._cfg(), B, dev) == [None] * 4
+    m.train()
+    m.reset_drop_path(0.0)
+    assert m._drop_path_scales(m._cfg(), B, dev) == [None] * 4
+    m.reset_drop_path(rate)
+    cfg = m._cfg()
+    keep = torch.tensor([1.0 - v.item() for v in torch.linspace(0, rate, 8)])   # fp32 roundings of the double differences
+    torch.manual_seed(1234)
+    kept = torch.zeros((8, 2), dtype=torch.float64)
+    differ = torch.zeros(8, dtype=torch.bool)
+    for it in range(n):
+        sc = m._drop_path_scales(cfg, B, dev)
+        if it < 3:
+            assert [tuple(s.shape) for s in sc] == [(d, 2, B) for d in m.depths]
+        flat = torch.cat(sc, 0)                                                # [8][2][B], encoder order
+        want = (1.0 / keep).view(8, 1, 1)
+        assert bool(((flat == 0) | (flat == want)).all())
+        kept += (flat != 0).double().sum(-1)
+        differ |= ((flat[:, 0] != 0) != (flat[:, 1] != 0)).any(-1)
+    freq = kept / (n * B)
+    assert bool((freq[0] == 1.0).all())                                        # block 0: rate 0
+    bound = 5 * torch.sqrt(keep * (1 - keep) / (n * B)).double()
+    assert bool(((freq - keep.double().view(8, 1)).abs() <= bound.view(8, 1)).all()), (freq, keep)
+    assert bool(differ[1:].all()), "the attention and the Mix-FFN branch of a block must not share one draw"
+
+
 def test_head_dim_entry_points_are_declared_and_bound():
     import os
     from diga_amd import _lib

@@ -538,9 +538,17 @@ def _import_reference_mit():
             super().__init__()
             self.drop_prob = drop_prob
 
+        # train mode (gen_mit_droppath only): the mask is GIVEN, not drawn -- `scale` holds one [B] vector per call of this module
+        # within a forward pass (Block.forward calls it once per branch, attention first); the generator sets it before the pass
+        scale = None
+
         def forward(self, x):
-            assert not self.training, "the capture runs in eval(): DropPath is the identity"
-            return x
+            if not self.training:
+                return x
+            assert self.scale is not None, "the capture runs in eval() (DropPath is the identity) unless it supplies the masks"
+            s = self.scale[self.calls]
+            self.calls += 1
+            return x * s.to(x.dtype).view(x.shape[0], 1, 1)
 
     def mod(name, **attrs):
         m = types.ModuleType(name)
@@ -659,6 +667,73 @@ def gen_mit_b0():
          c3_sample=o1[2].reshape(-1)[::7].clone(), c4_sample=o1[3].reshape(-1)[::3].clone(),
          sums=np.array([float(o.abs().sum()) for o in o1]), maxs=np.array([float(o.abs().max()) for o in o1]))
     assert os.path.getsize(os.path.join(OUT, "mit_b0_768.npz")) < 1000000
+
+
+# DropPath masks of gen_mit_droppath, chosen by hand: DROPPED[block][branch] = the images whose branch is dropped (blocks in encoder
+# order: 0,1 = block1.*, 2,3 = block2.*, 4,5 = block3.*, 6,7 = block4.*; branch 0 = attention, 1 = Mix-FFN).  They contain
+#   * a branch dropped for all three images: block2.1 attention;
+#   * a branch dropped for one image only in every stage: block1.1 attention (image 1), block2.0 Mix-FFN (image 0), block3.0 attention
+#     (image 2), block4.0 Mix-FFN (image 1), block4.1 attention (image 0);
+#   * one image with a whole stage dropped: image 2 in both blocks and both branches of stage 3;
+#   * attention dropped and Mix-FFN kept for the same image (block1.1, image 1) and the reverse (block2.0, image 0);
+#   * block1.0 (rate 0: nn.Identity in the reference) untouched.
+_DROPPATH_DROPPED = [[(), ()], [(1,), ()], [(), (0,)], [(0, 1, 2), (2,)], [(2,), (2,)], [(1, 2), (2,)], [(), (1,)], [(0,), ()]]
+
+
+def gen_mit_droppath():
+    """The reference's mit_b0 in train() with GIVEN DropPath masks (mit_b0_droppath.npz): three 64x64 images (stage maps 16x16, 8x8,
+    4x4, 2x2), scales 0 or 1 / keep with keep = 1 - linspace(0, 0.3, 8)[block] (none a power of two), the masks of _DROPPATH_DROPPED.
+    Stored: the input, the [8][2][3] scales, the four features and probes, every parameter's gradient norm, strided gradient samples
+    (gen_mit_b0's list plus the weights of both branches of the fully dropped block2.1 and of its neighbours block2.0 / block3.0)."""
+    from oracle import mit as om
+    ref = _import_reference_mit()
+    arch = om.MitArch(embed_dims=(32, 64, 160, 256), depths=(2, 2, 2, 2))
+    B = 3
+    torch.manual_seed(0)
+    net = ref.mit_b0()
+    sd = om.state_dict(arch)
+    assert list(net.state_dict().keys()) == list(sd.keys())
+    net.load_state_dict(sd)
+    net.train()
+    keep = 1.0 - torch.linspace(0, 0.3, 8)
+    scales = torch.empty((8, 2, B))
+    for b in range(8):
+        for r in range(2):
+            scales[b, r] = 1.0 / keep[b]
+            for img in _DROPPATH_DROPPED[b][r]:
+                scales[b, r, img] = 0.0
+    assert bool((scales[0] == 1.0).all())
+    blocks = [blk for s in range(4) for blk in getattr(net, f"block{s + 1}")]
+    assert len(blocks) == 8 and type(blocks[0].drop_path).__name__ == "Identity"
+    for b, blk in enumerate(blocks[1:], start=1):
+        assert type(blk.drop_path).__name__ == "_DropPath"
+        blk.drop_path.scale, blk.drop_path.calls = scales[b], 0
+    g = synth.gen(59)
+    x = torch.rand((B, 3, 64, 64), generator=g) * 2 - 1
+    outs = net(x)
+    assert all(blk.drop_path.calls == 2 for blk in blocks[1:])
+    probes = [torch.randn(o.shape, generator=g) for o in outs]
+    sum((o * p).sum() for o, p in zip(outs, probes)).backward()
+    res = {"x": x, "scales": scales, "keys": np.array(list(sd.keys()))}
+    for i, (o, p) in enumerate(zip(outs, probes)):
+        res[f"c{i + 1}"] = o
+        res[f"probe{i + 1}"] = p
+    named = dict(net.named_parameters())
+    res["grad_norms"] = np.array([float(named[k].grad.norm()) for k in sd.keys()])
+    picks = ["patch_embed1.proj.weight", "patch_embed3.proj.weight", "block1.0.attn.sr.weight", "block1.1.attn.q.weight",
+             "block1.0.attn.kv.weight", "block2.1.attn.kv.weight", "block2.0.attn.q.bias", "block3.0.norm1.weight",
+             "block3.1.mlp.fc1.weight", "block3.0.attn.q.weight", "block3.1.mlp.dwconv.dwconv.weight", "block3.1.mlp.fc2.bias",
+             "block4.1.attn.proj.weight", "block4.0.attn.kv.bias", "block4.1.attn.q.weight", "norm2.weight", "norm4.bias",
+             "block2.0.attn.norm.weight", "patch_embed2.norm.bias"]
+    for blk in ("block2.0", "block2.1", "block3.0"):
+        picks += [f"{blk}.{n}.weight" for n in ("attn.q", "attn.kv", "attn.proj", "attn.sr", "mlp.fc1", "mlp.dwconv.dwconv", "mlp.fc2")]
+    for k in dict.fromkeys(picks):
+        gr = named[k].grad
+        step = max(1, gr.numel() // 2048)
+        res["g_" + k.replace(".", "_")] = gr.reshape(-1)[::step].clone()
+        res["gstep_" + k.replace(".", "_")] = np.array(step)
+    save("mit_b0_droppath", **res)
+    assert os.path.getsize(os.path.join(OUT, "mit_b0_droppath.npz")) < 1000000
 
 
 def gen_mit768bwd():
@@ -1758,7 +1833,7 @@ def gen_daformer_head():
     assert os.path.getsize(os.path.join(OUT, "daformer_head.npz")) < 1000000
 
 
-ALL = dict(mit_b0=gen_mit_b0, daformer_head=gen_daformer_head,hrnet_fuse_down=gen_hrnet_fuse_down,ocr_head=gen_ocr_head, trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
+ALL = dict(mit_b0_droppath=gen_mit_droppath, mit_b0=gen_mit_b0,daformer_head=gen_daformer_head,hrnet_fuse_down=gen_hrnet_fuse_down,ocr_head=gen_ocr_head, trainmiou=gen_trainmiou, aspp_dropout=gen_aspp_dropout, valmiou_full=gen_valmiou_full, full768b8=gen_full768b8, full512x1024b8=gen_full512x1024b8, traj25=gen_traj25, traj768=gen_traj768, selftraj10=gen_selftraj10, mit=gen_mit, segformer_head=gen_segformer_head, mit768bwd=gen_mit768bwd, full768=gen_full768, full512x1024=gen_full512x1024, ohem=gen_ohem, ce=gen_ce, distill=gen_distill, upsample=gen_upsample, ema=gen_ema, sgd=gen_sgd,
            classmix=gen_classmix, centroid=gen_centroid, meanvec=gen_meanvec, aspp=gen_aspp,
            model=gen_model, step=gen_step, selftrain=gen_selftrain, translator=gen_translator, miou=gen_miou, valmiou=gen_valmiou)
 
